@@ -3,11 +3,19 @@
 
     python bench.py --gpus N --steps K --warmup W                     # headline: BASELINE configs[1]
     python bench.py --config {gsf32,bpf4096,kalman64} --gpus N ...    # configs[2..4]
+    python bench.py ... --full                                        # + finite_frac, roofline, cpu_baseline
+    python bench.py ... --dump-outputs DIR                            # + DIR/<name>.npy of the last timed step
 
 One "step" = one pass of the hot path (the whole T-step scan) over one batch of synthetic trajectories already
 resident in HBM.  Observations are drawn FROM THE MODEL ITSELF on the device (bf_sample_ssm_f32 =
-NonlinearSSM.sample, gaussfiltax/models.py:240-289), so the filters track and stay finite; the JSON line reports the
-fraction of trajectories whose final posterior is finite.
+NonlinearSSM.sample, gaussfiltax/models.py:240-289), so the filters track and stay finite; with --full the JSON line
+reports the fraction of trajectories whose final posterior is finite.
+
+A plain run (no --full) sets up, warms up, times --steps steps and prints the headline line (metric, value, unit,
+ms_per_step, ...); everything else it can measure runs only with --full.  --dump-outputs writes, after the timed steps,
+what the timed path returned in its last step as float32 .npy files: a fixed, seeded sample of trajectories and time
+steps (sample_idx), under 64 MB in all.  The inputs depend only on the arguments, so two builds run with the same
+arguments can be compared output for output.  With N > 1, rank 0 writes its own shard.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU; the process group is initialised before anything else
 touches the GPU): trajectories are independent, the batch axis shards with no traffic during the scan, and the
@@ -15,8 +23,8 @@ per-trajectory posterior summaries are all-gathered over RCCL inside the timed r
   * kalman4 (headline):           every rank filters its own 65 536 trajectories            -> "scaling": "weak"
   * gsf32 / bpf4096 / kalman64:   BASELINE's total batch (16 384 / 8 192 / 32 768) is split
                                   over the ranks with distributed.shard_bounds               -> "scaling": "strong"
-Rank 0 prints ONE JSON line carrying `roofline` (dominant kernel: algorithmic bytes / flops / issue slots per launch over
-its HIP-event time) and, for the headline at N = 1, `cpu_baseline` (the oracle's plain-C port on the host cores, a
+Rank 0 prints ONE JSON line; with --full it also carries `roofline` (dominant kernel: algorithmic bytes / flops / issue
+slots per launch over its HIP-event time) and, at N = 1, `cpu_baseline` (the oracle's plain-C port on the host cores, a
 bounded sample of the same workload -- a reported baseline, not the target).
 """
 import argparse
@@ -151,6 +159,35 @@ def profiled(name):
         return None, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_idx(n, k, seed=0):
+    """k sorted indices of range(n) drawn with a fixed seed, the last one always among them (all of range(n) if n <= k)."""
+    if n <= k:
+        return np.arange(n)
+    rng = np.random.default_rng(seed)
+    return np.sort(np.append(rng.choice(n - 1, k - 1, replace=False), n - 1))
+
+
+def dump_outputs(out_dir, outputs, rows, times):
+    """Write {name: (tensor, time axis or None)} -- batch on axis 0 -- as out_dir/name.npy: the sample_idx rows of the batch
+    axis and, where there is one, the sample_idx steps of the time axis, as float32 (float64 stays float64)."""
+    import torch
+    arrays = {}
+    for name, (t, t_axis) in outputs.items():
+        x = t.index_select(0, torch.as_tensor(sample_idx(t.shape[0], rows), device=t.device))
+        if t_axis is not None:
+            x = x.index_select(t_axis, torch.as_tensor(sample_idx(t.shape[t_axis], times), device=t.device))
+        arrays[name] = x.cpu().numpy().astype(np.float64 if x.dtype == torch.float64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ workloads
 def make_kalman4(args, rank, world, device):
     """BASELINE configs[1]: n = 4, m = 2, T = 10 000, B = 65 536 per GPU, FULL5 in the reference layout."""
@@ -180,9 +217,12 @@ def make_kalman4(args, rank, world, device):
         p = st["post"]
         return float((torch.isfinite(p.means[:, 0, -1]).all(dim=1) & torch.isfinite(p.covariances[:, 0, -1]).all(dim=(1, 2))).float().mean())
 
+    def outputs():
+        return {k: (getattr(st["post"], k), 2) for k in bfa.FULL5}
+
     bps = int(lib.bf_bytes_per_step(n, m, 1, None))      # 4m + 4(1 + 2n + 2n^2) = 172
-    return dict(kernels=kernels, summary=summary, finite=finite, units=B * T, total_units=world * B * T, scaling="weak",
-                gather_rows=world * B, a=a, T=T,
+    return dict(kernels=kernels, summary=summary, finite=finite, outputs=outputs, dump_sample=(256, 256), units=B * T,
+                total_units=world * B * T, scaling="weak", gather_rows=world * B, a=a, T=T,
                 roofline=lambda ms: {"bound": "hbm", "achieved": bps * B * T / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                      "kernel": "kf_scan_group_kernel<n=4,m=2,NL=2,EMIT_STAGED>", "bytes_per_step": bps},
                 workload=f"batched Kalman filter state_dim=4 obs_dim=2 T={T} batch={B} per GPU, K=1, all five posterior streams "
@@ -213,7 +253,9 @@ def make_gsf32(args, rank, world, device):
 
     def kernels():
         if collapsed:      # COLLAPSED mode: per step only the moment-matched Gaussian leaves the chip
-            _, st["carry"], _ = bfa.gaussian_sum_filter(p, y, K, 1, initial_means=init, fields=(), return_carry=True, return_collapsed=True)
+            st["collapsed"] = None     # released before the call allocates the next step's moments
+            _, st["carry"], st["collapsed"] = bfa.gaussian_sum_filter(p, y, K, 1, initial_means=init, fields=(), return_carry=True,
+                                                                      return_collapsed=True)
             return
         carry = None
         for t0 in range(0, T, Tc):
@@ -230,6 +272,14 @@ def make_gsf32(args, rank, world, device):
         c = st["carry"]
         return float((torch.isfinite(c.weights).all(dim=1) & torch.isfinite(c.means).all(dim=(1, 2))).float().mean())
 
+    def outputs():
+        o = {"carry_" + k: (v, None) for k, v in st["carry"]._asdict().items()}
+        if collapsed:
+            o.update(collapsed_means=(st["collapsed"][0], 1), collapsed_covariances=(st["collapsed"][1], 1))
+        else:
+            o.update({k: (getattr(st["post"], k), 2) for k in bfa.FULL5})
+        return o
+
     if collapsed:
         bps, fl = 4 * m + 4 * (n + n * n + K), 1.4e5
         roof = lambda ms: {"bound": "mfma", "achieved": fl * B * T / (ms * 1e-3) / 1e12, "peak": FP32_PEAK_TFS, "unit": "TFLOP/s",
@@ -241,8 +291,8 @@ def make_gsf32(args, rank, world, device):
         roof = lambda ms: {"bound": "hbm", "achieved": bps * B * T / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                            "kernel": "gsf_scan_kernel<8,4,NL=2,EMIT_STAGED,L96_PICK>", "bytes_per_step": bps}
         work = f"Gaussian-sum filter 32 components, Lorenz-96[{args.l96_mode}] state_dim=8 obs_dim=4, T={T} batch={Bt}, FULL5 in T-chunks of {Tc}"
-    return dict(kernels=kernels, summary=summary, finite=finite, units=B * T, total_units=Bt * T, scaling="strong", gather_rows=Bt,
-                roofline=roof, workload=work + ", observations drawn from the model", extra={"batch_total": Bt, "batch_this_rank": B, "T": T},
+    return dict(kernels=kernels, summary=summary, finite=finite, outputs=outputs, dump_sample=(32, 32), units=B * T, total_units=Bt * T,
+                scaling="strong", gather_rows=Bt, roofline=roof, workload=work + ", observations drawn from the model", extra={"batch_total": Bt, "batch_this_rank": B, "T": T},
                 cpu=lambda: cpu_baseline_gsf(y[:4096].cpu().numpy(), init[:4096].cpu().numpy(), K, args.l96_mode, T))
 
 
@@ -276,12 +326,18 @@ def make_kalman64(args, rank, world, device):
         c = st["carry"]
         return float((torch.isfinite(c.means.reshape(B, n)).all(dim=1) & torch.isfinite(c.covariances.reshape(B, n * n)).all(dim=1)).float().mean())
 
+    def outputs():       # the last chunk's posterior and the carry out of it
+        o = {"carry_" + k: (v, None) for k, v in st["carry"]._asdict().items()}
+        o.update({k: (getattr(st["post"], k), 2) for k in bfa.FULL5})
+        return o
+
     # algorithmic flop per step of the reference's formulation (2 n^3 x 2 predict, H P, S, the gain solve,
     # K S K^T ~ 2.0e6).  The kernel runs the five products as three-term bf16 splits (6 x v_mfma_f32_32x32x16_bf16 per
     # K = 16 chunk, fp32 accumulation, fp32-level rounding) plus a ~2 900-instruction fp32 vector Cholesky; "peak" stays the
     # fp32 matrix / vector peak the same algebra would be priced against in fp32
     bps, fl = 4 * m + 4 * (1 + 2 * n + 2 * n * n), 2.0e6
-    return dict(kernels=kernels, summary=summary, finite=finite, units=B * T, total_units=Bt * T, scaling="strong", gather_rows=Bt, a=a, T=T,
+    return dict(kernels=kernels, summary=summary, finite=finite, outputs=outputs, dump_sample=(32, 32), units=B * T, total_units=Bt * T,
+                scaling="strong", gather_rows=Bt, a=a, T=T,
                 roofline=lambda ms: {"bound": "mfma", "achieved": fl * B * T / (ms * 1e-3) / 1e12, "peak": FP32_PEAK_TFS, "unit": "TFLOP/s",
                                      "kernel": "kf_scan_mfma5_kernel<64,32>", "flop_per_step": fl, "bytes_per_step": bps,
                                      "hbm_GBs": bps * B * T / (ms * 1e-3) / 1e9,
@@ -321,6 +377,9 @@ def make_bpf4096(args, rank, world, device):
     def finite():
         return float(torch.isfinite(st["out"]["mean"]).all(dim=(1, 2)).float().mean())
 
+    def outputs():
+        return {k: (v, 1) for k, v in st["out"].items()}
+
     prof, src = profiled("r03_pmc_bpf4096.json")
     ipp = (prof or {}).get("valu_wave_inst_per_particle_step_x64")   # SQ_INSTS_VALU per launch / particle-steps per launch x 64 lanes
     bps = 4 * m + 4 * (n + 3)
@@ -342,12 +401,41 @@ def make_bpf4096(args, rank, world, device):
             r["achieved"] = None
         return r
 
-    return dict(kernels=kernels, summary=summary, finite=finite, units=B * T, total_units=Bt * T, scaling="strong", gather_rows=Bt,
-                roofline=roof,
+    return dict(kernels=kernels, summary=summary, finite=finite, outputs=outputs, dump_sample=(256, 256), units=B * T, total_units=Bt * T,
+                scaling="strong", gather_rows=Bt, roofline=roof,
                 workload=f"bootstrap particle filter {N} particles, Lorenz-96 state_dim=16 obs_dim=8, T={T} batch={Bt}, SUMMARY output, "
                          "observations drawn from the model",
                 extra={"batch_total": Bt, "batch_this_rank": B, "T": T, "particles": N},
                 cpu=lambda: cpu_baseline_bpf(y[:256].cpu().numpy(), N, T))
+
+
+def roofline(args, w, world, kernel_ms):
+    """--full: the dominant kernel's figures at the measured kernel time, with HBM traffic from committed rocprofv3 passes."""
+    roof = w["roofline"](kernel_ms)
+    if roof.get("achieved") is not None:
+        roof["frac"] = roof["achieved"] / roof["peak"]
+    roof["kernel_ms"] = kernel_ms
+    roof["traffic"] = None         # HBM bytes from PMC counters: not collected inside this run (see profiles/ for the rocprofv3 passes)
+    if args.config == "kalman4" and w["extra"]["batch_per_gpu"] == 65536 and w["T"] == 10000:
+        prof, src = profiled("r03_bench_%s_summary.json" % args.layout)
+        if prof is None:
+            prof, src = profiled("r02_bench_%s_summary.json" % args.layout)
+        if prof and "pmc" in prof:
+            try:
+                roof["traffic_profiled"] = {"bytes": (prof["pmc"]["WRITE_SIZE"]["mean_per_dispatch"] + prof["pmc"]["FETCH_SIZE"]["mean_per_dispatch"]) * 1024.0,
+                                            "source": src}
+            except KeyError:
+                pass
+    if args.config == "gsf32" and args.mode == "full5" and w["extra"]["batch_total"] == 16384 and args.chunk == 500 and world == 1:
+        prof, src = profiled("r03_pmc_gsf32_traffic.json")     # HBM bytes per 500-step chunk from separate rocprofv3 --pmc passes
+        if prof and "pmc" in prof:
+            try:
+                roof["traffic_profiled"] = {"bytes_per_chunk_launch": (prof["pmc"]["WRITE_SIZE"]["mean_per_dispatch"] +
+                                                                       prof["pmc"]["FETCH_SIZE"]["mean_per_dispatch"]) * 1024.0,
+                                            "algorithmic_bytes_per_chunk_launch": prof.get("algorithmic_bytes_per_dispatch"), "source": src}
+            except KeyError:
+                pass
+    return roof
 
 
 MAKERS = {"kalman4": make_kalman4, "gsf32": make_gsf32, "bpf4096": make_bpf4096, "kalman64": make_kalman64}
@@ -362,7 +450,7 @@ def main():
     ap.add_argument("--T", type=int, default=0)
     ap.add_argument("--layout", default="reference", choices=["reference", "batch_inner"])
     ap.add_argument("--emit-mode", type=int, default=-1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--chunk", type=int, default=500,
                     help="gsf32 only: steps per launch (the posterior history of one chunk must fit HBM: 304 MB per step)")
     ap.add_argument("--mode", default="full5", choices=["full5", "collapsed"],
@@ -375,7 +463,14 @@ def main():
                     help="kalman4 = BASELINE configs[1] (headline, default); gsf32 / bpf4096 / kalman64 = configs[2..4]")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="bf_set_option(NAME, VALUE) before the run (tuning experiments; repeatable), e.g. --option bpf_arith=1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: finite_frac, roofline (HIP-event kernel time, "
+                         "profiled traffic) and, at N = 1, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed sample of what the last step returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -419,12 +514,15 @@ def main():
     if group:
         dist.barrier()
     torch.cuda.synchronize()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # --full: HIP events bracket the engine's kernels (it launches on torch's current stream) for the roofline's kernel time
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        ev[i][0].record()               # the engine launches on torch's current stream: these events bracket its kernels
+        if ev:
+            ev[i][0].record()
         w["kernels"]()
-        ev[i][1].record()
+        if ev:
+            ev[i][1].record()
         if group:
             gathered["t"] = bdist.all_gather_summaries(w["summary"](), w["gather_rows"], force=True)
     torch.cuda.synchronize()
@@ -437,49 +535,27 @@ def main():
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    kernel_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
-    fin = torch.tensor([w["finite"]() * w["units"]], device=device, dtype=torch.float64)
-    if group:
-        dist.all_reduce(fin)
-    finite_frac = float(fin.item()) / w["total_units"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w["outputs"](), *w["dump_sample"])
 
+    line = {
+        "metric": "filter timesteps/sec (batch x T)", "value": w["total_units"] * args.steps / elapsed, "unit": "timesteps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": w["scaling"], "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": w["workload"], **w["extra"],
+                   "parallelism": f"batch-sharded x{world}" + (" + RCCL all-gather of summaries" if group else "")},
+        **({"options": args.option} if args.option else {}),
+    }
+    if args.full:
+        fin = torch.tensor([w["finite"]() * w["units"]], device=device, dtype=torch.float64)
+        if group:
+            dist.all_reduce(fin)
+        line["finite_frac"] = float(fin.item()) / w["total_units"]
+        if rank == 0:
+            line["roofline"] = roofline(args, w, world, float(np.mean([s.elapsed_time(e) for s, e in ev])))
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = w["cpu"]() if "cpu" in w else cpu_baseline(w["a"], w["T"])
     if rank == 0:
-        roof = w["roofline"](kernel_ms)
-        if roof.get("achieved") is not None:
-            roof["frac"] = roof["achieved"] / roof["peak"]
-        roof["kernel_ms"] = kernel_ms
-        roof["traffic"] = None         # HBM bytes from PMC counters: not collected inside this run (see profiles/ for the rocprofv3 passes)
-        if args.config == "kalman4" and w["extra"]["batch_per_gpu"] == 65536 and w["T"] == 10000:
-            prof, src = profiled("r03_bench_%s_summary.json" % args.layout)
-            if prof is None:
-                prof, src = profiled("r02_bench_%s_summary.json" % args.layout)
-            if prof and "pmc" in prof:
-                try:
-                    roof["traffic_profiled"] = {"bytes": (prof["pmc"]["WRITE_SIZE"]["mean_per_dispatch"] + prof["pmc"]["FETCH_SIZE"]["mean_per_dispatch"]) * 1024.0,
-                                                "source": src}
-                except KeyError:
-                    pass
-        if args.config == "gsf32" and args.mode == "full5" and w["extra"]["batch_total"] == 16384 and args.chunk == 500 and world == 1:
-            prof, src = profiled("r03_pmc_gsf32_traffic.json")     # HBM bytes per 500-step chunk from separate rocprofv3 --pmc passes
-            if prof and "pmc" in prof:
-                try:
-                    roof["traffic_profiled"] = {"bytes_per_chunk_launch": (prof["pmc"]["WRITE_SIZE"]["mean_per_dispatch"] +
-                                                                           prof["pmc"]["FETCH_SIZE"]["mean_per_dispatch"]) * 1024.0,
-                                                "algorithmic_bytes_per_chunk_launch": prof.get("algorithmic_bytes_per_dispatch"), "source": src}
-                except KeyError:
-                    pass
-        line = {
-            "metric": "filter timesteps/sec (batch x T)", "value": w["total_units"] * args.steps / elapsed, "unit": "timesteps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": w["scaling"], "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": w["workload"], **w["extra"],
-                       "parallelism": f"batch-sharded x{world}" + (" + RCCL all-gather of summaries" if group else "")},
-            "finite_frac": finite_frac,
-            "roofline": roof,
-            **({"options": args.option} if args.option else {}),
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = w["cpu"]() if "cpu" in w else cpu_baseline(w["a"], w["T"])
         print(json.dumps(line), flush=True)
     if group:
         dist.destroy_process_group()

@@ -7,7 +7,7 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $root/bench.py --steps 5 --warmup 1 --no-cpu-baseline "$@" > $out/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $root/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline "$@" > $out/trace.log 2>&1
 # PMC passes: the same launch (B=65536, T=10000, FULL5) through scripts/kf_one.py
 export PB=65536 PT=10000 PF=full5 PR=2
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 $root/scripts/kf_one.py > $out/pmc_write.log 2>&1
@@ -16,7 +16,7 @@ rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LD
 python3 - <<PY
 import csv, glob, json, collections
 out = "$out"
-summary = {"tag": "$tag", "command": "bench.py --steps 5 --warmup 1 --no-cpu-baseline " + "$*"}
+summary = {"tag": "$tag", "command": "bench.py --steps 5 --warmup 1 --full --no-cpu-baseline " + "$*"}
 for f in glob.glob(out + "/trace/**/*kernel_stats.csv", recursive=True):
     rows = list(csv.DictReader(open(f)))
     summary["kernel_stats"] = [r for r in rows if "kf_scan" in r.get("Name", "")] or rows[:5]

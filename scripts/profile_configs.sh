@@ -6,7 +6,7 @@ out=$root/gpurun_out/profc_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for c in gsf32 kalman64 bpf4096; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/$c -- python3 $root/bench.py --config $c --steps 2 --warmup 1 > $out/$c.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/$c -- python3 $root/bench.py --config $c --steps 2 --warmup 1 --full > $out/$c.log 2>&1
   f=$(find $out/$c -name "*kernel_stats.csv" | head -1)
   echo "== $c"; grep -h '"metric"' $out/$c.log | cut -c1-200
   python3 - <<PY

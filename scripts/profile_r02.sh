@@ -23,8 +23,8 @@ PY
 
 if [[ $what == *headline* ]]; then
   echo "== headline bench (default flags)"
-  python3 $root/bench.py > $out/bench_line.json 2> $out/bench_line.err; cut -c1-600 $out/bench_line.json
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $root/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $out/trace.log 2>&1
+  python3 $root/bench.py --full > $out/bench_line.json 2> $out/bench_line.err; cut -c1-600 $out/bench_line.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $root/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline > $out/trace.log 2>&1
   stats $out/trace $out/bench_reference_kernel_stats.csv
   grep -h '"metric"' $out/trace.log | cut -c1-300 > $out/bench_line_profiled.json
   export PB=65536 PT=10000 PF=full5 PR=2
@@ -55,7 +55,7 @@ if [[ $what == *others* ]]; then
   for c in "gsf32" "gsf32 --l96-mode as_written" "gsf32 --mode collapsed" "kalman64" "bpf4096"; do
     tag=$(echo $c | tr -d ' -' )
     echo "== $c"
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out/t_$tag -- python3 $root/bench.py --config $c --steps 3 --warmup 1 > $out/$tag.log 2>&1
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out/t_$tag -- python3 $root/bench.py --config $c --steps 3 --warmup 1 --full > $out/$tag.log 2>&1
     grep -h '"metric"' $out/$tag.log >> $out/other_configs.jsonl; grep -h '"metric"' $out/$tag.log | cut -c1-400
     tail -3 $out/$tag.log | grep -v metric | cut -c1-300
     stats $out/t_$tag $out/${tag}_kernel_stats.csv

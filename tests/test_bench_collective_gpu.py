@@ -37,7 +37,7 @@ def test_bench_under_torchrun_one_rank(config):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--config", config] + SMALL[config]
+           "--full", "--no-cpu-baseline", "--config", config] + SMALL[config]
     d = _line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     assert d["n_gpus"] == 1 and d["scaling"] in ("weak", "strong") and d["steps"] == 2 and d["warmup"] == 1
     assert "RCCL all-gather" in d["config"]["parallelism"]
@@ -50,7 +50,7 @@ def test_bench_force_collective_flag():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(_free_port()))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-collective", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + SMALL["kalman4"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-collective", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"] + SMALL["kalman4"]
     d = _line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     assert d["n_gpus"] == 1 and "RCCL all-gather" in d["config"]["parallelism"] and d["roofline"]["frac"] > 0
     # ... and without the flag the plain single-GPU path (no process group) prints the same schema
