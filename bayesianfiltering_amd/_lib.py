@@ -42,6 +42,14 @@ class bf_carry(C.Structure):
 _FP = C.POINTER(C.c_float)
 
 
+class bf_smooth_desc(C.Structure):
+    _fields_ = [("means", bf_stream), ("covs", bf_stream), ("cross_covs", bf_stream)]
+
+
+class bf_smooth_carry(C.Structure):
+    _fields_ = [("m_in", C.c_void_p), ("P_in", C.c_void_p), ("m_out", C.c_void_p), ("P_out", C.c_void_p)]
+
+
 class bf_lgssm(C.Structure):
     _fields_ = [("n", C.c_int32), ("dq", C.c_int32), ("m", C.c_int32), ("dr", C.c_int32),
                 ("A", _FP), ("G", _FP), ("H", _FP), ("D", _FP), ("q0", _FP), ("r0", _FP), ("Q", _FP), ("R", _FP),
@@ -118,6 +126,11 @@ SYMBOLS = {
     "bf_random_split": (C.c_int, [C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_uint32)]),
     "bf_kalman_filter_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
                                        C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
+    "bf_smoother_abi_check": (C.c_int, [C.c_size_t, C.c_size_t]),
+    "bf_rts_smoother_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_out_desc), C.c_int64, C.c_int64,
+                                      C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p]),
+    "bf_eks_smoother_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_out_desc), C.c_int64,
+                                      C.c_int64, C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p]),
 }
 
 _lib = None
@@ -144,6 +157,8 @@ def load():
     # the structs above mirror include/bayesfilt.h by hand: let the library compare layouts before anything is launched
     if lib.bf_abi_check(HEADER_VERSION, C.sizeof(bf_out_desc), C.sizeof(bf_lgssm), C.sizeof(bf_model), C.sizeof(bf_bpf_model),
                         C.sizeof(bf_bpf_out)) != BF_OK:
+        raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
+    if lib.bf_smoother_abi_check(C.sizeof(bf_smooth_desc), C.sizeof(bf_smooth_carry)) != BF_OK:
         raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
     _lib = lib
     return lib

@@ -39,7 +39,8 @@ static size_t gen_lds_floats(int n, int m, int KP) {
 }
 
 // Host side: registry model -> one constant block {A, Hm, Gq0, Dr0, R, r0, GQG[steps], DRD[steps]} on the device.
-static int gen_fill(const bf_model* p, long long T, GenModel& g, std::vector<float>& blk) {
+// (also validates the registry model of the extended smoother, rts_smoother.hip)
+int gen_fill(const bf_model* p, long long T, GenModel& g, std::vector<float>& blk) {
   const int n = p->n, m = p->m, dq = p->dq, dr = p->dr;
   g.dyn_id = p->dyn_id; g.emi_id = p->emi_id; g.n = n; g.dq = dq; g.m = m; g.dr = dr;
   for (int i = 0; i < 8; ++i) g.dth[i] = g.eth[i] = 0.f;

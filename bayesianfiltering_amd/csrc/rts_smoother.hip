@@ -1,0 +1,403 @@
+// Host side of the RTS smoother (rts_smoother.hpp): validation of the layouts, the register instances for n <= 8 and the
+// run-time-dimension kernel for every other n (one wave per trajectory, the smoother's matrices in LDS).
+//
+// Register instances (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): every instance, n = 1 ... 8, both data paths,
+// all three dynamics kinds, builds without scratch.  Strided path, VGPRs (arch + acc) / waves per SIMD: n = 1: 24-48 / 8,
+// n = 2: 44-67 / 7-8, n = 3: 79-104 / 4-6, n = 4: 131-168 / 3, n = 5: 189-206 / 2, n = 6 ... 8: 266-481 / 1 (the five
+// n x n matrices of a step plus the carry spill into the accumulation registers, not to memory).  Staged path (n <= 4,
+// plus the chunk's prefetch registers): n = 1: 76-114 / 4-6, n = 2: 125-180 / 2-4, n = 3: 261-357 / 1, n = 4: 255-343 / 1-2.
+// The run-time-dimension kernel serves n > 8 and "force_generic" = 1.
+#include <cstring>
+#include <vector>
+#include "rts_smoother.hpp"
+#include "generic_device.hpp"
+
+namespace bf {
+
+int gen_fill(const bf_model* p, long long T, GenModel& g, std::vector<float>& blk);  // generic_scan.hip
+
+// ---- run-time-dimension kernel -----------------------------------------------------------------------------------
+// One 64-lane workgroup per trajectory.  LDS: five n x ld matrices (P, P^s, P-, X, W) and four vectors.  Per step:
+// W <- F_t (registry dynamics; linear: A read from the constant block), X = F P, [recompute: P- = X F^T + GQG_t,
+// m- = F m + G q0], W <- chol(P-) left-looking (one column per barrier), X <- L^-T L^-1 X (a column per lane),
+// C = X^T P^s (straight to HBM), m^s <- m + X^T (m^s - m-), P^s <- P^s - P-, P- <- X^T (P^s), P <- P + P- X, swap P / P^s.
+struct RtsGen {
+  int n, kind;          // RTS_LIN, RTS_LIN_RECOMPUTE, RTS_EXT
+  const float* A;       // [n][n]            (linear kinds)
+  const float* GQG;     // [q_steps][n][n]   (recompute)
+  const float* Gq0;     // [n]               (recompute)
+  int q_tv;
+};
+
+__host__ __device__ inline int rts_gen_ld(int n) { return n + 1; }
+static inline size_t rts_gen_lds_floats(int n) { return 5 * (size_t)n * rts_gen_ld(n) + 4 * (size_t)n; }
+
+__global__ void __launch_bounds__(64) rts_generic_kernel(RtsGen c, GenModel g, RtsViews v, long long T) {
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const int n = c.n, ld = rts_gen_ld(n), nn = n * n;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* P = lds;
+  float* Ps = P + n * ld;
+  float* Pp = Ps + n * ld;
+  float* X = Pp + n * ld;
+  float* W = X + n * ld;
+  float* m = W + n * ld;
+  float* ms = m + n;
+  float* mp = ms + n;
+  float* tv = mp + n;
+  const bool want_c = v.Cs.p != nullptr;
+  auto at = [&](const SView& s, long long t, int e) { return b * s.sB + t * s.sT + e * s.sE; };
+
+  long long t = T - 1;
+  if (v.m_in) {
+    for (int e = tid; e < n; e += 64) ms[e] = v.m_in[b * n + e];
+    for (int e = tid; e < nn; e += 64) Ps[(e / n) * ld + e % n] = v.P_in[b * nn + e];
+  } else {
+    for (int e = tid; e < n; e += 64) { const float x = v.m.p[at(v.m, t, e)]; ms[e] = x; v.ms.p[at(v.ms, t, e)] = x; }
+    for (int e = tid; e < nn; e += 64) { const float x = v.P.p[at(v.P, t, e)]; Ps[(e / n) * ld + e % n] = x; v.Ps.p[at(v.Ps, t, e)] = x; }
+    --t;
+  }
+  wave_lds_sync();
+  for (; t >= 0; --t) {
+    for (int e = tid; e < n; e += 64) m[e] = v.m.p[at(v.m, t, e)];
+    for (int e = tid; e < nn; e += 64) P[(e / n) * ld + e % n] = v.P.p[at(v.P, t, e)];
+    if (c.kind != RTS_LIN_RECOMPUTE) {
+      for (int e = tid; e < n; e += 64) mp[e] = v.pm.p[at(v.pm, t, e)];
+      for (int e = tid; e < nn; e += 64) Pp[(e / n) * ld + e % n] = v.pP.p[at(v.pP, t, e)];
+    }
+    wave_lds_sync();
+    const float* F;
+    int ldf;
+    if (c.kind == RTS_EXT) {
+      const float u0 = v.u ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+      gen_dyn_linearize<64>(g, m, u0, W, ld, tv, tid);
+      wave_lds_sync();
+      F = W;
+      ldf = ld;
+    } else {
+      F = c.A;
+      ldf = n;
+    }
+    for (int e = tid; e < nn; e += 64) {  // X = F P
+      const int i = e / n, j = e - i * n;
+      float s = F[i * ldf] * P[j];
+      for (int k = 1; k < n; ++k) s = fmaf(F[i * ldf + k], P[k * ld + j], s);
+      X[i * ld + j] = s;
+    }
+    wave_lds_sync();
+    if (c.kind == RTS_LIN_RECOMPUTE) {
+      const float* q = c.GQG + (c.q_tv ? t * nn : 0);
+      for (int e = tid; e < nn; e += 64) {  // P- = (F P) F^T + G Q_t G^T
+        const int i = e / n, j = e - i * n;
+        float s = X[i * ld] * F[j * ldf];
+        for (int k = 1; k < n; ++k) s = fmaf(X[i * ld + k], F[j * ldf + k], s);
+        Pp[i * ld + j] = s + q[e];
+      }
+      for (int i = tid; i < n; i += 64) {
+        float s = F[i * ldf] * m[0];
+        for (int k = 1; k < n; ++k) s = fmaf(F[i * ldf + k], m[k], s);
+        mp[i] = s + c.Gq0[i];
+      }
+      wave_lds_sync();
+    }
+    // Cholesky of P- into W (lower triangle); every lane forms the pivot itself
+    for (int j = 0; j < n; ++j) {
+      float d = Pp[j * ld + j];
+      for (int k = 0; k < j; ++k) d = fmaf(-W[j * ld + k], W[j * ld + k], d);
+      d = fast_sqrt(d);
+      const float inv = fast_rcp(d);
+      for (int i = j + 1 + tid; i < n; i += 64) {
+        float s = Pp[i * ld + j];
+        for (int k = 0; k < j; ++k) s = fmaf(-W[i * ld + k], W[j * ld + k], s);
+        W[i * ld + j] = s * inv;
+      }
+      if (tid == 0) W[j * ld + j] = inv;  // the diagonal holds the reciprocal pivot
+      wave_lds_sync();
+    }
+    for (int cc = tid; cc < n; cc += 64) {  // X <- L^-T L^-1 X, a column per lane
+      for (int i = 0; i < n; ++i) {
+        float s = X[i * ld + cc];
+        for (int k = 0; k < i; ++k) s = fmaf(-W[i * ld + k], X[k * ld + cc], s);
+        X[i * ld + cc] = s * W[i * ld + i];
+      }
+      for (int i = n - 1; i >= 0; --i) {
+        float s = X[i * ld + cc];
+        for (int k = i + 1; k < n; ++k) s = fmaf(-W[k * ld + i], X[k * ld + cc], s);
+        X[i * ld + cc] = s * W[i * ld + i];
+      }
+    }
+    wave_lds_sync();
+    if (want_c) {
+      for (int e = tid; e < nn; e += 64) {  // C = G P^s = X^T P^s
+        const int i = e / n, j = e - i * n;
+        float s = X[i] * Ps[j];
+        for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], Ps[k * ld + j], s);
+        v.Cs.p[at(v.Cs, t, e)] = s;
+      }
+    }
+    for (int i = tid; i < n; i += 64) tv[i] = ms[i] - mp[i];
+    wave_lds_sync();
+    for (int i = tid; i < n; i += 64) {
+      float s = X[i] * tv[0];
+      for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], tv[k], s);
+      ms[i] = m[i] + s;
+    }
+    for (int e = tid; e < nn; e += 64) {
+      const int i = e / n, j = e - i * n;
+      Ps[i * ld + j] = Ps[i * ld + j] - Pp[i * ld + j];
+    }
+    wave_lds_sync();
+    for (int e = tid; e < nn; e += 64) {  // G D -> P-
+      const int i = e / n, j = e - i * n;
+      float s = X[i] * Ps[j];
+      for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], Ps[k * ld + j], s);
+      Pp[i * ld + j] = s;
+    }
+    wave_lds_sync();
+    for (int e = tid; e < nn; e += 64) {  // P + (G D) G^T -> P, which becomes P^s
+      const int i = e / n, j = e - i * n;
+      float s = Pp[i * ld] * X[j];
+      for (int k = 1; k < n; ++k) s = fmaf(Pp[i * ld + k], X[k * ld + j], s);
+      P[i * ld + j] = P[i * ld + j] + s;
+    }
+    wave_lds_sync();
+    float* sw = P;
+    P = Ps;
+    Ps = sw;
+    for (int e = tid; e < n; e += 64) v.ms.p[at(v.ms, t, e)] = ms[e];
+    for (int e = tid; e < nn; e += 64) v.Ps.p[at(v.Ps, t, e)] = Ps[(e / n) * ld + e % n];
+    wave_lds_sync();
+  }
+  if (v.m_out) for (int e = tid; e < n; e += 64) v.m_out[b * n + e] = ms[e];
+  if (v.P_out) for (int e = tid; e < nn; e += 64) v.P_out[b * nn + e] = Ps[(e / n) * ld + e % n];
+}
+
+// ---- host helpers --------------------------------------------------------------------------------------------------
+// A, G Q_s G^T for every step s of Q, G q0: fp32 with the association of kf_scan_group.hpp's fill_const
+static void rts_lin_fill(const bf_lgssm* p, std::vector<float>& A, std::vector<float>& GQG, std::vector<float>& Gq0) {
+  const int n = p->n, dq = p->dq, qs = p->Q_steps;
+  auto Gat = [&](int i, int k) { return p->G ? p->G[i * dq + k] : (i == k ? 1.f : 0.f); };
+  A.assign(p->A, p->A + (size_t)n * n);
+  GQG.assign((size_t)qs * n * n, 0.f);
+  for (int s = 0; s < qs; ++s) {
+    const float* Q = p->Q + (size_t)s * dq * dq;
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) {
+        float acc = 0.f;
+        for (int l = 0; l < dq; ++l) {
+          float gq = 0.f;
+          for (int k = 0; k < dq; ++k) gq = fmaf(Gat(i, k), Q[k * dq + l], gq);
+          acc = fmaf(gq, Gat(j, l), acc);
+        }
+        GQG[(size_t)s * n * n + (size_t)i * n + j] = acc;
+      }
+  }
+  Gq0.assign(n, 0.f);
+  for (int i = 0; i < n; ++i) {
+    float acc = 0.f;
+    for (int k = 0; k < dq; ++k) acc = fmaf(Gat(i, k), p->q0 ? p->q0[k] : 0.f, acc);
+    Gq0[i] = acc;
+  }
+}
+
+static inline bool rts_ref_stream(const SView& s, long long E, long long T) {
+  return s.p == nullptr || (s.sE == 1 && s.sT == E && s.sB == T * E && (reinterpret_cast<uintptr_t>(s.p) % 16 == 0) &&
+                            (T * E) % 4 == 0);
+}
+
+static Option g_rts_load_mode{-1, OPT_RTS_LOAD_MODE};
+Option& rts_load_mode_option() { return g_rts_load_mode; }
+
+template <int N, int KIND, class Arg>
+static int launch_rts_n(const Arg& c, const float* d_gqg, const RtsViews& v, long long B, long long T, int load_mode,
+                        hipStream_t stream) {
+  using S = RtsStage<N>;
+  bool staged_ok = S::OK && rts_ref_stream(v.m, N, T) && rts_ref_stream(v.P, N * N, T) && rts_ref_stream(v.ms, N, T) &&
+                   rts_ref_stream(v.Ps, N * N, T) && rts_ref_stream(v.Cs, N * N, T);
+  if (KIND != RTS_LIN_RECOMPUTE) staged_ok = staged_ok && rts_ref_stream(v.pm, N, T) && rts_ref_stream(v.pP, N * N, T);
+  if (load_mode == RTS_STAGED && !staged_ok)
+    return set_error(BF_EINVAL, "rts_load_mode = 2 needs n <= 4 and the contiguous reference layout with 16-byte aligned rows");
+  const bool staged = staged_ok && load_mode != RTS_STRIDED && B >= 64;
+  auto shifted = [&](long long b_begin) {
+    RtsViews w = v;
+    for (SView* s : {&w.m, &w.P, &w.pm, &w.pP, &w.ms, &w.Ps, &w.Cs}) if (s->p) s->p += b_begin * s->sB;
+    if (w.m_in) w.m_in += b_begin * N;
+    if (w.P_in) w.P_in += b_begin * N * N;
+    if (w.m_out) w.m_out += b_begin * N;
+    if (w.P_out) w.P_out += b_begin * N * N;
+    if (w.u) w.u += b_begin * w.u_sB;
+    return w;
+  };
+  long long b_main = 0;
+  if constexpr (S::OK) {
+    if (staged) {
+      // the staged kernel takes whole waves; a ragged remainder goes through the strided one
+      b_main = (B / 64) * 64;
+      hipLaunchKernelGGL((rts_reg_kernel<N, RTS_STAGED, KIND, Arg>), dim3((unsigned)(b_main / 64)), dim3(64),
+                         sizeof(float) * S::FLOATS, stream, c, d_gqg, v, b_main, T);
+    }
+  }
+  if (b_main < B) {
+    const long long nb = B - b_main;
+    hipLaunchKernelGGL((rts_reg_kernel<N, RTS_STRIDED, KIND, Arg>), dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, stream, c,
+                       d_gqg, shifted(b_main), nb, T);
+  }
+  BF_HIP_CHECK(hipGetLastError());
+  return BF_OK;
+}
+
+static int launch_rts_generic(const RtsGen& c0, const GenModel& g, const std::vector<float>& blk, const RtsViews& v,
+                              long long B, long long T, hipStream_t stream) {
+  const size_t lds = sizeof(float) * rts_gen_lds_floats(c0.n);
+  if (lds > 160 * 1024)
+    return set_error(BF_EUNSUPPORTED, "smoother: n = %d needs %zu bytes of LDS (160 KiB per workgroup)", c0.n, lds);
+  const void* dv = nullptr;
+  const int rc = device_constants(blk.data(), sizeof(float) * blk.size(), stream, &dv);
+  if (rc != BF_OK) return rc;
+  const float* base = static_cast<const float*>(dv);
+  RtsGen c = c0;
+  GenModel gg = g;
+  auto fix = [&](const float*& q) { q = base + reinterpret_cast<size_t>(q); };
+  if (c.kind == RTS_EXT) {
+    fix(gg.A); fix(gg.Hm); fix(gg.Gq0); fix(gg.Dr0); fix(gg.R); fix(gg.r0); fix(gg.GQG); fix(gg.DRD);
+    fix(gg.q0); fix(gg.Q); fix(gg.dyn_theta); fix(gg.emi_theta);
+  } else {
+    fix(c.A); fix(c.GQG); fix(c.Gq0);
+  }
+  if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "smoother: B too large for the run-time-dimension kernel");
+  hipLaunchKernelGGL(rts_generic_kernel, dim3((unsigned)B), dim3(64), lds, stream, c, gg, v, T);
+  BF_HIP_CHECK(hipGetLastError());
+  return BF_OK;
+}
+
+int launch_rts_linear(const bf_lgssm* p, const RtsViews& v, long long B, long long T, bool recompute, bool force_generic,
+                      int load_mode, hipStream_t stream) {
+  const int n = p->n;
+  std::vector<float> A, GQG, Gq0;
+  rts_lin_fill(p, A, GQG, Gq0);
+  const bool tv = recompute && p->Q_steps > 1;
+  if (!force_generic && n <= 8) {
+    const float* d_gqg = nullptr;
+    if (tv) {
+      const void* dv = nullptr;
+      const int rc = device_constants(GQG.data(), sizeof(float) * GQG.size(), stream, &dv);
+      if (rc != BF_OK) return rc;
+      d_gqg = static_cast<const float*>(dv);
+    }
+    auto go = [&](auto NC) -> int {
+      constexpr int N = decltype(NC)::value;
+      RtsLin<N> c;
+      std::memcpy(c.A, A.data(), sizeof(c.A));
+      std::memcpy(c.GQG, GQG.data(), sizeof(c.GQG));
+      std::memcpy(c.Gq0, Gq0.data(), sizeof(c.Gq0));
+      if (recompute) return launch_rts_n<N, RTS_LIN_RECOMPUTE>(c, d_gqg, v, B, T, load_mode, stream);
+      return launch_rts_n<N, RTS_LIN>(c, nullptr, v, B, T, load_mode, stream);
+    };
+    switch (n) {
+      case 1: return go(std::integral_constant<int, 1>{});
+      case 2: return go(std::integral_constant<int, 2>{});
+      case 3: return go(std::integral_constant<int, 3>{});
+      case 4: return go(std::integral_constant<int, 4>{});
+      case 5: return go(std::integral_constant<int, 5>{});
+      case 6: return go(std::integral_constant<int, 6>{});
+      case 7: return go(std::integral_constant<int, 7>{});
+      default: return go(std::integral_constant<int, 8>{});
+    }
+  }
+  if (load_mode == RTS_STAGED) return set_error(BF_EINVAL, "rts_load_mode = 2 needs n <= 4 on the register kernel");
+  // constant block A | Gq0 | GQG[qs] (offsets, fixed up once uploaded)
+  std::vector<float> blk;
+  blk.insert(blk.end(), A.begin(), A.end());
+  blk.insert(blk.end(), Gq0.begin(), Gq0.end());
+  blk.insert(blk.end(), GQG.begin(), GQG.end());
+  RtsGen c;
+  c.n = n;
+  c.kind = recompute ? RTS_LIN_RECOMPUTE : RTS_LIN;
+  c.A = reinterpret_cast<const float*>((size_t)0);
+  c.Gq0 = reinterpret_cast<const float*>((size_t)n * n);
+  c.GQG = reinterpret_cast<const float*>((size_t)n * n + n);
+  c.q_tv = p->Q_steps > 1;
+  GenModel g;
+  std::memset(&g, 0, sizeof(g));
+  return launch_rts_generic(c, g, blk, v, B, T, stream);
+}
+
+int launch_rts_ext(const bf_model* p, const RtsViews& v, long long B, long long T, bool force_generic, int load_mode,
+                   hipStream_t stream) {
+  GenModel g;
+  std::vector<float> blk;
+  int rc = gen_fill(p, T, g, blk);  // validates the registry ids and theta layouts
+  if (rc != BF_OK) return rc;
+  const int n = p->n;
+  if (!force_generic && n <= 8) {
+    auto go = [&](auto NC) -> int {
+      constexpr int N = decltype(NC)::value;
+      EkfModel<N, 1> e;
+      std::memset(&e, 0, sizeof(e));
+      e.dyn_id = p->dyn_id;
+      for (int i = 0; i < 8; ++i) e.dth[i] = g.dth[i];
+      if (p->dyn_id == DYN_LINEAR) for (int i = 0; i < N * N; ++i) e.A[i] = p->dyn_theta[i];
+      return launch_rts_n<N, RTS_EXT>(e, nullptr, v, B, T, load_mode, stream);
+    };
+    switch (n) {
+      case 1: return go(std::integral_constant<int, 1>{});
+      case 2: return go(std::integral_constant<int, 2>{});
+      case 3: return go(std::integral_constant<int, 3>{});
+      case 4: return go(std::integral_constant<int, 4>{});
+      case 5: return go(std::integral_constant<int, 5>{});
+      case 6: return go(std::integral_constant<int, 6>{});
+      case 7: return go(std::integral_constant<int, 7>{});
+      default: return go(std::integral_constant<int, 8>{});
+    }
+  }
+  if (load_mode == RTS_STAGED) return set_error(BF_EINVAL, "rts_load_mode = 2 needs n <= 4 on the register kernel");
+  RtsGen c;
+  std::memset(&c, 0, sizeof(c));
+  c.n = n;
+  c.kind = RTS_EXT;
+  return launch_rts_generic(c, g, blk, v, B, T, stream);
+}
+
+}  // namespace bf
+
+namespace bf {
+
+// bf_out_desc / bf_smooth_carry / bf_smooth_desc -> RtsViews, with the checks both entry points share
+int rts_views(const bf_out_desc* f, const bf_smooth_carry* carry, const bf_smooth_desc* out, const bf_cstream* u, long long B,
+              long long T, int n, bool need_pred, int (*launch)(const RtsViews&, void*), void* ctx) {
+  if (!f->means.ptr || !f->covs.ptr) return set_error(BF_EINVAL, "filtered means and covariances are required");
+  if (need_pred && (!f->pred_means.ptr || !f->pred_covs.ptr))
+    return set_error(BF_EINVAL, "the extended smoother needs the predicted means and covariances");
+  if (!out->means.ptr || !out->covs.ptr) return set_error(BF_EINVAL, "smoothed means and covariances are required outputs");
+  if (carry && ((carry->m_in == nullptr) != (carry->P_in == nullptr)))
+    return set_error(BF_EINVAL, "carry.m_in and carry.P_in are given together or not at all");
+  if (carry && ((carry->m_out == nullptr) != (carry->P_out == nullptr)))
+    return set_error(BF_EINVAL, "carry.m_out and carry.P_out are given together or not at all");
+  (void)n;
+  RtsViews v;
+  std::memset(&v, 0, sizeof(v));
+  v.m = make_sview(f->means);
+  v.P = make_sview(f->covs);
+  v.pm = make_sview(f->pred_means);
+  v.pP = make_sview(f->pred_covs);
+  v.ms = make_sview(out->means);
+  v.Ps = make_sview(out->covs);
+  v.Cs = make_sview(out->cross_covs);
+  if (carry) {
+    v.m_in = carry->m_in;
+    v.P_in = carry->P_in;
+    v.m_out = carry->m_out;
+    v.P_out = carry->P_out;
+  }
+  if (u && u->ptr) {
+    v.u = u->ptr;
+    v.u_sB = u->sB;
+    v.u_sT = u->sT;
+  }
+  (void)B;
+  (void)T;
+  return launch(v, ctx);
+}
+
+}  // namespace bf

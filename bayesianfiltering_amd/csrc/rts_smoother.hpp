@@ -1,0 +1,326 @@
+// rts_smoother: batched Rauch-Tung-Striebel backward pass over the streams a filter emitted (include/bayesfilt.h,
+// bf_rts_smoother_f32 / bf_eks_smoother_f32; the reference's SSM.smoother, gaussfiltax/ssm.py:55-61, 282-300).
+//
+// Math (the contract).  The filter's streams at step t (update -> predict order, inference.py:342-363) are the filtered
+// m_t, P_t and the one-step prediction m-_{t+1}, P-_{t+1} (pred_means[t], pred_covs[t]).  With F_t the dynamics Jacobian
+// the filter's predict used at step t:
+//   t = T-1 (no carry):  m^s = m, P^s = P, bit for bit
+//   t = T-2 ... 0:       X_t = (P-_{t+1})^-1 (F_t P_t)  (Cholesky of P-_{t+1}, lower triangle read, no jitter), G_t = X_t^T
+//                        m^s_t = m_t + G_t (m^s_{t+1} - m-_{t+1})
+//                        P^s_t = P_t + G_t (P^s_{t+1} - P-_{t+1}) G_t^T
+//                        C_t  = G_t P^s_{t+1}                                   (optional lag-one cross-covariance)
+// A P- that is not positive definite gives NaN (sqrt of a negative pivot) from that step backwards.
+//
+// Register kernel (this file, n <= 8): one lane per trajectory, 64-thread workgroups.  The carry (m^s, P^s) and the
+// step's P, P-, X, Cholesky factor live in VGPRs; every loop has compile-time bounds.  Two data paths, same arithmetic
+// (so the same bits):
+//   RTS_STRIDED  any strides: each lane loads / stores its own elements (the batch-inner layout [T][E][B] is coalesced
+//                across lanes as it is);
+//   RTS_STAGED   contiguous reference layout [B][T][E], n <= 4: the wave walks time in chunks of TC steps.  A chunk of
+//                the 64 trajectories' rows is fetched with 16-byte loads (consecutive lanes on consecutive 16-byte pieces
+//                of one row: TC*E*4-byte runs) into per-stream LDS tiles padded by 4 floats per row, the lanes walk
+//                their row backwards from LDS, write the smoothed values in place of the inputs they consumed (m^s over
+//                m, P^s over P, C over P-) and the tile leaves through 16-byte non-temporal stores.  The next (earlier)
+//                chunk's loads are issued into registers before the current chunk is computed (double buffering: the
+//                registers are the second buffer) and land in LDS after the flush.
+// Run-time-dimension kernel (rts_smoother.hip): one wave per trajectory, state in LDS, for every other n.
+#pragma once
+#include "bf_common.hpp"
+#include "kf_math.hpp"
+#include "models.hpp"
+#include "scan_common.hpp"
+
+namespace bf {
+
+enum { RTS_STRIDED = 0, RTS_STAGED = 2 };
+enum { RTS_LIN = 0, RTS_LIN_RECOMPUTE = 1, RTS_EXT = 2 };
+
+// Linear dynamics: A, G Q G^T (constant part), G q0.
+template <int N>
+struct RtsLin {
+  float A[N * N];
+  float GQG[N * N];
+  float Gq0[N];
+};
+
+struct RtsViews {
+  SView m, P, pm, pP;  // filtered inputs (read only)
+  SView ms, Ps, Cs;    // outputs (Cs.p may be NULL)
+  const float* m_in;   // smoothed state after the chunk ([B][n], [B][n][n]); NULL = the chunk ends at T-1
+  const float* P_in;
+  float* m_out;
+  float* P_out;
+  const float* u;      // inputs, element (b, t) at u[b*u_sB + t*u_sT]; NULL = zeros
+  long long u_sB, u_sT;
+};
+
+// steps per staged chunk: 128-byte runs for the covariance rows where the prefetch registers allow (TC*E % 4 == 0 for
+// E = n and n*n)
+template <int N>
+struct RtsStage {
+  static constexpr int TC = N == 1 ? 8 : (N == 2 ? 4 : (N == 3 ? 4 : 2));
+  static constexpr int WM = TC * N, WP = TC * N * N;
+  static constexpr int PAD = 4;
+  static constexpr int PM = WM + PAD, PP = WP + PAD;  // row pitches (floats); rows stay 16-byte aligned
+  static constexpr int CHM = WM / 4, CHP = WP / 4;    // 16-byte pieces per row = loads per lane per tile
+  static constexpr int FLOATS = 64 * (2 * PM + 2 * PP);
+  static constexpr bool OK = N <= 4 && WM % 4 == 0 && WP % 4 == 0;
+};
+
+// One backward step.  In: X = F_t P_t, P_t, m_t, m-_{t+1}, P-_{t+1}; carry ms / Ps = smoothed state at t+1.
+// Out: ms / Ps = smoothed state at t; C = G_t P^s_{t+1} when WANT_C.
+template <int N>
+__device__ __forceinline__ void rts_step(float* X, const float* P, const float* m, const float* mp, const float* Pp,
+                                         float* ms, float* Ps, float* C, bool want_c) {
+  // Cholesky of P- (lower triangle), reciprocal pivots
+  float L[N * N];
+  float rd[N];
+  BF_UNROLL for (int j = 0; j < N; ++j) {
+    float d = Pp[j * N + j];
+    BF_UNROLL for (int k = 0; k < j; ++k) d = fmaf(-L[j * N + k], L[j * N + k], d);
+    d = fast_sqrt(d);  // NaN for a non-PD P-
+    const float inv = fast_rcp(d);
+    rd[j] = inv;
+    BF_UNROLL for (int i = j + 1; i < N; ++i) {
+      float s = Pp[i * N + j];
+      BF_UNROLL for (int k = 0; k < j; ++k) s = fmaf(-L[i * N + k], L[j * N + k], s);
+      L[i * N + j] = s * inv;
+    }
+  }
+  // X <- L^-T L^-1 X, column by column
+  BF_UNROLL for (int c = 0; c < N; ++c) {
+    BF_UNROLL for (int i = 0; i < N; ++i) {
+      float s = X[i * N + c];
+      BF_UNROLL for (int k = 0; k < i; ++k) s = fmaf(-L[i * N + k], X[k * N + c], s);
+      X[i * N + c] = s * rd[i];
+    }
+    BF_UNROLL for (int i = N - 1; i >= 0; --i) {
+      float s = X[i * N + c];
+      BF_UNROLL for (int k = i + 1; k < N; ++k) s = fmaf(-L[k * N + i], X[k * N + c], s);
+      X[i * N + c] = s * rd[i];
+    }
+  }
+  // G[i][k] = X[k][i]
+  if (want_c) {
+    BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = 0; j < N; ++j) {
+      float s = X[i] * Ps[j];
+      BF_UNROLL for (int k = 1; k < N; ++k) s = fmaf(X[k * N + i], Ps[k * N + j], s);
+      C[i * N + j] = s;
+    }
+  }
+  float dm[N];
+  BF_UNROLL for (int i = 0; i < N; ++i) dm[i] = ms[i] - mp[i];
+  BF_UNROLL for (int i = 0; i < N; ++i) {
+    float s = X[i] * dm[0];
+    BF_UNROLL for (int k = 1; k < N; ++k) s = fmaf(X[k * N + i], dm[k], s);
+    ms[i] = m[i] + s;
+  }
+  BF_UNROLL for (int i = 0; i < N * N; ++i) Ps[i] = Ps[i] - Pp[i];  // D = P^s_{t+1} - P-_{t+1}
+  float GD[N * N];
+  BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = 0; j < N; ++j) {
+    float s = X[i] * Ps[j];
+    BF_UNROLL for (int k = 1; k < N; ++k) s = fmaf(X[k * N + i], Ps[k * N + j], s);
+    GD[i * N + j] = s;
+  }
+  BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = 0; j < N; ++j) {
+    float s = GD[i * N] * X[j];
+    BF_UNROLL for (int k = 1; k < N; ++k) s = fmaf(GD[i * N + k], X[k * N + j], s);
+    Ps[i * N + j] = P[i * N + j] + s;
+  }
+}
+
+// F_t P_t and, for the recompute path, m-_{t+1} = A m + G q0, P-_{t+1} = (A P) A^T + G Q_t G^T (kf_math.hpp's
+// predict_cov association).
+template <int N, int KIND, class Arg>
+__device__ __forceinline__ void rts_linearize(const Arg& c, const float* gqg_t, long long t, float u0, const float* m,
+                                              const float* P, float* X, float* mp, float* Pp) {
+  float F[N * N];
+  if constexpr (KIND == RTS_EXT) {
+    float fx[N];
+    dyn_linearize<N, 1>(c, m, u0, F, fx);
+  } else {
+    BF_UNROLL for (int i = 0; i < N * N; ++i) F[i] = c.A[i];
+  }
+  mm<N, N, N>(F, P, X);
+  if constexpr (KIND == RTS_LIN_RECOMPUTE) {
+    mm_nt<N, N, N>(X, F, Pp);
+    const float* q = gqg_t ? gqg_t + t * (N * N) : c.GQG;
+    BF_UNROLL for (int i = 0; i < N * N; ++i) Pp[i] = Pp[i] + q[i];
+    mv<N, N>(F, m, mp);
+    BF_UNROLL for (int i = 0; i < N; ++i) mp[i] += c.Gq0[i];
+  }
+}
+
+typedef float rts_f4 __attribute__((ext_vector_type(4)));  // native vector: stays in registers across the chunk loop
+
+__device__ __forceinline__ void rts_store16(float* p, const rts_f4& v) {
+  __builtin_nontemporal_store(v, reinterpret_cast<rts_f4*>(p));
+}
+
+// Rows of one staged tile: CH 16-byte pieces per row, piece q = lane + 64 i of the wave -> row q / CH, piece q % CH.
+// Global row r starts at base + r * sB (floats); only floats below `lim` of each row are touched.
+template <int CH>
+__device__ __forceinline__ void tile_fetch(const float* base, long long sB, int lim, int lane, rts_f4* v) {
+  BF_UNROLL for (int i = 0; i < CH; ++i) {
+    const int q = lane + 64 * i, r = q / CH, ch = q - r * CH;
+    if (ch * 4 < lim) v[i] = *reinterpret_cast<const rts_f4*>(base + (long long)r * sB + ch * 4);
+  }
+}
+template <int CH, int PITCH>
+__device__ __forceinline__ void tile_put(float* tile, int lane, const rts_f4* v) {
+  BF_UNROLL for (int i = 0; i < CH; ++i) {
+    const int q = lane + 64 * i, r = q / CH, ch = q - r * CH;
+    *reinterpret_cast<rts_f4*>(tile + r * PITCH + ch * 4) = v[i];
+  }
+}
+// LDS tile -> global; a piece that straddles `lim` is written dword by dword
+template <int CH, int PITCH>
+__device__ __forceinline__ void tile_flush(const float* tile, float* base, long long sB, int lim, int lane) {
+  BF_UNROLL for (int i = 0; i < CH; ++i) {
+    const int q = lane + 64 * i, r = q / CH, ch = q - r * CH;
+    const rts_f4 v = *reinterpret_cast<const rts_f4*>(tile + r * PITCH + ch * 4);
+    float* dst = base + (long long)r * sB + ch * 4;
+    if (ch * 4 + 4 <= lim) {
+      rts_store16(dst, v);
+    } else if (ch * 4 < lim) {
+      BF_UNROLL for (int j = 0; j < 4; ++j) if (ch * 4 + j < lim) dst[j] = v[j];
+    }
+  }
+}
+
+template <int N, int MODE, int KIND, class Arg>
+__global__ void __launch_bounds__(64) rts_reg_kernel(Arg c, const float* __restrict__ gqg_t, RtsViews v, long long B,
+                                                     long long T) {
+  constexpr int NN = N * N;
+  const int lane = threadIdx.x;
+  const long long b0 = (long long)blockIdx.x * 64;
+  const long long b_raw = b0 + lane;
+  if constexpr (MODE == RTS_STRIDED) {
+    if (b_raw >= B) return;  // no cross-lane work on this path
+  }
+  const long long b = b_raw;  // staged launches hold whole waves only
+  const bool want_c = v.Cs.p != nullptr;
+  const bool carry_in = v.m_in != nullptr;
+  float ms[N], Ps[NN];
+
+  if constexpr (MODE == RTS_STRIDED) {
+    auto ld = [&](const SView& s, long long t, int e) { return s.p[b * s.sB + t * s.sT + e * s.sE]; };
+    auto st = [&](const SView& s, long long t, int e, float x) { s.p[b * s.sB + t * s.sT + e * s.sE] = x; };
+    long long t = T - 1;
+    if (carry_in) {
+      BF_UNROLL for (int i = 0; i < N; ++i) ms[i] = v.m_in[b * N + i];
+      BF_UNROLL for (int i = 0; i < NN; ++i) Ps[i] = v.P_in[b * NN + i];
+    } else {
+      BF_UNROLL for (int i = 0; i < N; ++i) { ms[i] = ld(v.m, t, i); st(v.ms, t, i, ms[i]); }
+      BF_UNROLL for (int i = 0; i < NN; ++i) { Ps[i] = ld(v.P, t, i); st(v.Ps, t, i, Ps[i]); }
+      --t;
+    }
+    for (; t >= 0; --t) {
+      float m[N], P[NN], mp[N], Pp[NN], X[NN], C[NN];
+      BF_UNROLL for (int i = 0; i < N; ++i) m[i] = ld(v.m, t, i);
+      BF_UNROLL for (int i = 0; i < NN; ++i) P[i] = ld(v.P, t, i);
+      if constexpr (KIND != RTS_LIN_RECOMPUTE) {
+        BF_UNROLL for (int i = 0; i < N; ++i) mp[i] = ld(v.pm, t, i);
+        BF_UNROLL for (int i = 0; i < NN; ++i) Pp[i] = ld(v.pP, t, i);
+      }
+      const float u0 = v.u ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+      rts_linearize<N, KIND>(c, gqg_t, t, u0, m, P, X, mp, Pp);
+      rts_step<N>(X, P, m, mp, Pp, ms, Ps, C, want_c);
+      BF_UNROLL for (int i = 0; i < N; ++i) st(v.ms, t, i, ms[i]);
+      BF_UNROLL for (int i = 0; i < NN; ++i) st(v.Ps, t, i, Ps[i]);
+      if (want_c) BF_UNROLL for (int i = 0; i < NN; ++i) st(v.Cs, t, i, C[i]);
+    }
+  } else if constexpr (RtsStage<N>::OK) {
+    using S = RtsStage<N>;
+    constexpr int TC = S::TC;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* tm = lds;                 // m    -> m^s
+    float* tP = tm + 64 * S::PM;     // P    -> P^s
+    float* tpm = tP + 64 * S::PP;    // m-
+    float* tpP = tpm + 64 * S::PM;   // P-   -> C
+    constexpr bool LOAD_PRED = KIND != RTS_LIN_RECOMPUTE;
+    // wave-uniform row bases of this wave's 64 trajectories (reference layout: sE = 1, sT = E, sB = T*E)
+    const float* gm = v.m.p + b0 * v.m.sB;
+    const float* gP = v.P.p + b0 * v.P.sB;
+    const float* gpm = LOAD_PRED ? v.pm.p + b0 * v.pm.sB : nullptr;
+    const float* gpP = LOAD_PRED ? v.pP.p + b0 * v.pP.sB : nullptr;
+    float* gms = v.ms.p + b0 * v.ms.sB;
+    float* gPs = v.Ps.p + b0 * v.Ps.sB;
+    float* gCs = want_c ? v.Cs.p + b0 * v.Cs.sB : nullptr;
+    rts_f4 fm[S::CHM], fP[S::CHP], fpm[LOAD_PRED ? S::CHM : 1], fpP[LOAD_PRED ? S::CHP : 1];
+    const long long NC = (T + TC - 1) / TC;
+    auto fetch = [&](long long k) __attribute__((always_inline)) {
+      const long long t0 = k * TC;
+      const int vs = (int)((T - t0) < TC ? (T - t0) : TC);
+      tile_fetch<S::CHM>(gm + t0 * N, v.m.sB, vs * N, lane, fm);
+      tile_fetch<S::CHP>(gP + t0 * NN, v.P.sB, vs * NN, lane, fP);
+      if constexpr (LOAD_PRED) {
+        tile_fetch<S::CHM>(gpm + t0 * N, v.pm.sB, vs * N, lane, fpm);
+        tile_fetch<S::CHP>(gpP + t0 * NN, v.pP.sB, vs * NN, lane, fpP);
+      }
+    };
+    auto put = [&]() __attribute__((always_inline)) {
+      tile_put<S::CHM, S::PM>(tm, lane, fm);
+      tile_put<S::CHP, S::PP>(tP, lane, fP);
+      if constexpr (LOAD_PRED) {
+        tile_put<S::CHM, S::PM>(tpm, lane, fpm);
+        tile_put<S::CHP, S::PP>(tpP, lane, fpP);
+      }
+    };
+    fetch(NC - 1);
+    put();
+    const float* rm = tm + lane * S::PM;  // this lane's rows
+    const float* rP = tP + lane * S::PP;
+    const float* rpm = tpm + lane * S::PM;
+    const float* rpP = tpP + lane * S::PP;
+    float* wm = tm + lane * S::PM;
+    float* wP = tP + lane * S::PP;
+    float* wC = tpP + lane * S::PP;
+    for (long long k = NC - 1; k >= 0; --k) {
+      const long long t0 = k * TC;
+      const int vs = (int)((T - t0) < TC ? (T - t0) : TC);
+      wave_lds_sync();
+      if (k > 0) fetch(k - 1);  // in flight while this chunk is computed
+      int s = vs - 1;
+      if (k == NC - 1) {
+        if (carry_in) {
+          BF_UNROLL for (int i = 0; i < N; ++i) ms[i] = v.m_in[b * N + i];
+          BF_UNROLL for (int i = 0; i < NN; ++i) Ps[i] = v.P_in[b * NN + i];
+        } else {  // t = T-1: the filtered state, left in the tile as it is
+          BF_UNROLL for (int i = 0; i < N; ++i) ms[i] = rm[s * N + i];
+          BF_UNROLL for (int i = 0; i < NN; ++i) Ps[i] = rP[s * NN + i];
+          --s;
+        }
+      }
+      for (; s >= 0; --s) {
+        const long long t = t0 + s;
+        float m[N], P[NN], mp[N], Pp[NN], X[NN], C[NN];
+        BF_UNROLL for (int i = 0; i < N; ++i) m[i] = rm[s * N + i];
+        BF_UNROLL for (int i = 0; i < NN; ++i) P[i] = rP[s * NN + i];
+        if constexpr (LOAD_PRED) {
+          BF_UNROLL for (int i = 0; i < N; ++i) mp[i] = rpm[s * N + i];
+          BF_UNROLL for (int i = 0; i < NN; ++i) Pp[i] = rpP[s * NN + i];
+        }
+        const float u0 = v.u ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+        rts_linearize<N, KIND>(c, gqg_t, t, u0, m, P, X, mp, Pp);
+        rts_step<N>(X, P, m, mp, Pp, ms, Ps, C, want_c);
+        BF_UNROLL for (int i = 0; i < N; ++i) wm[s * N + i] = ms[i];
+        BF_UNROLL for (int i = 0; i < NN; ++i) wP[s * NN + i] = Ps[i];
+        if (want_c) BF_UNROLL for (int i = 0; i < NN; ++i) wC[s * NN + i] = C[i];
+      }
+      wave_lds_sync();
+      tile_flush<S::CHM, S::PM>(tm, gms + t0 * N, v.ms.sB, vs * N, lane);
+      tile_flush<S::CHP, S::PP>(tP, gPs + t0 * NN, v.Ps.sB, vs * NN, lane);
+      // C: entry T-1 exists only with a carry
+      if (want_c) tile_flush<S::CHP, S::PP>(tpP, gCs + t0 * NN, v.Cs.sB, (k == NC - 1 && !carry_in ? vs - 1 : vs) * NN, lane);
+      if (k > 0) {
+        wave_lds_sync();
+        put();
+      }
+    }
+  }
+  if (v.m_out) BF_UNROLL for (int i = 0; i < N; ++i) v.m_out[b * N + i] = ms[i];
+  if (v.P_out) BF_UNROLL for (int i = 0; i < NN; ++i) v.P_out[b * NN + i] = Ps[i];
+}
+
+}  // namespace bf

@@ -135,7 +135,10 @@ int bf_device_count(void);
  *                   (64, 32) kernel, smaller n on the run-time-dimension kernel); 2 = the same kernel with two chains per wave
  *                   (one factorization serves both half-waves; identical bits, measured 10-20 % slower: kept for experiments).
  *   "force_generic": 1 = bf_kalman_filter_f32 / bf_gsf_ekf_f32 run the run-time-dimension kernel (any n, m, K; state in
- *                   LDS) even where a compile-time-dimension instance exists (test hook; default 0).
+ *                   LDS) even where a compile-time-dimension instance exists (test hook; default 0).  The smoothers
+ *                   (bf_rts_smoother_f32, bf_eks_smoother_f32) honour it the same way.
+ *   "rts_load_mode": the smoothers' data path: -1 = choose from the layout (default), 0 = strided per-lane loads and
+ *                   stores, 2 = LDS-staged time chunks (contiguous reference layout, n <= 4 only).
  *   "gsf_structured": 1 (default) lets bf_gsf_ekf_f32 use the structure-aware kernel instances
  *                   (banded Lorenz-96 Jacobian, selection emission) when the model qualifies;
  *                   0 forces the dense generic instances.
@@ -155,7 +158,7 @@ int bf_device_count(void);
  * bf_set_option changes the PROCESS-WIDE default.  A library or a thread that must not disturb -- or be disturbed by -- other
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
  * called on that thread (bf_kalman_filter_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
- * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32) and for that call only; every armed override is dropped when
+ * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_eks_smoother_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
 int bf_set_option(const char* name, int value);
 int bf_set_call_option(const char* name, int value);
@@ -381,6 +384,51 @@ int bf_random_split(const uint32_t key[2], int64_t num, uint32_t* host_out);
  * void*; RCCL over xGMI).  RCCL is loaded on first use.  The Python layer does the same through torch.distributed
  * (bayesianfiltering_amd/distributed.py: backend "nccl" is RCCL). */
 int bf_allgather_summaries(const void* d_send, void* d_recv, size_t bytes, void* nccl_comm, void* stream);
+
+/* ---- Rauch-Tung-Striebel smoothing (the reference's SSM.smoother, gaussfiltax/ssm.py:55-61, 282-300) --------------
+ * Input: the streams a filter above emitted (update -> predict order): filtered m_t, P_t (out->means / covs) and the
+ * one-step predictions m-_{t+1}, P-_{t+1} (out->pred_means / pred_covs at index t).  With F_t the dynamics Jacobian the
+ * filter's predict used at step t (A for bf_lgssm; the registry Jacobian at (m_t, q0, u_t) for bf_model):
+ *   t = T-1:            m^s = m, P^s = P (copied bit for bit; unless carry->m_in gives the smoothed state at T)
+ *   t = T-2 ... 0:      X_t = (P-_{t+1})^-1 (F_t P_t) by Cholesky of P-_{t+1} (lower triangle read, no jitter), G_t = X_t^T
+ *                       m^s_t = m_t + G_t (m^s_{t+1} - m-_{t+1})
+ *                       P^s_t = P_t + G_t (P^s_{t+1} - P-_{t+1}) G_t^T
+ *                       C_t  = Cov(x_t, x_{t+1} | y_{1:T}) = G_t P^s_{t+1}   (optional: what EM's E-step needs)
+ * A P- that is not positive definite gives NaN for that trajectory from that step backwards (as a non-PD S does in the
+ * filters).  Element (b, t, e) of every stream at ptr[b*sB + t*sT + e*sE] (sK unused: one component). */
+typedef struct bf_smooth_desc {
+  bf_stream means;      /* E = n,   required */
+  bf_stream covs;       /* E = n*n, required */
+  bf_stream cross_covs; /* E = n*n, optional: entry t for t < T-1 (entry T-1 too when carry->m_in is given) */
+} bf_smooth_desc;
+
+/* Backward chunking when the history does not fit in HBM: process the LAST chunk of steps first, then feed its m_out /
+ * P_out as the next (earlier) chunk's m_in / P_in.  DEVICE pointers, contiguous [B][n] and [B][n][n].
+ * m_in / P_in: the smoothed state at the first step AFTER this chunk (both NULL: the chunk ends at T-1).
+ * m_out / P_out: receive the smoothed state at the chunk's first step (NULL = not written). */
+typedef struct bf_smooth_carry {
+  const float* m_in;
+  const float* P_in;
+  float* m_out;
+  float* P_out;
+} bf_smooth_carry;
+
+/* ABI guard of the two smoother structs (bf_abi_check covers the rest); a size of 0 = not mirrored. */
+int bf_smoother_abi_check(size_t sizeof_smooth_desc, size_t sizeof_smooth_carry);
+
+/* RTS smoother of the linear model (bf_kalman_filter_f32's).  filtered->means / covs are required, the other fields
+ * other than pred_means / pred_covs are ignored.  pred_means / pred_covs both NULL: they are RECOMPUTED from the filtered
+ * streams, m- = A m + G q0 and P- = A P A^T + G Q_t G^T (Q_steps honoured; Q_steps = T of THIS call), so that the filter
+ * may emit the filtered fields only.  carry may be NULL.  Asynchronous on `stream`, no allocation.  n <= 8: registers,
+ * one lane per trajectory; larger n: the run-time-dimension kernel (one workgroup per trajectory, state in LDS). */
+int bf_rts_smoother_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T,
+                        const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream);
+
+/* Extended RTS smoother for registry dynamics (K = 1; the streams of bf_gsf_ekf_f32 with one component).
+ * pred_means / pred_covs are required.  u: the filter's inputs (NULL or u->ptr == NULL = zeros).
+ * BF_EUNSUPPORTED for functions given as source (BF_FN_USER) and for model->flags != 0. */
+int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
+                        const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream);
 
 /* Bytes one (trajectory, timestep) moves for the streams enabled in `out`: the algorithmic
  * traffic figure of SURVEY.md 8(d)  (4m + 4K(1 + 2n + 2n^2) for all five streams). */
