@@ -23,6 +23,7 @@
 #include <vector>
 #include "bf_common.hpp"
 #include "kf_math.hpp"
+#include "lgssm_pack.hpp"
 #include "scan_common.hpp"
 #include "models.hpp"
 #include "bf_rng.hpp"
@@ -133,50 +134,13 @@ int gen_fill(const bf_model* p, long long T, GenModel& g, std::vector<float>& bl
   for (size_t i = 0; i < nth_e; ++i) blk[oThe + i] = p->emi_theta[i];
   for (int i = 0; i < n * n; ++i) blk[oA + i] = A[i];
   for (int i = 0; i < m * n; ++i) blk[oH + i] = Hm[i];
-  for (int i = 0; i < n; ++i) {
-    float s = 0.f;
-    for (int kq = 0; kq < dq; ++kq) s = fmaf(G[(size_t)i * dq + kq], p->q0 ? p->q0[kq] : 0.f, s);
-    blk[oGq + i] = s;
-  }
-  for (int i = 0; i < m; ++i) {
-    float s = 0.f;
-    for (int kr = 0; kr < dr; ++kr) s = fmaf(D[(size_t)i * dr + kr], p->r0 ? p->r0[kr] : 0.f, s);
-    blk[oDr + i] = s;
-  }
+  noise_mean(G.data(), p->q0, n, dq, &blk[oGq]);
+  noise_mean(D.data(), p->r0, m, dr, &blk[oDr]);
   for (size_t i = 0; i < nR; ++i) blk[oR + i] = p->R[i];
   for (int i = 0; i < dr; ++i) blk[or0 + i] = p->r0 ? p->r0[i] : 0.f;
-  // (F_q Q) F_q^T and (H_r R) H_r^T in fp32 with the association of inference.py:69, :100
-  std::vector<float> tmp((size_t)(n > m ? n : m) * (dq > dr ? dq : dr));
-  for (int s = 0; s < qs; ++s) {
-    const float* Q = p->Q + (size_t)s * dq * dq;
-    for (int i = 0; i < n; ++i)
-      for (int l = 0; l < dq; ++l) {
-        float v = 0.f;
-        for (int kq = 0; kq < dq; ++kq) v = fmaf(G[(size_t)i * dq + kq], Q[kq * dq + l], v);
-        tmp[(size_t)i * dq + l] = v;
-      }
-    for (int i = 0; i < n; ++i)
-      for (int j = 0; j < n; ++j) {
-        float v = 0.f;
-        for (int l = 0; l < dq; ++l) v = fmaf(tmp[(size_t)i * dq + l], G[(size_t)j * dq + l], v);
-        blk[oGQG + (size_t)s * n * n + (size_t)i * n + j] = v;
-      }
-  }
-  for (int s = 0; s < rs; ++s) {
-    const float* R = p->R + (size_t)s * dr * dr;
-    for (int i = 0; i < m; ++i)
-      for (int l = 0; l < dr; ++l) {
-        float v = 0.f;
-        for (int kr = 0; kr < dr; ++kr) v = fmaf(D[(size_t)i * dr + kr], R[kr * dr + l], v);
-        tmp[(size_t)i * dr + l] = v;
-      }
-    for (int i = 0; i < m; ++i)
-      for (int j = 0; j < m; ++j) {
-        float v = 0.f;
-        for (int l = 0; l < dr; ++l) v = fmaf(tmp[(size_t)i * dr + l], D[(size_t)j * dr + l], v);
-        blk[oDRD + (size_t)s * m * m + (size_t)i * m + j] = v;
-      }
-  }
+  // (F_q Q_s) F_q^T and (H_r R_s) H_r^T for every step s (lgssm_pack.hpp)
+  for (int s = 0; s < qs; ++s) noise_cov(G.data(), p->Q + (size_t)s * dq * dq, n, dq, &blk[oGQG + (size_t)s * n * n], n);
+  for (int s = 0; s < rs; ++s) noise_cov(D.data(), p->R + (size_t)s * dr * dr, m, dr, &blk[oDRD + (size_t)s * m * m], m);
   // offsets -> stored as pointers once the block is on the device (the caller adds the base)
   g.A = reinterpret_cast<const float*>(oA); g.Hm = reinterpret_cast<const float*>(oH); g.Gq0 = reinterpret_cast<const float*>(oGq);
   g.Dr0 = reinterpret_cast<const float*>(oDr); g.R = reinterpret_cast<const float*>(oR); g.r0 = reinterpret_cast<const float*>(or0);

@@ -35,6 +35,7 @@
 #include "bf_common.hpp"
 #include "kf_math.hpp"
 #include "lane_group.hpp"
+#include "lgssm_pack.hpp"
 #include "scan_common.hpp"
 #include "models.hpp"
 
@@ -657,55 +658,23 @@ static inline int fill_model(const bf_model* p, EkfModel<N, M>& e, std::vector<f
       break;
     default: return set_error(BF_EUNSUPPORTED, "unknown emission function id %d", p->emi_id);
   }
-  // (F_q Q) F_q^T, (H_r R) H_r^T, F_q q0, H_r r0 in fp32 with the association of inference.py:69,:100
-  auto gqg_of = [&](const float* Q, float* out) {
-    for (int i = 0; i < N; ++i)
-      for (int j = 0; j < N; ++j) {
-        float s = 0.f;
-        for (int l = 0; l < dq; ++l) {
-          float gq = 0.f;
-          for (int kq = 0; kq < dq; ++kq) gq = fmaf(G[i * dq + kq], Q[kq * dq + l], gq);
-          s = fmaf(gq, G[j * dq + l], s);
-        }
-        out[i * N + j] = s;
-      }
-  };
-  auto drd_of = [&](const float* R, float* out) {
-    for (int i = 0; i < M; ++i)
-      for (int j = 0; j < M; ++j) {
-        float s = 0.f;
-        for (int l = 0; l < dr; ++l) {
-          float d1 = 0.f;
-          for (int kr = 0; kr < dr; ++kr) d1 = fmaf(D[i * dr + kr], R[kr * dr + l], d1);
-          s = fmaf(d1, D[j * dr + l], s);
-        }
-        out[i * M + j] = s;
-      }
-  };
-  gqg_of(p->Q, e.GQG);
-  drd_of(p->R, e.DRD);
+  // (F_q Q) F_q^T, (H_r R) H_r^T, F_q q0, H_r r0 (lgssm_pack.hpp)
+  noise_cov(G, p->Q, N, dq, e.GQG, N);
+  noise_cov(D, p->R, M, dr, e.DRD, M);
   if (p->Q_steps > 1) {
     if (!tvq) return set_error(BF_EUNSUPPORTED, "time-varying Q is not supported on this path");
     tvq->resize((size_t)p->Q_steps * N * N);
-    for (int t = 0; t < p->Q_steps; ++t) gqg_of(p->Q + (size_t)t * dq * dq, tvq->data() + (size_t)t * N * N);
+    for (int t = 0; t < p->Q_steps; ++t) noise_cov(G, p->Q + (size_t)t * dq * dq, N, dq, tvq->data() + (size_t)t * N * N, N);
   }
   if (p->R_steps > 1) {
     if (!tvr) return set_error(BF_EUNSUPPORTED, "time-varying R is not supported on this path");
     if (p->emi_id == EMI_STOCH_VOL)
       return set_error(BF_EUNSUPPORTED, "time-varying R needs an emission with a constant noise Jacobian H_r");
     tvr->resize((size_t)p->R_steps * M * M);
-    for (int t = 0; t < p->R_steps; ++t) drd_of(p->R + (size_t)t * dr * dr, tvr->data() + (size_t)t * M * M);
+    for (int t = 0; t < p->R_steps; ++t) noise_cov(D, p->R + (size_t)t * dr * dr, M, dr, tvr->data() + (size_t)t * M * M, M);
   }
-  for (int i = 0; i < N; ++i) {
-    float s = 0.f;
-    for (int kq = 0; kq < dq; ++kq) s = fmaf(G[i * dq + kq], p->q0 ? p->q0[kq] : 0.f, s);
-    e.Gq0[i] = s;
-  }
-  for (int i = 0; i < M; ++i) {
-    float s = 0.f;
-    for (int kr = 0; kr < dr; ++kr) s = fmaf(D[i * dr + kr], p->r0 ? p->r0[kr] : 0.f, s);
-    e.Dr0[i] = s;
-  }
+  noise_mean(G, p->q0, N, dq, e.Gq0);
+  noise_mean(D, p->r0, M, dr, e.Dr0);
   if (p->emi_id == EMI_STOCH_VOL) {
     for (int i = 0; i < M * M; ++i) e.R[i] = p->R[i];
     for (int i = 0; i < M; ++i) e.r0[i] = p->r0 ? p->r0[i] : 0.f;

@@ -34,6 +34,7 @@
 #include "bf_common.hpp"
 #include "kf_math.hpp"
 #include "lane_group.hpp"
+#include "lgssm_pack.hpp"
 #include "scan_common.hpp"
 
 namespace bf {
@@ -410,42 +411,12 @@ kf_scan_group_kernel(KFConst<NS, M> c, const float* __restrict__ gqg_t, const fl
 // ---------------------------------------------------------------------------------------
 template <int N, int M>
 static inline void fill_const(const bf_lgssm* p, KFConst<N, M>& c, const float* Qt, const float* Rt) {
-  const int dq = p->dq, dr = p->dr;
-  auto Gat = [&](int i, int k) { return p->G ? p->G[i * dq + k] : (i == k ? 1.f : 0.f); };
-  auto Dat = [&](int i, int k) { return p->D ? p->D[i * dr + k] : (i == k ? 1.f : 0.f); };
   for (int i = 0; i < N * N; ++i) c.A[i] = p->A[i];
   for (int i = 0; i < M * N; ++i) c.H[i] = p->H[i];
-  // (G @ Q) @ G^T and (D @ R) @ D^T in fp32, association as written in inference.py:69,:100
-  for (int i = 0; i < N; ++i)
-    for (int j = 0; j < N; ++j) {
-      float s = 0.f;
-      for (int l = 0; l < dq; ++l) {
-        float gq = 0.f;
-        for (int k = 0; k < dq; ++k) gq = fmaf(Gat(i, k), Qt[k * dq + l], gq);
-        s = fmaf(gq, Gat(j, l), s);
-      }
-      c.GQG[i * N + j] = s;
-    }
-  for (int i = 0; i < M; ++i)
-    for (int j = 0; j < M; ++j) {
-      float s = 0.f;
-      for (int l = 0; l < dr; ++l) {
-        float dq_ = 0.f;
-        for (int k = 0; k < dr; ++k) dq_ = fmaf(Dat(i, k), Rt[k * dr + l], dq_);
-        s = fmaf(dq_, Dat(j, l), s);
-      }
-      c.DRD[i * M + j] = s;
-    }
-  for (int i = 0; i < N; ++i) {
-    float s = 0.f;
-    for (int k = 0; k < dq; ++k) s = fmaf(Gat(i, k), p->q0 ? p->q0[k] : 0.f, s);
-    c.Gq0[i] = s;
-  }
-  for (int i = 0; i < M; ++i) {
-    float s = 0.f;
-    for (int k = 0; k < dr; ++k) s = fmaf(Dat(i, k), p->r0 ? p->r0[k] : 0.f, s);
-    c.Dr0[i] = s;
-  }
+  noise_cov(p->G, Qt, N, p->dq, c.GQG, N);
+  noise_cov(p->D, Rt, M, p->dr, c.DRD, M);
+  noise_mean(p->G, p->q0, N, p->dq, c.Gq0);
+  noise_mean(p->D, p->r0, M, p->dr, c.Dr0);
 }
 
 static inline bool stream_is_reference(const bf_stream& s, long long E, long long T) {

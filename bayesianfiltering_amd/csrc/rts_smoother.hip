@@ -11,6 +11,7 @@
 #include <vector>
 #include "rts_smoother.hpp"
 #include "generic_device.hpp"
+#include "lgssm_pack.hpp"
 
 namespace bf {
 
@@ -174,31 +175,14 @@ __global__ void __launch_bounds__(64) rts_generic_kernel(RtsGen c, GenModel g, R
 }
 
 // ---- host helpers --------------------------------------------------------------------------------------------------
-// A, G Q_s G^T for every step s of Q, G q0: fp32 with the association of kf_scan_group.hpp's fill_const
+// A, G Q_s G^T for every step s of Q, G q0 (lgssm_pack.hpp: the bits the filters upload)
 static void rts_lin_fill(const bf_lgssm* p, std::vector<float>& A, std::vector<float>& GQG, std::vector<float>& Gq0) {
   const int n = p->n, dq = p->dq, qs = p->Q_steps;
-  auto Gat = [&](int i, int k) { return p->G ? p->G[i * dq + k] : (i == k ? 1.f : 0.f); };
   A.assign(p->A, p->A + (size_t)n * n);
   GQG.assign((size_t)qs * n * n, 0.f);
-  for (int s = 0; s < qs; ++s) {
-    const float* Q = p->Q + (size_t)s * dq * dq;
-    for (int i = 0; i < n; ++i)
-      for (int j = 0; j < n; ++j) {
-        float acc = 0.f;
-        for (int l = 0; l < dq; ++l) {
-          float gq = 0.f;
-          for (int k = 0; k < dq; ++k) gq = fmaf(Gat(i, k), Q[k * dq + l], gq);
-          acc = fmaf(gq, Gat(j, l), acc);
-        }
-        GQG[(size_t)s * n * n + (size_t)i * n + j] = acc;
-      }
-  }
+  for (int s = 0; s < qs; ++s) noise_cov(p->G, p->Q + (size_t)s * dq * dq, n, dq, &GQG[(size_t)s * n * n], n);
   Gq0.assign(n, 0.f);
-  for (int i = 0; i < n; ++i) {
-    float acc = 0.f;
-    for (int k = 0; k < dq; ++k) acc = fmaf(Gat(i, k), p->q0 ? p->q0[k] : 0.f, acc);
-    Gq0[i] = acc;
-  }
+  noise_mean(p->G, p->q0, n, dq, Gq0.data());
 }
 
 static inline bool rts_ref_stream(const SView& s, long long E, long long T) {

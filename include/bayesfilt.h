@@ -123,17 +123,11 @@ int bf_device_count(void);
  *                   stores, 2 = LDS time-transpose (contiguous reference layout only).
  *   "kf_lanes":     lanes that cooperate on one trajectory (0 = default for the dimensions;
  *                   otherwise one of the compiled powers of two, e.g. 1, 2 or 4 at n = 4).
- *   "kf_mfma_variant": the n = 64, m = 32 Kalman kernel: 5 (default) = gain-free update (P+ = P - W^T W + c c^T with
- *                   W = L^-1 H P) with the five matrix products as three-term bf16 splits of the fp32 operands on the
- *                   bf16 matrix pipe (fp32-level rounding); 2 = the same update on fp32 MFMAs, Cholesky and forward
- *                   substitution fused in one wave's registers; 3 = 2 with the factorization itself as rank-2 MFMA
- *                   eliminations; 4 = 2 at three workgroups per CU; 1 = round 1's kernel (explicit inverse through LDS).
- *                   Same results to rounding (< 5e-6 against the test oracle over 2 000 steps); env BAYESFILT_MFMA_VARIANT
- *                   sets the default.
  *   "kf_small_mode": 1 (default) = Kalman models with 9 <= n <= 32, m <= 32 run on the one-wave-per-trajectory matrix-core
  *                   kernel (single 32 x 32 tiles, bf16 three-term products); 0 = off (n >= 24 then rides padded in the
- *                   (64, 32) kernel, smaller n on the run-time-dimension kernel); 2 = the same kernel with two chains per wave
- *                   (one factorization serves both half-waves; identical bits, measured 10-20 % slower: kept for experiments).
+ *                   (64, 32) kernel, smaller n on the run-time-dimension kernel).  Models with 33 <= n <= 64, m <= 32 always
+ *                   run on the (64, 32) matrix-core kernel (gain-free update P+ = P - W^T W + c c^T with W = L^-1 H P, the
+ *                   same three-term bf16 products); it has no option.
  *   "force_generic": 1 = bf_kalman_filter_f32 / bf_gsf_ekf_f32 run the run-time-dimension kernel (any n, m, K; state in
  *                   LDS) even where a compile-time-dimension instance exists (test hook; default 0).  The smoothers
  *                   (bf_rts_smoother_f32, bf_eks_smoother_f32) honour it the same way.

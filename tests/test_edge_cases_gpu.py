@@ -158,6 +158,9 @@ def test_call_options_apply_to_one_call_only():
     again = bfa.kalman_filter(p, ys, return_loglik=True)
     assert torch.equal(again[0].covariances, default[0].covariances)
     assert lib.bf_set_call_option(b"no_such_option", 1) == _lib.BF_EINVAL
+    # retired options: the name of the (64, 32) kernel's variant switch is unknown, the one-wave kernel's mode is 0 or 1
+    assert lib.bf_set_option(b"kf_mfma_variant", 5) == _lib.BF_EINVAL
+    assert lib.bf_set_option(b"kf_small_mode", 2) == _lib.BF_EINVAL
 
 
 def test_constant_cache_under_eviction_pressure():
