@@ -1,13 +1,8 @@
 // Instances and dispatch of the augmented Gaussian-sum filter kernel (agsf_scan.hpp) over the compiled (n, m) table.
 #include "agsf_scan.hpp"
+#include "user_model.hpp"
 
 namespace bf {
-
-int launch_agsf_user_impl(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
-                          const int32_t nc[3], const uint32_t key[2], const float opt[2], const bf_carry* carry, const bf_out_desc* out,
-                          int* d_leaf_idx, int variant, hipStream_t stream);  // user_model.hip
-
-const bf_user_model* registry_jit_handle(const bf_model* p, bool hw_arith);   // user_model.hip
 
 int launch_agsf_ekf(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, const int32_t nc[3],
                     const uint32_t key[2], const float opt[2], const bf_carry* carry, const bf_out_desc* out, int* d_leaf_idx,

@@ -556,26 +556,14 @@ agsf_scan_kernel(typename NODES::Arg mdl, CView y, UView uin, CarryView carry, A
 
 #ifndef BF_JIT
 template <int N, int M, class NODES, int NW>
-static inline int launch_agsf_geom(typename NODES::Arg arg, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
-                                   const int32_t nc[3], const uint32_t key[2], const float opt[2], const bf_carry* carry,
-                                   const bf_out_desc* out, int* d_leaf_idx, int variant, int MP, const float* d_tvq, const float* d_tvr,
+static inline int launch_agsf_geom(typename NODES::Arg arg, const AgsfLaunch& L, long long B, long long T, const int32_t nc[3],
+                                   const uint32_t key[2], const float opt[2], int variant, const float* d_tvq, const float* d_tvr,
                                    hipStream_t stream) {
-  constexpr int NT = NW == 1 ? 256 : 64 * NW;
-  const int carry_records = NW == 1 ? 256 : ((nc[0] + 3) & ~3);
-  const size_t lds_bytes = agsf_lds_bytes(N, NW, nc[0]);
-  if (lds_bytes > 160 * 1024)
-    return set_error(BF_EUNSUPPORTED, "augmented Gaussian-sum filter: %d leaves and %d components of dimension %d exceed the 160 KiB LDS",
-                     nc[0] * nc[1] * nc[2], nc[0], N);
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  UView uv{u && u->ptr ? u->ptr : nullptr, u ? u->sB : 0, u ? u->sT : 0};
-  CarryView cv{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
-  AgsfOut ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs), d_leaf_idx};
   auto kern = agsf_scan_kernel<N, M, NODES, NW>;
-  if (lds_bytes > 64 * 1024)
-    BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  const int tpb = NT / MP;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((B + tpb - 1) / tpb)), dim3(NT), lds_bytes, stream, arg, yv, uv, cv, ov, B, T, nc[0],
-                     nc[1], nc[2], MP, opt[0], opt[1], key[0], key[1], variant, carry_records, d_tvq, d_tvr);
+  if (L.lds_bytes > 64 * 1024)
+    BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes));
+  hipLaunchKernelGGL(kern, dim3(L.grid), dim3(L.nt), L.lds_bytes, stream, arg, L.y, L.u, L.carry, L.out, B, T, nc[0], nc[1], nc[2], L.MP,
+                     opt[0], opt[1], key[0], key[1], variant, L.carry_records, d_tvq, d_tvr);
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;
 }
@@ -585,34 +573,19 @@ static inline int launch_agsf_nodes(typename NODES::Arg arg, const bf_cstream* y
                                     const int32_t nc[3], const uint32_t key[2], const float opt[2], const bf_carry* carry,
                                     const bf_out_desc* out, int* d_leaf_idx, int variant, const float* d_tvq, const float* d_tvr,
                                     hipStream_t stream) {
-  const long long Mleaf = (long long)nc[0] * nc[1] * nc[2];
-  if (Mleaf > 1024)
-    return set_error(BF_EUNSUPPORTED, "augmented Gaussian-sum filter: %lld leaves per trajectory exceed one workgroup (1024)", Mleaf);
-  int MP = 1;
-  while (MP < Mleaf) MP <<= 1;
-  if (out->pred_means.ptr || out->pred_covs.ptr || out->coll_mean.ptr || out->coll_cov.ptr || out->loglik.ptr)
-    return set_error(BF_EINVAL, "the augmented filter emits weights, means and covariances only (inference.py:771-775)");
-#define BF_GEOM(NW_) return launch_agsf_geom<N, M, NODES, NW_>(arg, y, u, B, T, nc, key, opt, carry, out, d_leaf_idx, variant, MP, d_tvq, d_tvr, stream)
-  if (MP <= 64) BF_GEOM(1);
-  if constexpr (N <= 4) {  // the multi-wave geometries are built for the small state dimensions only (build time, LDS)
-    if (MP <= 128) {  // e.g. the [5, 5, 5] tree of the reference's own test (docs/tests/test_inference.py): 125 leaves on 2 waves
-      MP = 128;
-      BF_GEOM(2);
-    }
-    if (MP <= 256) {
-      MP = 256;
-      BF_GEOM(4);
-    }
-    if (MP <= 512) {  // e.g. the [100, 2, 2] tree of BOT_Experiment_script.py:118: 400 leaves on 8 waves, two trajectories per CU
-      MP = 512;
-      BF_GEOM(8);
-    }
-    MP = 1024;
+  AgsfLaunch L;
+  const int rc = prepare_agsf(N, y, u, B, nc, carry, out, d_leaf_idx, L);
+  if (rc != BF_OK) return rc;
+#define BF_GEOM(NW_) return launch_agsf_geom<N, M, NODES, NW_>(arg, L, B, T, nc, key, opt, variant, d_tvq, d_tvr, stream)
+  if (L.nw == 1) BF_GEOM(1);
+  if constexpr (N <= 4) {  // (prepare_agsf refuses more than one wave per trajectory above this state dimension)
+    if (L.nw == 2) BF_GEOM(2);
+    if (L.nw == 4) BF_GEOM(4);
+    if (L.nw == 8) BF_GEOM(8);
     BF_GEOM(16);
-  } else {
-    return set_error(BF_EUNSUPPORTED, "augmented Gaussian-sum filter: more than 64 leaves per trajectory need state_dim <= 4");
   }
 #undef BF_GEOM
+  return set_error(BF_EUNSUPPORTED, "augmented Gaussian-sum filter: no compiled geometry of %d waves for state_dim %d", L.nw, N);
 }
 
 template <int N, int M>
@@ -636,21 +609,12 @@ template <int N, int DQ, int M, int DR>
 static inline int launch_uagsf(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
                                long long T, const int32_t nc[3], const uint32_t key[2], const float opt[2], const bf_carry* carry,
                                const bf_out_desc* out, int* d_leaf_idx, int variant, hipStream_t stream) {
-  UkfModel<N, DQ, M, DR> h;
-  std::memset(&h, 0, sizeof(h));  // the constant cache compares contents
-  std::vector<float> tvsq, tvsr;
-  int rc = fill_ukf_model<N, DQ, M, DR>(p, up, h, &tvsq, &tvsr);
+  static_assert(sizeof(UkfModel<N, DQ, M, DR>) == 4 * ukf_model_words(N, DQ, M, DR), "UkfModel: 4-byte members in declaration order, no padding");
+  UkfLaunch L;
+  const int rc = prepare_ukf_model(p, up, 0, T, stream, L);
   if (rc != BF_OK) return rc;
-  if ((p->Q_steps > 1 && p->Q_steps != T) || (p->R_steps > 1 && p->R_steps != T))
-    return set_error(BF_EINVAL, "time-varying covariances need one matrix per step (Q_steps / R_steps = T = %lld)", T);
-  const void* dv = nullptr;
-  rc = device_constants(&h, sizeof(h), stream, &dv);
-  if (rc != BF_OK) return rc;
-  const UkfModel<N, DQ, M, DR>* d_mdl = static_cast<const UkfModel<N, DQ, M, DR>*>(dv);
-  const float *d_tvq = nullptr, *d_tvr = nullptr;
-  if ((rc = upload_table(tvsq, stream, &d_tvq)) != BF_OK || (rc = upload_table(tvsr, stream, &d_tvr)) != BF_OK) return rc;
-  return launch_agsf_nodes<N, M, UkfNodes<N, DQ, M, DR>>(d_mdl, y, u, B, T, nc, key, opt, carry, out, d_leaf_idx, variant, d_tvq, d_tvr,
-                                                         stream);
+  return launch_agsf_nodes<N, M, UkfNodes<N, DQ, M, DR>>(static_cast<const UkfModel<N, DQ, M, DR>*>(L.d_mdl), y, u, B, T, nc, key, opt, carry, out,
+                                                         d_leaf_idx, variant, L.d_tvq, L.d_tvr, stream);
 }
 
 #endif  // BF_JIT

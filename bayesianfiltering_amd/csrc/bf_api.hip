@@ -2,6 +2,7 @@
 // the kf_*/gsf_*/bpf_* translation units.
 #include <cstring>
 #include "bf_common.hpp"
+#include "user_model.hpp"
 #include "bf_rng.hpp"
 
 namespace bf {
@@ -68,9 +69,6 @@ CallOverrides& call_overrides() {
 
 // tuning options: process-wide defaults (atomics) with per-call overrides (bf_common.hpp: Option)
 extern Option g_bpf_variant;
-bool gsf_user_regs_eligible(const bf_model* p, int K, const bf_out_desc* out);   // user_model.hip
-int launch_gsf_user_regs_impl(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K, const bf_carry* carry,
-                              const bf_out_desc* out, hipStream_t stream);
 extern Option g_bpf_hbm_mode;
 extern Option g_bpf_spec;
 extern Option g_bpf_arith;

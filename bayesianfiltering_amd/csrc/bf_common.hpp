@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <atomic>
 #include "../../include/bayesfilt.h"
+#include "bf_views.hpp"  // SView, CView, OutViews, CarryView, UView, UViewG
 
 namespace bf {
 
@@ -60,31 +61,7 @@ struct CallOptionScope {   // at the top of every filter entry point: overrides 
 // uploaded stream-ordered through pinned staging: no host synchronisation, nothing to free (const_cache.hip).
 int device_constants(const void* host, size_t bytes, hipStream_t stream, const void** d_out);
 
-// Device-side view of one strided stream with the component axis folded in by the caller.
-struct SView {
-  float* p;
-  long long sB, sK, sT, sE;
-};
-struct CView {
-  const float* p;
-  long long sB, sT, sE;
-};
-
 inline SView make_sview(const bf_stream& s) { return SView{s.ptr, s.sB, s.sK, s.sT, s.sE}; }
-
-struct OutViews {
-  SView w, m, P, pm, pP, ll;
-  SView cm, cP;  // collapsed mean / covariance of the filtered mixture (Gaussian-sum kernel only)
-};
-
-struct CarryView {
-  const float* w_in;
-  const float* m_in;
-  const float* P_in;
-  float* w_out;
-  float* m_out;
-  float* P_out;
-};
 
 // Layout classification of an output descriptor (see bayesfilt.h, bf_stream).
 enum Layout { LAYOUT_GENERIC = 0, LAYOUT_REFERENCE = 1, LAYOUT_BATCH_INNER = 2 };

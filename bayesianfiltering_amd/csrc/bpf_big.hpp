@@ -352,24 +352,31 @@ bpf_big_kernel(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float
 }
 
 #ifndef BF_JIT
-template <int N, int DQ, int M>
-static inline int launch_bpf_big_dims(const BpfModel<N, DQ, M>* d_mdl, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
-                                 int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out,
-                                 hipStream_t stream) {
+// launch preparation, shared with the kernel built at run time (bpf_scan.hip): the capacity check and the stream-ordered
+// scratch of a launch, carved from one allocation (*buf: the caller frees it on the stream after the launch)
+static inline int prepare_bpf_big(int n, long long B, int NP, hipStream_t stream, BigScratch& sc, float** buf) {
   if (NP > BIG_NT * BIG_MAXCH)
     return set_error(BF_EUNSUPPORTED, "bootstrap particle filter: %d particles exceed the capacity of %d per trajectory", NP,
                      BIG_NT * BIG_MAXCH);
   const size_t per = (size_t)B * NP;
-  float* buf = nullptr;
-  const size_t floats = per * (2 * N + 3);
-  BF_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&buf), sizeof(float) * floats + sizeof(int) * per, stream));
-  BigScratch sc;
-  sc.xa = buf;
-  sc.xb = sc.xa + per * N;
-  sc.w = sc.xb + per * N;
+  BF_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(buf), sizeof(float) * per * (2 * (size_t)n + 3) + sizeof(int) * per, stream));
+  sc.xa = *buf;
+  sc.xb = sc.xa + per * n;
+  sc.w = sc.xb + per * n;
   sc.ll = sc.w + per;
   sc.cdf = sc.ll + per;
   sc.anc = reinterpret_cast<int*>(sc.cdf + per);
+  return BF_OK;
+}
+
+template <int N, int DQ, int M>
+static inline int launch_bpf_big_dims(const BpfModel<N, DQ, M>* d_mdl, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
+                                 int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out,
+                                 hipStream_t stream) {
+  BigScratch sc;
+  float* buf = nullptr;
+  const int rc = prepare_bpf_big(N, B, NP, stream, sc, &buf);
+  if (rc != BF_OK) return rc;
   CView yv{y->ptr, y->sB, y->sT, y->sE};
   hipLaunchKernelGGL((bpf_big_kernel<N, DQ, M>), dim3((unsigned)B), dim3(BIG_NT), 0, stream, d_mdl, yv, (u && u->ptr) ? u->ptr : nullptr,
                      u ? u->sB : 0, u ? u->sT : 0, cr, out, sc, B, T, NP, ess, resampler, key[0], key[1]);

@@ -1,6 +1,7 @@
 // Dispatch of the bootstrap particle filter over the compiled (n, dq, m) table (instantiations in
-// bpf_group_{a,b,c}.hip) and the stand-alone resampler.
-#include "bpf_scan.hpp"
+// bpf_group_{a,b,c}.hip), the launch of the same kernels built at run time, and the stand-alone resampler.
+#include "bpf_big.hpp"   // (brings bpf_scan.hpp)
+#include "user_model.hpp"
 
 namespace bf {
 
@@ -48,38 +49,75 @@ BF_DECL(launch_bpf_group_b);
 BF_DECL(launch_bpf_group_c);
 #undef BF_DECL
 
-int launch_bpf_user_impl(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP, float ess,
-                         int resampler, const uint32_t key[2], const bf_bpf_carry* carry, const bf_bpf_out* o, hipStream_t stream);
-
-const bf_user_model* registry_jit_handle(const bf_model* p, bool hw_arith);   // user_model.hip
-int launch_bpf_hw_arith_impl(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP, float ess,
-                             int resampler, const uint32_t key[2], const bf_bpf_carry* carry, const bf_bpf_out* o, hipStream_t stream);
+// The particle filter built at run time (user_model.hpp): around the functions of a handle from source (the caller's functions
+// see the CANONICAL arithmetic of the weight path, so a function written like its registry twin gives the registry twin's bits),
+// or -- an internal handle without sources -- around the registry's, for dimensions without a compiled instance and for
+// bf_set_option "bpf_arith" = 1.  State in registers at the compile-time dimensions of the handle, one kernel per particle
+// capacity; beyond the register capacities the particles live in HBM (bpf_big.hpp), up to 2^20 per trajectory.
+static int launch_bpf_jit(const bf_user_model* um, const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
+                          int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out, hipStream_t stream) {
+  int rc = check_user_model(um, &bp->ssm);
+  if (rc != BF_OK || (rc = check_user_device(um)) != BF_OK) return rc;
+  const int N = bp->ssm.n;
+  BpfModelLaunch L;
+  if ((rc = prepare_bpf_model(bp, um->user_flags(), stream, L)) != BF_OK) return rc;
+  // registry models (the hardware-arithmetic build): the model structure as a compile-time spec where bpf_scan.hpp has one
+  const int spec = !um->hw_arith ? JIT_SPEC_USER : (L.l96_pick ? JIT_SPEC_L96_PICK : JIT_SPEC_RUNTIME);
+  int ppt, nw;
+  bpf_capacity(NP, N, &ppt, &nw);
+  hipFunction_t fn = nullptr;
+  if ((rc = user_kernel(um, ppt == 0 ? JIT_BPF_BIG : JIT_BPF, ppt, ppt == 0 ? 0 : nw, spec, &fn)) != BF_OK) return rc;
+  if (ppt == 0) {
+    BigScratch sc;
+    float* buf = nullptr;
+    if ((rc = prepare_bpf_big(N, B, NP, stream, sc, &buf)) != BF_OK) return rc;
+    CView yv{y->ptr, y->sB, y->sT, y->sE};
+    const float* uptr = (u && u->ptr) ? u->ptr : nullptr;
+    long long u_sB = u ? u->sB : 0, u_sT = u ? u->sT : 0;
+    BpfCarry crv = cr;
+    BpfOut ov = out;
+    uint32_t k0 = key[0], k1 = key[1];
+    void* args[] = {&L.d_mdl, &yv, &uptr, &u_sB, &u_sT, &crv, &ov, &sc, &B, &T, &NP, &ess, &resampler, &k0, &k1};
+    const hipError_t le = hipModuleLaunchKernel(fn, (unsigned)B, 1, 1, BIG_NT, 1, 1, 0, stream, args, nullptr);
+    const hipError_t fe = hipFreeAsync(buf, stream);
+    BF_HIP_CHECK(le);
+    BF_HIP_CHECK(fe);
+    return BF_OK;
+  }
+  const size_t lds_bytes = bpf_lds_bytes(N, ppt, nw);
+  if (lds_bytes > 160 * 1024) return set_error(BF_EUNSUPPORTED, "particle tile exceeds the 160 KiB LDS");
+  struct { const void* mdl; BpfArgs<1, 1, 1> a; } packed;   // the kernarg segment: the model pointer, then the struct
+  packed.mdl = L.d_mdl;
+  fill_bpf_args(packed.a, y, u, B, T, NP, ess, resampler, key, cr, out);
+  size_t psz = sizeof(packed);
+  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &packed, HIP_LAUNCH_PARAM_BUFFER_SIZE, &psz, HIP_LAUNCH_PARAM_END};
+  BF_HIP_CHECK(hipModuleLaunchKernel(fn, (unsigned)B, 1, 1, (unsigned)(64 * nw), 1, 1, (unsigned)lds_bytes, stream, nullptr, config));
+  return BF_OK;
+}
 
 int launch_bpf(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP,
                float ess, int resampler, const uint32_t key[2], const bf_bpf_carry* carry, const bf_bpf_out* o,
                hipStream_t stream) {
-  BpfCarry cr{carry ? carry->x_in : nullptr, carry ? carry->w_in : nullptr, carry ? carry->key_in : nullptr,
-              carry ? carry->x_out : nullptr, carry ? carry->w_out : nullptr, carry ? carry->key_out : nullptr};
-  BpfOut out{o->weights, o->w_sB, o->w_sN, o->w_sT, o->particles, o->x_sB, o->x_sN, o->x_sT, o->ancestors,
-             o->mean, o->ess, o->logz, o->resampled};
-  if (bp->ssm.user)   // functions from the caller's source: the kernel compiled at run time for this model (user_model.hip)
-    return launch_bpf_user_impl(bp, y, u, B, T, NP, ess, resampler, key, carry, o, stream);
+  const BpfCarry cr = make_bpf_carry(carry);
+  const BpfOut out = make_bpf_out(o);
+  if (bp->ssm.user)   // functions from the caller's source: the kernel compiled at run time for this model
+    return launch_bpf_jit(bp->ssm.user, bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
   if (bp->ssm.dyn_id == BF_FN_USER || bp->ssm.emi_id == BF_FN_USER)
     return set_error(BF_EINVAL, "dyn_id / emi_id = BF_FN_USER needs bf_model.user (bf_user_model_create)");
-  if (g_bpf_arith == 1)   // the same kernel with the hardware's transcendentals, compiled at run time (user_model.hip)
-    return launch_bpf_hw_arith_impl(bp, y, u, B, T, NP, ess, resampler, key, carry, o, stream);
   bool matched = false;
-  int rc = launch_bpf_group_a(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
-  if (matched) return rc;
-  rc = launch_bpf_group_b(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
-  if (matched) return rc;
-  rc = launch_bpf_group_c(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
-  if (matched) return rc;
-  // no compiled instance for these dimensions: the same kernel, compiled now (needs hiprtc; in-register particle counts)
-  bf_bpf_model jit = *bp;
-  jit.ssm.user = registry_jit_handle(&bp->ssm, false);
-  if (!jit.ssm.user) return set_error(BF_ENOGPU, "no current device");
-  return launch_bpf_user_impl(&jit, y, u, B, T, NP, ess, resampler, key, carry, o, stream);
+  int rc = BF_OK;
+  if (g_bpf_arith != 1) {   // (1: the same kernel with the hardware's transcendentals, compiled at run time)
+    rc = launch_bpf_group_a(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
+    if (matched) return rc;
+    rc = launch_bpf_group_b(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
+    if (matched) return rc;
+    rc = launch_bpf_group_c(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
+    if (matched) return rc;
+  }
+  // hardware arithmetic, or no compiled instance for these dimensions: the same kernel, compiled now (needs hiprtc)
+  const bf_user_model* um = registry_jit_handle(&bp->ssm, g_bpf_arith == 1);
+  if (!um) return set_error(BF_ENOGPU, "no current device");
+  return launch_bpf_jit(um, bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
 }
 
 }  // namespace bf

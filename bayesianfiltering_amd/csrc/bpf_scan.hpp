@@ -251,7 +251,7 @@ struct BpfArgs {
 };
 
 // The kernel proper, as a device function: every kernel entry that runs it -- bpf_scan_kernel below, the `extern "C"` entries
-// of a build compiled at run time with a caller's functions (user_model.hip) -- has the parameter list
+// of a build compiled at run time with a caller's functions (jit_source.hip) -- has the parameter list
 // (const BpfModel*, BpfArgs by value), which is what the kernarg-segment reads below rely on.
 template <int N, int DQ, int M, int PPT, int NW, class SP = SpecRuntime>
 __device__ __forceinline__ void bpf_scan_body(const BpfModel<N, DQ, M>* __restrict__ mdlp) {
@@ -583,15 +583,34 @@ bpf_scan_kernel(const BpfModel<N, DQ, M>* __restrict__ mdlp, const BpfArgs<N, DQ
 
 #ifndef BF_JIT   // host side: launches
 // ---------------------------------------------------------------------------------------
-template <int N, int DQ, int M, int PPT, int NW, class SP = SpecRuntime>
-static inline int launch_bpf_cfg(const BpfModel<N, DQ, M>* d_mdl, const bf_cstream* y, const bf_cstream* u, long long B,
-                          long long T, int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr,
-                          const BpfOut& out, hipStream_t stream) {
-  constexpr int CAP = 64 * NW * PPT;
-  constexpr int DCH = (PPT >= 16) ? 1 : ((N >= 8) ? 8 : N);
-  const size_t lds_bytes = sizeof(float) * (size_t)(((cdf_words(CAP) + 3) & ~3) + 64 + ((NW * N + 3) & ~3) + CAP * DCH);
-  if (lds_bytes > 160 * 1024) return set_error(BF_EUNSUPPORTED, "particle tile exceeds the 160 KiB LDS");
-  BpfArgs<N, DQ, M> a;
+// Launch preparation, shared by the compiled instances below and the kernels built at run time (bpf_scan.hip).
+static inline BpfCarry make_bpf_carry(const bf_bpf_carry* c) {
+  return BpfCarry{c ? c->x_in : nullptr, c ? c->w_in : nullptr, c ? c->key_in : nullptr, c ? c->x_out : nullptr, c ? c->w_out : nullptr, c ? c->key_out : nullptr};
+}
+static inline BpfOut make_bpf_out(const bf_bpf_out* o) {
+  return BpfOut{o->weights, o->w_sB, o->w_sN, o->w_sT, o->particles, o->x_sB, o->x_sN, o->x_sT, o->ancestors, o->mean, o->ess, o->logz, o->resampled};
+}
+
+// smallest in-register particle capacity that holds NP: 64 * nw threads with ppt particles each; ppt = 0: beyond the registers
+static inline void bpf_capacity(int NP, int n, int* ppt, int* nw) {
+  *ppt = 1;
+  if (NP <= 64) *nw = 1;
+  else if (NP <= 128) *nw = 2;   // (the reference's usual 100)
+  else if (NP <= 256) *nw = 4;
+  else if (NP <= 512) *nw = 8;
+  else if (NP <= 1024) *nw = 16;
+  else if (NP <= 4096 && n <= 16) { *ppt = 4; *nw = 16; }
+  else { *ppt = 0; *nw = 16; }
+}
+// dynamic LDS of a launch: CDF, reduction scratch, per-wave means, the gather tile (DCH state dimensions per pass)
+static inline size_t bpf_lds_bytes(int n, int ppt, int nw) {
+  const int cap = 64 * nw * ppt, dch = (ppt >= 16) ? 1 : ((n >= 8) ? 8 : n);
+  return sizeof(float) * (size_t)(((cdf_words(cap) + 3) & ~3) + 64 + ((nw * n + 3) & ~3) + cap * dch);
+}
+// the argument struct, which does not depend on the dimensions (BpfArgs<1, 1, 1> for a kernel built at run time)
+template <int N, int DQ, int M>
+static inline void fill_bpf_args(BpfArgs<N, DQ, M>& a, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP, float ess,
+                                 int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out) {
   std::memset(&a, 0, sizeof(a));
   a.y = CView{y->ptr, y->sB, y->sT, y->sE};
   a.uptr = (u && u->ptr) ? u->ptr : nullptr;
@@ -599,6 +618,33 @@ static inline int launch_bpf_cfg(const BpfModel<N, DQ, M>* d_mdl, const bf_cstre
   a.u_sT = u ? u->sT : 0;
   a.carry = cr; a.out = out; a.B = B; a.T = T; a.NP = NP; a.ess_threshold = ess; a.resampler = resampler;
   a.key0 = key[0]; a.key1 = key[1];
+}
+// the model on the device, as the flat words of a BpfModel<N, DQ, M>; l96_pick: the structure BASELINE configs[3] has -- Lorenz-96
+// dynamics with identity noise input, diagonal chol(Q), an emission that selects the even states, diagonal chol(R) -- for which
+// SpecFixed instances exist (results are bit-identical either way: tests/test_bpf_gpu.py)
+struct BpfModelLaunch {
+  const void* d_mdl;
+  bool l96_pick;
+};
+static inline int prepare_bpf_model(const bf_bpf_model* bp, int user_flags, hipStream_t stream, BpfModelLaunch& L) {
+  const bf_model* p = &bp->ssm;
+  std::vector<uint32_t> words(bpf_model_words(p->n, p->dq, p->m), 0u);   // zeroed: the constant cache compares contents
+  const BpfModelView v = bpf_model_view_flat(words.data(), p->n, p->dq, p->m);
+  const int rc = fill_bpf_model_view(bp, v, user_flags, bp->lp_theta, bp->n_lp_theta);
+  if (rc != BF_OK) return rc;
+  L.l96_pick = p->n == p->dq && p->n >= 8 && 2 * p->m <= p->n + 1 && *v.dyn_id == DYN_LORENZ96 && *v.emi_id == EMI_LINEAR && *v.g_identity &&
+               *v.lq_diag && *v.lr_diag && *v.h_pick;
+  return device_constants(words.data(), sizeof(uint32_t) * words.size(), stream, &L.d_mdl);
+}
+
+template <int N, int DQ, int M, int PPT, int NW, class SP = SpecRuntime>
+static inline int launch_bpf_cfg(const BpfModel<N, DQ, M>* d_mdl, const bf_cstream* y, const bf_cstream* u, long long B,
+                          long long T, int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr,
+                          const BpfOut& out, hipStream_t stream) {
+  const size_t lds_bytes = bpf_lds_bytes(N, PPT, NW);
+  if (lds_bytes > 160 * 1024) return set_error(BF_EUNSUPPORTED, "particle tile exceeds the 160 KiB LDS");
+  BpfArgs<N, DQ, M> a;
+  fill_bpf_args(a, y, u, B, T, NP, ess, resampler, key, cr, out);
   auto kern = bpf_scan_kernel<N, DQ, M, PPT, NW, SP>;
   if (lds_bytes > 64 * 1024)
     BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -621,48 +667,43 @@ template <int N, int DQ, int M>
 static inline int launch_bpf_dims(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
                            int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out,
                            hipStream_t stream) {
-  BpfModel<N, DQ, M> h;
-  std::memset(&h, 0, sizeof(h));  // the constant cache compares contents
-  int rc = fill_bpf_model<N, DQ, M>(bp, h);
+  static_assert(sizeof(BpfModel<N, DQ, M>) == 4 * bpf_model_words(N, DQ, M), "BpfModel: 4-byte members in declaration order, no padding");
+  BpfModelLaunch L;
+  const int rc = prepare_bpf_model(bp, 0, stream, L);
   if (rc != BF_OK) return rc;
-  const void* dv = nullptr;
-  rc = device_constants(&h, sizeof(h), stream, &dv);
-  if (rc != BF_OK) return rc;
-  const BpfModel<N, DQ, M>* d_mdl = static_cast<const BpfModel<N, DQ, M>*>(dv);
+  const BpfModel<N, DQ, M>* d_mdl = static_cast<const BpfModel<N, DQ, M>*>(L.d_mdl);
   // few trajectories with thousands of particles: one workgroup per trajectory would leave the chip idle (a step of the
   // in-register kernel takes ~19 us per 1024 particles on its one CU); the workgroup-per-chunk kernels of bpf_wide.hpp
   // spread the particles over the CUs at ~25 us of launches per step
   const bool spread = NP > 2048 && B <= 32 && g_bpf_hbm_mode != 1;
   if (spread) return launch_bpf_hbm_dims<N, DQ, M>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
-  // smallest compiled particle capacity that holds NP, for the model's structure as a run-time (SpecRuntime) or compile-time
-  // (SpecFixed) property
+  int ppt, nw;
+  bpf_capacity(NP, N, &ppt, &nw);
+  // the compiled instance of that capacity, for the model's structure as a run-time (SpecRuntime) or compile-time (SpecFixed) property
   auto by_capacity = [&](auto spec) -> int {
     using SP = decltype(spec);
-    if (NP <= 64) return launch_bpf_cfg<N, DQ, M, 1, 1, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
-    if (NP <= 128) return launch_bpf_cfg<N, DQ, M, 1, 2, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);   // (the reference's usual 100)
-    if (NP <= 256) return launch_bpf_cfg<N, DQ, M, 1, 4, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
-    if (NP <= 512) return launch_bpf_cfg<N, DQ, M, 1, 8, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
-    if (NP <= 1024) return launch_bpf_cfg<N, DQ, M, 1, 16, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
-    if (NP <= 4096) {
+#define BF_CFG(PPT_, NW_) return launch_bpf_cfg<N, DQ, M, PPT_, NW_, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream)
+    if (ppt == 1 && nw == 1) BF_CFG(1, 1);
+    if (ppt == 1 && nw == 2) BF_CFG(1, 2);
+    if (ppt == 1 && nw == 4) BF_CFG(1, 4);
+    if (ppt == 1 && nw == 8) BF_CFG(1, 8);
+    if (ppt == 1 && nw == 16) BF_CFG(1, 16);
+    if (ppt == 4) {
       // two geometries for the largest capacity: 1024 threads x 4 particles (128-VGPR budget, variant 0, the default) or
       // 512 threads x 8 particles (256-VGPR budget, variant 1)
-      if (g_bpf_variant == 1) return launch_bpf_cfg<N, DQ, M, 8, 8, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
-      return launch_bpf_cfg<N, DQ, M, 4, 16, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
+      if (g_bpf_variant == 1) BF_CFG(8, 8);
+      BF_CFG(4, 16);
     }
     if (NP <= 16384 && N <= 4 && DQ <= 4) {
       // small states: 16 particles per thread still fit the registers (1024 threads x 16; the gather goes one
       // state dimension at a time so that CDF + tile stay within the LDS)
-      if constexpr (N <= 4 && DQ <= 4) return launch_bpf_cfg<N, DQ, M, 16, 16, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
+      if constexpr (N <= 4 && DQ <= 4) BF_CFG(16, 16);
     }
+#undef BF_CFG
     return launch_bpf_hbm_dims<N, DQ, M>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);  // particles in HBM (bpf_big.hpp, bpf_wide.hpp)
   };
-  // The structure BASELINE configs[3] has -- Lorenz-96 dynamics with identity noise input, diagonal chol(Q), an emission
-  // that selects the even states, diagonal chol(R) -- as a compile-time instance (bf_set_option "bpf_spec" = 0 turns it
-  // off; results are bit-identical either way: tests/test_bpf_gpu.py)
-  if constexpr (N == DQ && N >= 8 && 2 * M <= N + 1) {
-    if (g_bpf_spec != 0 && h.dyn_id == DYN_LORENZ96 && h.emi_id == EMI_LINEAR && h.g_identity && h.lq_diag && h.lr_diag && h.h_pick && NP <= 4096) {
-      return by_capacity(SpecFixed<DYN_LORENZ96, EMI_LINEAR, true, true, true, true>{});
-    }
+  if constexpr (N == DQ && N >= 8 && 2 * M <= N + 1) {   // (bf_set_option "bpf_spec" = 0 turns the compile-time structure off)
+    if (g_bpf_spec != 0 && L.l96_pick && NP <= 4096) return by_capacity(SpecFixed<DYN_LORENZ96, EMI_LINEAR, true, true, true, true>{});
   }
   return by_capacity(SpecRuntime{});
 }

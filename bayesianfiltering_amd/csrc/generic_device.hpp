@@ -1,10 +1,11 @@
 // generic_device.hpp: the device side of the run-time-dimension scan (see generic_scan.hip for the design notes).
 // It is compiled twice: ahead of time into libbayesfilt_hip.so (generic_scan.hip), and at RUN time by hiprtc together
-// with a user's own dynamics / emission functions (user_model.hip: BF_JIT, BF_USER_DYN / BF_USER_EMI) -- the text of this
+// with a user's own dynamics / emission functions (jit_source.hip: BF_JIT, BF_USER_DYN / BF_USER_EMI) -- the text of this
 // file is embedded in the library for that purpose, so it must stay self-contained under BF_JIT.
 #pragma once
 #ifdef BF_JIT
 // hiprtc build: the few helpers the ahead-of-time build takes from bf_common.hpp / kf_math.hpp / scan_common.hpp / models.hpp
+// (the kernel-argument views, bf_views.hpp, precede this text in both builds)
 namespace bf {
 #define BF_UNROLL _Pragma("unroll")
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
@@ -22,37 +23,12 @@ __device__ __forceinline__ void lds_barrier() {
 }
 enum { DYN_LINEAR = 0, DYN_LORENZ96 = 1, DYN_LORENZ63 = 2, DYN_MANEUVER_BOT = 3, DYN_SINE = 4, DYN_GROWTH = 5 };
 enum { EMI_LINEAR = 0, EMI_BEARING_RANGE = 1, EMI_QUADRATIC = 2, EMI_STOCH_VOL = 3, EMI_BEARING = 4 };
-struct SView {
-  float* p;
-  long long sB, sK, sT, sE;
-};
-struct CView {
-  const float* p;
-  long long sB, sT, sE;
-};
-struct OutViews {
-  SView w, m, P, pm, pP, ll;
-  SView cm, cP;
-};
-struct CarryView {
-  const float* w_in;
-  const float* m_in;
-  const float* P_in;
-  float* w_out;
-  float* m_out;
-  float* P_out;
-};
 }  // namespace bf
 #endif
 
 namespace bf {
 
 enum { DYN_USER = 100, EMI_USER = 100 };  // functions compiled at run time from the caller's source (user_model.hip)
-
-struct UViewG {
-  const float* p;
-  long long sB, sT;
-};
 
 struct GenModel {  // pointers are DEVICE pointers into one constant block (const_cache.hip)
   int dyn_id, emi_id, n, dq, m, dr;

@@ -28,6 +28,7 @@
 #include "models.hpp"
 #include "bf_rng.hpp"
 #include "generic_device.hpp"
+#include "user_model.hpp"
 
 namespace bf {
 
@@ -159,9 +160,6 @@ static int gen_nt64_max() {
   }();
   return v;
 }
-
-int launch_user_kernel(const bf_user_model* um, int nt, unsigned grid, size_t lds_bytes, hipStream_t stream, void** args);
-int check_user_model(const bf_user_model* um, const bf_model* p);
 
 int launch_gsf_generic(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
                        const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {

@@ -69,11 +69,6 @@ struct GsfCfg {
   static constexpr bool STAGED_OK = TP::OK && TM::OK && TW::OK;
 };
 
-struct UView {
-  const float* p;  // NULL: inputs = zeros((T, 1)) as inference.py:23
-  long long sB, sT;
-};
-
 enum { SPEC_GENERIC = 0, SPEC_L96_PICK = 1 };
 constexpr int GSF_HDR = 32;  // LDS floats ahead of the tiles: cross-wave reduction scratch [0..7] scalar, [8..23] per lane-in-group
 

@@ -1,5 +1,5 @@
 // sample_ssm.hpp: the device side of NonlinearSSM.sample (gaussfiltax/models.py:240-289) -- see sample_ssm.hip.  A header so
-// that user_model.hip can hand the same code to hiprtc with the caller's f / h compiled in (SpecUser).
+// that jit_source.hip can hand the same code to hiprtc with the caller's f / h compiled in (SpecUser).
 #pragma once
 #include "bf_common.hpp"
 #include "bf_rng.hpp"

@@ -1,17 +1,61 @@
 // Instances and dispatch of the unscented Gaussian-sum filter kernel (ugsf_scan.hpp) over the compiled
-// (n, dq, m, dr) table.
+// (n, dq, m, dr) table, and the launches of the same kernel built at run time (user_model.hpp).
 #include "ugsf_scan.hpp"
+#include "user_model.hpp"
 
 namespace bf {
 
-int launch_ugsf_user_impl(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
-                          int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream);
+// ugsf_scan_body built around the handle's functions: `kind` JIT_UGSF (sigma points through f and h) or JIT_GSF_REGS
+// (extended-Kalman operations, Jacobians by dual numbers; user_flags bit 2: the covariances themselves, not their roots)
+static int launch_ugsf_jit(int kind, const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
+                           long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
+  const bf_user_model* um = p->user;
+  hipFunction_t fn = nullptr;
+  int rc = user_kernel(um, kind, 0, 0, JIT_SPEC_USER, &fn);
+  if (rc != BF_OK) return rc;
+  UgsfLaunch L;
+  rc = prepare_ugsf(p, up, (um->user_flags() & 3) | (kind == JIT_GSF_REGS ? 4 : 0), y, u, B, T, K, carry, out, stream, L);
+  if (rc != BF_OK) return rc;
+  void* args[] = {&L.d_mdl, &L.y, &L.uptr, &L.u_sB, &L.u_sT, &L.carry, &L.out, &B, &T, &K, &L.KP, &L.d_tvq, &L.d_tvr};
+  BF_HIP_CHECK(hipModuleLaunchKernel(fn, L.grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr));
+  return BF_OK;
+}
 
-const bf_user_model* registry_jit_handle(const bf_model* p, bool hw_arith);   // user_model.hip
+// The unscented Gaussian-sum scan with the caller's functions: state in registers, so the state dimension is bounded like the
+// compiled instances' (n <= 8)
+static int launch_ugsf_user_impl(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
+                                 int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
+  const int rc = check_user_model(p->user, p);
+  if (rc != BF_OK) return rc;
+  if (p->user->has_lp) return set_error(BF_EINVAL, "a log-density from source belongs to the particle filter, not to the unscented filter");
+  if (p->n > 8 || p->dq > 8 || p->m > 8 || p->dr > 8)
+    return set_error(BF_EUNSUPPORTED, "unscented filter with functions from source: dimensions up to 8 (the sigma points live in registers)");
+  return launch_ugsf_jit(JIT_UGSF, p, up, y, u, B, T, K, carry, out, stream);
+}
+
+// bf_gsf_ekf_f32 with functions from source and small dimensions: the Gaussian-sum scan of inference.py:333-371 with one lane per
+// (trajectory, component), mean and covariance in registers, the Jacobians by dual numbers (ugsf_scan.hpp: UserEkfNodes) -- two
+// orders of magnitude faster than the run-time-dimension kernel the same handle also carries (state in LDS, any n), which remains
+// the path for n > 8, for a nonlinear registry function beside one from source, legacy flags, collapsed streams and K > 256.
+bool gsf_user_regs_eligible(const bf_model* p, int K, const bf_out_desc* out) {
+  const bf_user_model* um = p->user;
+  if (!um || um->has_lp || p->flags != 0) return false;
+  if (p->n > 8 || p->dq > 8 || p->m > 8 || p->dr > 8 || K > 256) return false;
+  if (out->coll_mean.ptr || out->coll_cov.ptr) return false;
+  if (!(um->has_dyn || p->dyn_id == DYN_LINEAR) || !(um->has_emi || p->emi_id == EMI_LINEAR)) return false;
+  return true;
+}
+
+int launch_gsf_user_regs_impl(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K, const bf_carry* carry,
+                              const bf_out_desc* out, hipStream_t stream) {
+  const int rc = check_user_model(p->user, p);
+  if (rc != BF_OK) return rc;
+  return launch_ugsf_jit(JIT_GSF_REGS, p, nullptr, y, u, B, T, K, carry, out, stream);
+}
 
 int launch_ugsf_ukf(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
                     long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
-  if (p->user)   // functions from the caller's source: the kernel compiled at run time for this model (user_model.hip)
+  if (p->user)   // functions from the caller's source: the kernel compiled at run time for this model
     return launch_ugsf_user_impl(p, up, y, u, B, T, K, carry, out, stream);
   if (p->dyn_id == BF_FN_USER || p->emi_id == BF_FN_USER)
     return set_error(BF_EINVAL, "dyn_id / emi_id = BF_FN_USER needs bf_model.user (bf_user_model_create)");

@@ -49,7 +49,7 @@ struct UkfModel {
   // unscented-transform constants for the update (L = n + dr) and the prediction (L = n + dq)
   float c_u, ws_u, w0_u, wc_u;  // sqrt(L + lambda), 1 / (2 (L + lambda)), lambda / (L + lambda), w0 + 1 - alpha^2 + beta
   float c_p, ws_p, w0_p, wc_p;
-  float uth_dyn[64], uth_emi[64];   // parameters of functions compiled from the caller's source (user_model.hip)
+  float uth_dyn[64], uth_emi[64];   // parameters of functions compiled from the caller's source (jit_source.hip)
 };
 
 // Symmetric square root of a symmetric positive semi-definite matrix, in place (row-major N x N).
@@ -316,7 +316,7 @@ __device__ __forceinline__ void ukf_predict(const UkfModel<N, DQ, M, DR>& mdl, f
 }
 
 #ifdef BF_USER_EKF_NODES
-// Extended-Kalman node operations around functions compiled from the caller's source (user_model.hip): _predict /
+// Extended-Kalman node operations around functions compiled from the caller's source (jit_source.hip): _predict /
 // _condition_on (inference.py:51-105) with the Jacobians of :58-61 / :82-86 -- jacfwd w.r.t. the state AND w.r.t. the noise, at
 // the noise bias -- by forward-mode dual numbers, one seed direction after the other on the chain's own lane; F_q Q F_q^T and
 // H_r R H_r^T are formed here every step.  A function that is not from source must be the registry's linear one (A x + G q,
@@ -696,42 +696,64 @@ static inline int fill_ukf_model_view(const bf_model* p, const bf_ukf_params* up
   return BF_OK;
 }
 
-template <int N, int DQ, int M, int DR>
-static inline int fill_ukf_model(const bf_model* p, const bf_ukf_params* up, UkfModel<N, DQ, M, DR>& e,
-                                 std::vector<float>* tvsq = nullptr, std::vector<float>* tvsr = nullptr) {
-  static_assert(sizeof(UkfModel<N, DQ, M, DR>) == 4 * ukf_model_words(N, DQ, M, DR), "UkfModel: 4-byte members in declaration order, no padding");
-  std::memset(&e, 0, sizeof(e));
-  return fill_ukf_model_view(p, up, ukf_model_view_flat(reinterpret_cast<uint32_t*>(&e), N, DQ, M, DR), 0, tvsq, tvsr);
+// ---- launch preparation, shared by the compiled instances below and the kernels built at run time (ugsf_scan.hip, agsf_ukf.hip):
+// everything but the launch itself.  The model goes to the device as the flat words of a UkfModel<N, DQ, M, DR>.
+struct UkfLaunch {
+  const void* d_mdl;
+  const float *d_tvq, *d_tvr;   // per-step sqrtm(Q_t) / sqrtm(R_t) -- the covariances themselves under user_flags & 4 -- or NULL
+};
+static inline int prepare_ukf_model(const bf_model* p, const bf_ukf_params* up, int user_flags, long long T, hipStream_t stream, UkfLaunch& L) {
+  if ((p->Q_steps > 1 && p->Q_steps != T) || (p->R_steps > 1 && p->R_steps != T))
+    return set_error(BF_EINVAL, "time-varying covariances need one matrix per step (Q_steps / R_steps = T = %lld)", T);
+  std::vector<uint32_t> words(ukf_model_words(p->n, p->dq, p->m, p->dr), 0u);   // zeroed: the constant cache compares contents
+  std::vector<float> tvq, tvr;
+  const bf_ukf_params unit{1.f, 0.f, 0.f};  // (the extended-Kalman operations ignore the unscented constants)
+  int rc = fill_ukf_model_view(p, up ? up : &unit, ukf_model_view_flat(words.data(), p->n, p->dq, p->m, p->dr), user_flags, &tvq, &tvr);
+  if (rc != BF_OK) return rc;
+  if ((rc = device_constants(words.data(), sizeof(uint32_t) * words.size(), stream, &L.d_mdl)) != BF_OK) return rc;
+  if ((rc = upload_table(tvq, stream, &L.d_tvq)) != BF_OK || (rc = upload_table(tvr, stream, &L.d_tvr)) != BF_OK) return rc;
+  return BF_OK;
+}
+
+struct UgsfLaunch : UkfLaunch {
+  CView y;
+  const float* uptr;
+  long long u_sB, u_sT;
+  CarryView carry;
+  OutViews out;
+  int KP;
+  unsigned grid;   // workgroups of 256 lanes, a lane per (trajectory, component)
+};
+static inline int prepare_ugsf(const bf_model* p, const bf_ukf_params* up, int user_flags, const bf_cstream* y, const bf_cstream* u, long long B,
+                               long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, UgsfLaunch& L) {
+  L.KP = 1;
+  while (L.KP < K) L.KP <<= 1;
+  if (L.KP > 256) return set_error(BF_EUNSUPPORTED, "unscented Gaussian-sum filter: %d components exceed one workgroup (256 lanes)", K);
+  if (out->coll_mean.ptr || out->coll_cov.ptr)
+    return set_error(BF_EUNSUPPORTED, "collapsed streams are produced by bf_gsf_ekf_f32 only");
+  const int rc = prepare_ukf_model(p, up, user_flags, T, stream, L);
+  if (rc != BF_OK) return rc;
+  L.y = CView{y->ptr, y->sB, y->sT, y->sE};
+  L.uptr = (u && u->ptr) ? u->ptr : nullptr;
+  L.u_sB = u ? u->sB : 0;
+  L.u_sT = u ? u->sT : 0;
+  L.carry = CarryView{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
+  L.out = OutViews{make_sview(out->weights), make_sview(out->means), make_sview(out->covs),
+                   make_sview(out->pred_means), make_sview(out->pred_covs), make_sview(out->loglik)};
+  const int tpb = 256 / L.KP;
+  L.grid = (unsigned)((B + tpb - 1) / tpb);
+  return BF_OK;
 }
 
 template <int N, int DQ, int M, int DR>
 static inline int launch_ugsf(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
                               long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
-  UkfModel<N, DQ, M, DR> h;
-  std::memset(&h, 0, sizeof(h));  // the constant cache compares contents
-  std::vector<float> tvsq, tvsr;
-  int rc = fill_ukf_model<N, DQ, M, DR>(p, up, h, &tvsq, &tvsr);
+  static_assert(sizeof(UkfModel<N, DQ, M, DR>) == 4 * ukf_model_words(N, DQ, M, DR), "UkfModel: 4-byte members in declaration order, no padding");
+  UgsfLaunch L;
+  const int rc = prepare_ugsf(p, up, 0, y, u, B, T, K, carry, out, stream, L);
   if (rc != BF_OK) return rc;
-  if ((p->Q_steps > 1 && p->Q_steps != T) || (p->R_steps > 1 && p->R_steps != T))
-    return set_error(BF_EINVAL, "time-varying covariances need one matrix per step (Q_steps / R_steps = T = %lld)", T);
-  int KP = 1;
-  while (KP < K) KP <<= 1;
-  if (KP > 256) return set_error(BF_EUNSUPPORTED, "unscented Gaussian-sum filter: %d components exceed one workgroup (256 lanes)", K);
-  if (out->coll_mean.ptr || out->coll_cov.ptr)
-    return set_error(BF_EUNSUPPORTED, "collapsed streams are produced by bf_gsf_ekf_f32 only");
-  const void* dv = nullptr;
-  rc = device_constants(&h, sizeof(h), stream, &dv);
-  if (rc != BF_OK) return rc;
-  const UkfModel<N, DQ, M, DR>* d_mdl = static_cast<const UkfModel<N, DQ, M, DR>*>(dv);
-  const float *d_tvsq = nullptr, *d_tvsr = nullptr;
-  if ((rc = upload_table(tvsq, stream, &d_tvsq)) != BF_OK || (rc = upload_table(tvsr, stream, &d_tvsr)) != BF_OK) return rc;
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  CarryView cv{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
-  OutViews ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs),
-              make_sview(out->pred_means), make_sview(out->pred_covs), make_sview(out->loglik)};
-  const int tpb = 256 / KP;
-  hipLaunchKernelGGL((ugsf_scan_kernel<N, DQ, M, DR>), dim3((unsigned)((B + tpb - 1) / tpb)), dim3(256), 0, stream, d_mdl, yv,
-                     (u && u->ptr) ? u->ptr : nullptr, u ? u->sB : 0, u ? u->sT : 0, cv, ov, B, T, K, KP, d_tvsq, d_tvsr);
+  hipLaunchKernelGGL((ugsf_scan_kernel<N, DQ, M, DR>), dim3(L.grid), dim3(256), 0, stream, static_cast<const UkfModel<N, DQ, M, DR>*>(L.d_mdl),
+                     L.y, L.uptr, L.u_sB, L.u_sT, L.carry, L.out, B, T, K, L.KP, L.d_tvq, L.d_tvr);
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;
 }

@@ -9,18 +9,14 @@ os.chdir(root)
 def text(name):
     t = open(name).read().replace("#pragma once", "").replace("#include <hip/hip_runtime.h>", "")
     return re.sub(r'^#include "[^"]+".*$', "", t, flags=re.M)
-um = open("user_model.hip").read()
+um = open("jit_source.hip").read()
 consts = dict(re.findall(r'const char\* const (\w+) = R"BFSRC\((.*?)\)BFSRC";', um, flags=re.S))
 hw = (sys.argv[1] if len(sys.argv) > 1 else "1") == "1"
 fixed = (sys.argv[2] if len(sys.argv) > 2 else "1") == "1"
 n, dq, m, ppt, nw = 16, 16, 8, 4, 16
 s = "#define BF_JIT 1\n#include <cstdint>\n#include <type_traits>\n" + ("#define BF_BPF_HW_ARITH 1\n" if hw else "")
 s += "#define BF_N %d\n#define BF_DQ %d\n#define BF_M %d\n#define BF_DR %d\n" % (n, dq, m, m)
-s += """namespace bf { struct CView { const float* p; long long sB, sT, sE; };
-struct SView { float* p; long long sB, sK, sT, sE; };
-struct OutViews { SView w, m, P, pm, pP, ll; SView cm, cP; };
-struct CarryView { const float* w_in; const float* m_in; const float* P_in; float* w_out; float* m_out; float* P_out; }; }
-"""
+s += text("bf_views.hpp")
 s += text("kf_math.hpp") + text("bf_canon_math.hpp") + consts["kSamplingUserMath"] + "}  // namespace bfu\n"
 for h in ("scan_common.hpp", "bf_rng.hpp", "models.hpp", "ssm_device.hpp", "bpf_scan.hpp"):
     s += text(h)

@@ -1,7 +1,7 @@
 import re, sys, os
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from jit_try import compile_src
-root = "/root/repo/bayesianfiltering_amd/csrc/"
+root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bayesianfiltering_amd", "csrc") + "/"
 def hdr(name):
     t = open(root + name).read().replace("#pragma once", "")
     t = t.replace("#include <hip/hip_runtime.h>", "")
@@ -9,10 +9,7 @@ def hdr(name):
 PRELUDE = """#define BF_JIT 1
 #include <cstdint>
 #include <type_traits>
-namespace bf {
-struct CView { const float* p; long long sB, sT, sE; };
-}
-"""
+""" + hdr("bf_views.hpp")
 BFU = """
 namespace bfu {
 #pragma clang fp contract(off)
