@@ -91,6 +91,142 @@ __device__ __forceinline__ void transpose_lds(float* D, int ldd, const float* S,
   }
 }
 
+// X <- a^-1 X for a [m x m] (pitch ldm) and X [m x n] (pitch ldn), both in LDS: the psd_solve of utils.py:256-259 as getrf with
+// partial pivoting (LAPACK's order: row swaps, multipliers left in place; a is overwritten by its factors, srd / sperm take the
+// reciprocal pivots and the swaps) ...
+template <int NT>
+__device__ __forceinline__ void lu_solve_lds(float* sa, int ldm, float* sX, int ldn, float* srd, int* sperm, int m, int n, int tid) {
+#pragma clang fp contract(off)
+  for (int kk = 0; kk < m; ++kk) {
+    int pv = kk;
+    float best = fabsf(sa[kk * ldm + kk]);
+    for (int i = kk + 1; i < m; ++i) {  // every lane scans the column (broadcast reads): no hand-off needed
+      const float val = fabsf(sa[i * ldm + kk]);
+      if (val > best) { best = val; pv = i; }
+    }
+    if (tid == 0) sperm[kk] = pv;
+    if (pv != kk) {
+      gsync<NT>();
+      for (int j = tid; j < m; j += NT) {
+        const float a0 = sa[kk * ldm + j], a1 = sa[pv * ldm + j];
+        sa[kk * ldm + j] = a1;
+        sa[pv * ldm + j] = a0;
+      }
+    }
+    gsync<NT>();
+    const float rpiv = fast_rcp(sa[kk * ldm + kk]);
+    if (tid == 0) srd[kk] = rpiv;
+    const int rem = m - 1 - kk;
+    for (int e = tid; e < rem * rem; e += NT) {
+      const int i = kk + 1 + e / rem, j = kk + 1 + e % rem;
+      const float l = sa[i * ldm + kk] * rpiv;
+      sa[i * ldm + j] = fmaf(-l, sa[kk * ldm + j], sa[i * ldm + j]);
+    }
+    gsync<NT>();
+  }
+  // ... and getrs, one right-hand side (column of H P) per lane
+  for (int c = tid; c < n; c += NT) {
+    for (int kk = 0; kk < m; ++kk) {
+      const int pv = sperm[kk];
+      if (pv != kk) {
+        const float x0 = sX[kk * ldn + c], x1 = sX[pv * ldn + c];
+        sX[kk * ldn + c] = x1;
+        sX[pv * ldn + c] = x0;
+      }
+    }
+    for (int kk = 0; kk < m; ++kk) {
+      const float xk = sX[kk * ldn + c], rp = srd[kk];
+      for (int i = kk + 1; i < m; ++i) sX[i * ldn + c] = fmaf(-(sa[i * ldm + kk] * rp), xk, sX[i * ldn + c]);
+    }
+    for (int i = m - 1; i >= 0; --i) {
+      float s = sX[i * ldn + c];
+      for (int q = i + 1; q < m; ++q) s = fmaf(-sa[i * ldm + q], sX[q * ldn + c], s);
+      sX[i * ldn + c] = s * srd[i];
+    }
+  }
+  gsync<NT>();
+}
+
+// log N(v; 0, S) through chol(S) -> sL (left-looking, row per lane); sr takes the forward-substitution residual.  The value is
+// returned on lane 0 (0 elsewhere).
+template <int NT>
+__device__ __forceinline__ float chol_logpdf_lds(const float* sS, float* sL, int ldm, const float* sv, float* sr, int m, int tid) {
+#pragma clang fp contract(off)
+  for (int j = 0; j < m; ++j) {
+    float d = sS[j * ldm + j];
+    for (int q = 0; q < j; ++q) d = fmaf(-sL[j * ldm + q], sL[j * ldm + q], d);
+    d = fast_sqrt(d);
+    const float inv = fast_rcp(d);
+    for (int i = j + tid; i < m; i += NT) {
+      if (i == j) {
+        sL[j * ldm + j] = d;
+      } else {
+        float s = sS[i * ldm + j];
+        for (int q = 0; q < j; ++q) s = fmaf(-sL[i * ldm + q], sL[j * ldm + q], s);
+        sL[i * ldm + j] = s * inv;
+      }
+    }
+    gsync<NT>();
+  }
+  for (int a = tid; a < m; a += NT) sr[a] = sv[a];
+  gsync<NT>();
+  for (int j = 0; j < m; ++j) {
+    const float zj = sr[j] * fast_rcp(sL[j * ldm + j]);
+    gsync<NT>();
+    for (int i = j + tid; i < m; i += NT) {
+      if (i == j) sr[j] = zj;
+      else sr[i] = fmaf(-sL[i * ldm + j], zj, sr[i]);
+    }
+    gsync<NT>();
+  }
+  float ll = 0.f;
+  if (tid == 0) {
+    float quad = 0.f, logdet = 0.f;
+    for (int i = 0; i < m; ++i) {
+      quad = fmaf(sr[i], sr[i], quad);
+      logdet += fast_log(sL[i * ldm + i]);
+    }
+    ll = -0.5f * quad - 0.5f * (float)m * 1.8378770664093453f - logdet;
+  }
+  return ll;
+}
+
+// The weight update of inference.py:347-350 over all K components of a trajectory: lls -= max; w = exp(lls) * w; w /= sum(w),
+// max and sum as adjacent-pair trees over KP = K rounded up to a power of two (stree: KP floats of scratch)
+template <int NT>
+__device__ __forceinline__ void reweight_lds(const float* sll, float* sw, float* stree, int K, int KP, SView ow, long long b, long long t, int tid) {
+#pragma clang fp contract(off)
+  for (int k = tid; k < KP; k += NT) stree[k] = (k < K) ? sll[k] : -__builtin_inff();
+  gsync<NT>();
+  for (int s = 1; s < KP; s <<= 1) {
+    for (int k = tid * 2 * s; k + s < KP; k += NT * 2 * s) {
+      const float a = stree[k], c = stree[k + s];
+      stree[k] = (a != a || c != c) ? __builtin_nanf("") : fmaxf(a, c);  // jnp.max propagates NaN
+    }
+    gsync<NT>();
+  }
+  const float mx = stree[0];
+  gsync<NT>();
+  for (int k = tid; k < KP; k += NT) {
+    const float e = (k < K) ? expf(sll[k] - mx) * sw[k] : 0.f;
+    sw[k] = e;
+    stree[k] = e;
+  }
+  gsync<NT>();
+  for (int s = 1; s < KP; s <<= 1) {
+    for (int k = tid * 2 * s; k + s < KP; k += NT * 2 * s) stree[k] += stree[k + s];
+    gsync<NT>();
+  }
+  const float tot = stree[0];
+  gsync<NT>();
+  for (int k = tid; k < K; k += NT) {
+    const float wn = sw[k] / tot;
+    sw[k] = wn;
+    if (ow.p) ow.p[b * ow.sB + k * ow.sK + t * ow.sT] = wn;
+  }
+  gsync<NT>();
+}
+
 // f(x, q0, u), F_x at x -> LDS (F pitch ld).  Value and Jacobian formulas: csrc/models.hpp (same sources).
 template <int NT>
 __device__ void gen_dyn_linearize(const GenModel& p, const float* x, float u0, float* F, int ld, float* fx, int tid) {
@@ -430,55 +566,7 @@ __device__ __forceinline__ void gsf_generic_body(const GenModel& p, CView y, UVi
       gsync<NT>();
       for (int e = tid; e < m * m; e += NT) sa[(e / m) * ldm + (e % m)] = sS[(e / m) * ldm + (e % m)] + p.jitter;
       gsync<NT>();
-      // ---- psd_solve (utils.py:256-259): getrf with partial pivoting ...
-      for (int kk = 0; kk < m; ++kk) {
-        int pv = kk;
-        float best = fabsf(sa[kk * ldm + kk]);
-        for (int i = kk + 1; i < m; ++i) {  // every lane scans the column (broadcast reads): no hand-off needed
-          const float val = fabsf(sa[i * ldm + kk]);
-          if (val > best) { best = val; pv = i; }
-        }
-        if (tid == 0) sperm[kk] = pv;
-        if (pv != kk) {
-          gsync<NT>();
-          for (int j = tid; j < m; j += NT) {
-            const float a0 = sa[kk * ldm + j], a1 = sa[pv * ldm + j];
-            sa[kk * ldm + j] = a1;
-            sa[pv * ldm + j] = a0;
-          }
-        }
-        gsync<NT>();
-        const float rpiv = fast_rcp(sa[kk * ldm + kk]);
-        if (tid == 0) srd[kk] = rpiv;
-        const int rem = m - 1 - kk;
-        for (int e = tid; e < rem * rem; e += NT) {
-          const int i = kk + 1 + e / rem, j = kk + 1 + e % rem;
-          const float l = sa[i * ldm + kk] * rpiv;
-          sa[i * ldm + j] = fmaf(-l, sa[kk * ldm + j], sa[i * ldm + j]);
-        }
-        gsync<NT>();
-      }
-      // ... and getrs, one right-hand side (column of H P) per lane
-      for (int c = tid; c < n; c += NT) {
-        for (int kk = 0; kk < m; ++kk) {
-          const int pv = sperm[kk];
-          if (pv != kk) {
-            const float x0 = sX[kk * ldn + c], x1 = sX[pv * ldn + c];
-            sX[kk * ldn + c] = x1;
-            sX[pv * ldn + c] = x0;
-          }
-        }
-        for (int kk = 0; kk < m; ++kk) {
-          const float xk = sX[kk * ldn + c], rp = srd[kk];
-          for (int i = kk + 1; i < m; ++i) sX[i * ldn + c] = fmaf(-(sa[i * ldm + kk] * rp), xk, sX[i * ldn + c]);
-        }
-        for (int i = m - 1; i >= 0; --i) {
-          float s = sX[i * ldn + c];
-          for (int q = i + 1; q < m; ++q) s = fmaf(-sa[i * ldm + q], sX[q * ldn + c], s);
-          sX[i * ldn + c] = s * srd[i];
-        }
-      }
-      gsync<NT>();
+      lu_solve_lds<NT>(sa, ldm, sX, ldn, srd, sperm, m, n, tid);                       // psd_solve (utils.py:256-259)
       transpose_lds<NT>(sXT, ldm, sX, ldn, m, n, tid);                                 // K = X^T
       gsync<NT>();
       mm_lds<NT, 0>(sKS, ldm, sXT, ldm, sS, ldm, nullptr, 0, n, m, m, tid);            // K S (un-jittered S)
@@ -489,41 +577,8 @@ __device__ __forceinline__ void gsf_generic_body(const GenModel& p, CView y, UVi
       }
       gsync<NT>();
       mm_lds<NT, 2>(sP, ldn, sKS, ldm, sX, ldn, sP, ldn, n, m, n, tid);               // P+ = P - (K S) K^T
-      // ---- log N(y; h(m), S) through chol(S) (inference.py:104, :24), left-looking, row per lane
-      for (int j = 0; j < m; ++j) {
-        float d = sS[j * ldm + j];
-        for (int q = 0; q < j; ++q) d = fmaf(-sL[j * ldm + q], sL[j * ldm + q], d);
-        d = fast_sqrt(d);
-        const float inv = fast_rcp(d);
-        for (int i = j + tid; i < m; i += NT) {
-          if (i == j) {
-            sL[j * ldm + j] = d;
-          } else {
-            float s = sS[i * ldm + j];
-            for (int q = 0; q < j; ++q) s = fmaf(-sL[i * ldm + q], sL[j * ldm + q], s);
-            sL[i * ldm + j] = s * inv;
-          }
-        }
-        gsync<NT>();
-      }
-      for (int a = tid; a < m; a += NT) sr[a] = sv[a];
-      gsync<NT>();
-      for (int j = 0; j < m; ++j) {
-        const float zj = sr[j] * fast_rcp(sL[j * ldm + j]);
-        gsync<NT>();
-        for (int i = j + tid; i < m; i += NT) {
-          if (i == j) sr[j] = zj;
-          else sr[i] = fmaf(-sL[i * ldm + j], zj, sr[i]);
-        }
-        gsync<NT>();
-      }
+      const float ll = chol_logpdf_lds<NT>(sS, sL, ldm, sv, sr, m, tid);               // log N(y; h(m), S) (inference.py:104, :24)
       if (tid == 0) {
-        float quad = 0.f, logdet = 0.f;
-        for (int i = 0; i < m; ++i) {
-          quad = fmaf(sr[i], sr[i], quad);
-          logdet += fast_log(sL[i * ldm + i]);
-        }
-        const float ll = -0.5f * quad - 0.5f * (float)m * 1.8378770664093453f - logdet;
         sll[k] = ll;
         if (out.ll.p) out.ll.p[b * out.ll.sB + k * out.ll.sK + t * out.ll.sT] = ll;
       }
@@ -561,36 +616,7 @@ __device__ __forceinline__ void gsf_generic_body(const GenModel& p, CView y, UVi
         __syncthreads();  // global + LDS: the next component reuses the tile, the next step reads this component back
       }
     }
-    // ================= reweight (inference.py:347-350): lls -= max; w = exp(lls) * w; w /= sum(w), adjacent-pair trees
-    for (int k = tid; k < KP; k += NT) stree[k] = (k < K) ? sll[k] : -__builtin_inff();
-    gsync<NT>();
-    for (int s = 1; s < KP; s <<= 1) {
-      for (int k = tid * 2 * s; k + s < KP; k += NT * 2 * s) {
-        const float a = stree[k], c = stree[k + s];
-        stree[k] = (a != a || c != c) ? __builtin_nanf("") : fmaxf(a, c);  // jnp.max propagates NaN
-      }
-      gsync<NT>();
-    }
-    const float mx = stree[0];
-    gsync<NT>();
-    for (int k = tid; k < KP; k += NT) {
-      const float e = (k < K) ? expf(sll[k] - mx) * sw[k] : 0.f;
-      sw[k] = e;
-      stree[k] = e;
-    }
-    gsync<NT>();
-    for (int s = 1; s < KP; s <<= 1) {
-      for (int k = tid * 2 * s; k + s < KP; k += NT * 2 * s) stree[k] += stree[k + s];
-      gsync<NT>();
-    }
-    const float tot = stree[0];
-    gsync<NT>();
-    for (int k = tid; k < K; k += NT) {
-      const float wn = sw[k] / tot;
-      sw[k] = wn;
-      if (out.w.p) out.w.p[b * out.w.sB + k * out.w.sK + t * out.w.sT] = wn;
-    }
-    gsync<NT>();
+    reweight_lds<NT>(sll, sw, stree, K, KP, out.w, b, t, tid);   // (inference.py:347-350)
   }
 
   // ---- carry out

@@ -9,6 +9,7 @@ namespace bf {
 
 extern const char* const kViewsSource;          // bf_views.hpp, embedded at build time (jit_sources.hip)
 extern const char* const kGenericDeviceSource;  // generic_device.hpp
+extern const char* const kUgsfGenericSource;    // ugsf_generic_device.hpp
 extern const char* const kSamplingSourceA;      // kf_math.hpp + bf_canon_math.hpp
 extern const char* const kSamplingSourceB;      // scan_common / bf_rng / models / ssm_device / bpf_scan
 extern const char* const kAgsfSource;           // agsf_geom.hpp + agsf_scan.hpp
@@ -87,8 +88,10 @@ __device__ inline Dual fma(float a, Dual b, Dual c) { return a * b + c; }
 __device__ inline Dual fma(Dual a, float b, Dual c) { return a * b + c; }
 )BFSRC";
 
-// The run-time-dimension Gaussian-sum scan (generic_device.hpp) with dual-number Jacobians: libm's float functions
-std::string generic_scan_source(const bf_user_model& um) {
+// The run-time-dimension Gaussian-sum scan (generic_device.hpp) with dual-number Jacobians: libm's float functions.
+// nt_ugsf = 0: its two entry points; 64 / 256: the run-time-dimension unscented scan (ugsf_generic_device.hpp) instead, on the
+// same headers and the same float functions -- values of f and h only, no Jacobians.
+std::string generic_scan_source(const bf_user_model& um, int nt_ugsf) {
   std::string s;
   s += "#define BF_JIT 1\n";
   if (um.has_dyn) s += "#define BF_USER_DYN 1\n";
@@ -105,6 +108,14 @@ std::string generic_scan_source(const bf_user_model& um) {
   s += "}  // namespace bfu\n";
   s += kViewsSource;
   s += kGenericDeviceSource;
+  if (nt_ugsf != 0) {
+    const std::string nt = std::to_string(nt_ugsf);
+    s += kUgsfGenericSource;
+    s += "extern \"C\" __global__ void __launch_bounds__(" + nt + ") bf_user_ugsf_generic(bf::UgModel p, bf::CView y, bf::UViewG u, bf::CarryView carry,\n"
+         "    bf::OutViews out, float* gm, float* gP, long long B, long long T, int K, int KP) {\n"
+         "  bf::ugsf_generic_body<" + nt + ">(p, y, u, carry, out, gm, gP, B, T, K, KP);\n}\n";
+    return s;
+  }
   s += R"BFSRC(
 extern "C" __global__ void __launch_bounds__(64) bf_user_scan_64(bf::GenModel p, bf::CView y, bf::UViewG u, bf::CarryView carry,
     bf::OutViews out, float* gm, float* gP, long long B, long long T, int K, int KP) {
@@ -150,12 +161,14 @@ const char* jit_entry_name(int kind) {
     case JIT_GSF_REGS: return "bf_user_gsf_regs";
     case JIT_SAMPLE: return "bf_user_sample";
     case JIT_BPF_BIG: return "bf_user_bpf_big";
+    case JIT_UGSF_GENERIC: return "bf_user_ugsf_generic";
     default: return "bf_user_scan_64";
   }
 }
 
 std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int spec_id) {
-  if (kind == JIT_GSF_GENERIC) return generic_scan_source(um);
+  if (kind == JIT_GSF_GENERIC) return generic_scan_source(um, 0);
+  if (kind == JIT_UGSF_GENERIC) return generic_scan_source(um, 64 * nw);   // nw = 1: one wave per trajectory, 4: four
   std::string s = "#define BF_JIT 1\n#include <cstdint>\n#include <type_traits>\n";
   if (um.hw_arith) s += "#define BF_BPF_HW_ARITH 1\n";
   if (um.has_dyn) s += "#define BF_USER_DYN 1\n";

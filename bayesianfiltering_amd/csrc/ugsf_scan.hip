@@ -1,9 +1,12 @@
 // Instances and dispatch of the unscented Gaussian-sum filter kernel (ugsf_scan.hpp) over the compiled
-// (n, dq, m, dr) table, and the launches of the same kernel built at run time (user_model.hpp).
+// (n, dq, m, dr) table, and the launches of the same kernel built at run time (user_model.hpp).  Any dimension above 8 -- or
+// bf_set_option "ugsf_force_generic" = 1 -- goes to the run-time-dimension kernel instead (ugsf_generic.hip).
 #include "ugsf_scan.hpp"
 #include "user_model.hpp"
 
 namespace bf {
+
+extern Option g_ugsf_force_generic;   // ugsf_generic.hip
 
 // ugsf_scan_body built around the handle's functions: `kind` JIT_UGSF (sigma points through f and h) or JIT_GSF_REGS
 // (extended-Kalman operations, Jacobians by dual numbers; user_flags bit 2: the covariances themselves, not their roots)
@@ -21,15 +24,15 @@ static int launch_ugsf_jit(int kind, const bf_model* p, const bf_ukf_params* up,
   return BF_OK;
 }
 
-// The unscented Gaussian-sum scan with the caller's functions: state in registers, so the state dimension is bounded like the
-// compiled instances' (n <= 8)
+// The unscented Gaussian-sum scan with the caller's functions: state in registers up to dimension 8 (like the compiled
+// instances), in LDS above (ugsf_generic.hip)
 static int launch_ugsf_user_impl(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
                                  int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
   const int rc = check_user_model(p->user, p);
   if (rc != BF_OK) return rc;
   if (p->user->has_lp) return set_error(BF_EINVAL, "a log-density from source belongs to the particle filter, not to the unscented filter");
-  if (p->n > 8 || p->dq > 8 || p->m > 8 || p->dr > 8)
-    return set_error(BF_EUNSUPPORTED, "unscented filter with functions from source: dimensions up to 8 (the sigma points live in registers)");
+  if (p->n > 8 || p->dq > 8 || p->m > 8 || p->dr > 8 || g_ugsf_force_generic.load() != 0)
+    return launch_ugsf_generic(p, up, y, u, B, T, K, carry, out, stream);
   return launch_ugsf_jit(JIT_UGSF, p, up, y, u, B, T, K, carry, out, stream);
 }
 
@@ -59,6 +62,8 @@ int launch_ugsf_ukf(const bf_model* p, const bf_ukf_params* up, const bf_cstream
     return launch_ugsf_user_impl(p, up, y, u, B, T, K, carry, out, stream);
   if (p->dyn_id == BF_FN_USER || p->emi_id == BF_FN_USER)
     return set_error(BF_EINVAL, "dyn_id / emi_id = BF_FN_USER needs bf_model.user (bf_user_model_create)");
+  if (p->n > 8 || p->dq > 8 || p->m > 8 || p->dr > 8 || g_ugsf_force_generic.load() != 0)   // beyond the registers: state in LDS, ahead-of-time instance
+    return launch_ugsf_generic(p, up, y, u, B, T, K, carry, out, stream);
 #define BF_CASE(N_, DQ_, M_, DR_)                                                      \
   if (p->n == N_ && p->dq == DQ_ && p->m == M_ && p->dr == DR_)                        \
     return launch_ugsf<N_, DQ_, M_, DR_>(p, up, y, u, B, T, K, carry, out, stream);

@@ -40,10 +40,10 @@ int check_user_device(const bf_user_model* um) {   // a module is loaded on ONE 
   return BF_OK;
 }
 
-int launch_user_kernel(const bf_user_model* um, int nt, unsigned grid, size_t lds_bytes, hipStream_t stream, void** args) {
+int launch_user_kernel(const bf_user_model* um, int nt, unsigned grid, size_t lds_bytes, hipStream_t stream, void** args, hipFunction_t fn) {
   const int rc = check_user_device(um);
   if (rc != BF_OK) return rc;
-  hipFunction_t f = nt == 64 ? um->k64 : um->k256;
+  hipFunction_t f = fn ? fn : (nt == 64 ? um->k64 : um->k256);
   // (a module function needs no opt-in for more than 64 KiB of dynamic LDS on gfx950: the launch itself checks the 160 KiB limit)
   BF_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, (unsigned)nt, 1, 1, (unsigned)lds_bytes, stream, args, nullptr));
   return BF_OK;

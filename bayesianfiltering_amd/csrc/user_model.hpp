@@ -9,7 +9,7 @@
 #include "bf_common.hpp"
 
 // kernels compiled at run time around the caller's functions -- or around the registry's, for dimensions without a compiled instance
-enum bf_jit_kind { JIT_GSF_GENERIC, JIT_BPF, JIT_UGSF, JIT_AGSF_UKF, JIT_AGSF_EKF, JIT_GSF_REGS, JIT_SAMPLE, JIT_BPF_BIG };
+enum bf_jit_kind { JIT_GSF_GENERIC, JIT_BPF, JIT_UGSF, JIT_AGSF_UKF, JIT_AGSF_EKF, JIT_GSF_REGS, JIT_SAMPLE, JIT_BPF_BIG, JIT_UGSF_GENERIC };
 // the model structure a sampling kernel is compiled for: the handle's own functions, or (registry models) bpf_scan.hpp's specs
 enum bf_jit_spec { JIT_SPEC_USER = 0, JIT_SPEC_RUNTIME = 1, JIT_SPEC_L96_PICK = 2 };
 
@@ -42,9 +42,13 @@ int check_user_device(const bf_user_model* um);                     // ... and o
 const bf_user_model* registry_jit_handle(const bf_model* p, bool hw_arith);
 // the handle's kernel of this kind, built under the lock on first use (checks the device)
 int user_kernel(const bf_user_model* um, int kind, int ppt, int nw, int spec, hipFunction_t* fn);
-int launch_user_kernel(const bf_user_model* um, int nt, unsigned grid, size_t lds_bytes, hipStream_t stream, void** args);
+// launches the handle's run-time-dimension Gaussian-sum scan, or `fn` (another kernel of the handle with dynamic LDS) when given
+int launch_user_kernel(const bf_user_model* um, int nt, unsigned grid, size_t lds_bytes, hipStream_t stream, void** args,
+                       hipFunction_t fn = nullptr);
 
 // ---- launches of the kernels built at run time, next to their compiled twins
+int launch_ugsf_generic(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
+                        const bf_carry* carry, const bf_out_desc* out, hipStream_t stream);   // ugsf_generic.hip: registry or from source, any dimensions
 bool gsf_user_regs_eligible(const bf_model* p, int K, const bf_out_desc* out);   // ugsf_scan.hip
 int launch_gsf_user_regs_impl(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K, const bf_carry* carry,
                               const bf_out_desc* out, hipStream_t stream);

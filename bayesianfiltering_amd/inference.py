@@ -452,7 +452,7 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
 def unscented_gaussian_sum_filter(params, uparams, emissions, num_components: int = 1, num_iter: int = 1, inputs=None, *,
                                   initial_means=None, initial_covariances=None, carry=None,
                                   fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
-                                  return_loglik: bool = False, return_carry: bool = False, device="cuda"):
+                                  return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None):
     """Unscented Gaussian-sum filter (bank of K unscented Kalman filters with non-additive noise +
     weight update), gaussfiltax/inference.py:379-456, on the HIP engine.
 
@@ -460,12 +460,17 @@ def unscented_gaussian_sum_filter(params, uparams, emissions, num_components: in
     there).  Sigma points follow ``utils._get_sigma_points`` (utils.py:247-254): the symmetric square root
     of blockdiag(P, noise covariance), recomputed on the device twice per step.  Shapes, ``initial_means``,
     ``carry`` / ``return_carry``, ``fields`` and ``return_loglik`` as in :func:`gaussian_sum_filter`.
+
+    State, noise and observation dimensions up to 8 run with the state in registers (at most 256 components); anything larger
+    runs on the run-time-dimension kernel (state in LDS, any number of components, bounded by 160 KiB of LDS: about n = 70 with
+    n / 2 observations).  ``options={"ugsf_force_generic": 1}`` sends a small model through that kernel too.
     """
     if not isinstance(uparams, ParamsUKF):
         uparams = ParamsUKF(*uparams)
     return gaussian_sum_filter(params, emissions, num_components, num_iter, inputs, initial_means=initial_means,
                                initial_covariances=initial_covariances, carry=carry, fields=fields, layout=layout, out=out,
-                               return_loglik=return_loglik, return_carry=return_carry, device=device, _uparams=uparams)
+                               return_loglik=return_loglik, return_carry=return_carry, device=device, options=options,
+                               _uparams=uparams)
 
 
 def speedy_augmented_gaussian_sum_filter(params, emissions, num_components, rng_key=None, num_iter: int = 1,

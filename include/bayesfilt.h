@@ -211,7 +211,7 @@ int bf_user_model_create(const char* dynamics_src, const char* emission_src, int
  * the same handle also compiles the particle-filter kernel with the caller's functions, on first use and per particle
  * capacity (particles in registers up to 4096 for state_dim <= 16 / 1024 beyond; above that the particles-in-HBM kernel, up to
  * 2^20 per trajectory) -- and, likewise on first use, the unscented (bf_ugsf_ukf_f32) and augmented (bf_agsf_ekf_f32 /
- * bf_agsf_ukf_f32) scans and the data generator (bf_sample_ssm_f32) around the same functions (dimensions up to 8; sampler 32).  The density is either Gaussian around the (registry or
+ * bf_agsf_ukf_f32) scans and the data generator (bf_sample_ssm_f32) around the same functions (augmented scans: dimensions up to 8; sampler 32).  The density is either Gaussian around the (registry or
  * source) emission function, MVN(h(x, r_eval, u), lp_cov) as for registry models, or -- log_prob_src -- the caller's own
  *
  *     template <class T> __device__ T log_prob(const T* x, const float* y, T u, const float* theta);   // theta = bf_bpf_model.lp_theta
@@ -249,7 +249,10 @@ int bf_gsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream*
  * unscented_gaussian_sum_filter (inference.py:379-456) with _ukf_condition_on_nonadditive
  * (:198-224), the reweight (:424-427) and _ukf_predict_nonadditive (:146-174); sigma points as
  * utils._get_sigma_points (utils.py:247-254) with the symmetric matrix square root computed on the
- * device.  Arguments as bf_gsf_ekf_f32; constant covariances, out->coll_* unsupported. */
+ * device.  Arguments as bf_gsf_ekf_f32; constant or per-step (T, d, d) covariances; out->coll_* unsupported.  Every dimension
+ * <= 8: state in registers, K <= 256.  Any of n, dq, m, dr above 8 (or option "ugsf_force_generic" = 1): state in LDS, any K,
+ * registry functions linear / Lorenz-96 / sine and linear / quadratic / stochastic volatility or functions from source;
+ * BF_EUNSUPPORTED with the byte count when a workgroup's 160 KiB of LDS do not hold the model (n = 68 with n / 2 observations fits). */
 int bf_ugsf_ukf_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* y, const bf_cstream* u,
                     int64_t B, int64_t T, int32_t K, const bf_carry* carry, const bf_out_desc* out, void* stream);
 
