@@ -50,6 +50,14 @@ class bf_smooth_carry(C.Structure):
     _fields_ = [("m_in", C.c_void_p), ("P_in", C.c_void_p), ("m_out", C.c_void_p), ("P_out", C.c_void_p)]
 
 
+class bf_sample_desc(C.Structure):
+    _fields_ = [("samples", bf_stream), ("noise", bf_cstream), ("keys", C.c_void_p)]
+
+
+class bf_sample_carry(C.Structure):
+    _fields_ = [("x_in", C.c_void_p), ("x_out", C.c_void_p)]
+
+
 class bf_lgssm(C.Structure):
     _fields_ = [("n", C.c_int32), ("dq", C.c_int32), ("m", C.c_int32), ("dr", C.c_int32),
                 ("A", _FP), ("G", _FP), ("H", _FP), ("D", _FP), ("q0", _FP), ("r0", _FP), ("Q", _FP), ("R", _FP),
@@ -131,6 +139,12 @@ SYMBOLS = {
                                       C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p]),
     "bf_eks_smoother_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_out_desc), C.c_int64,
                                       C.c_int64, C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p]),
+    "bf_sampler_abi_check": (C.c_int, [C.c_size_t, C.c_size_t]),
+    "bf_ffbs_sample_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.c_int32,
+                                     C.POINTER(bf_sample_carry), C.POINTER(bf_sample_desc), C.c_void_p]),
+    "bf_effbs_sample_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_out_desc), C.c_int64,
+                                      C.c_int64, C.c_int32, C.POINTER(bf_sample_carry), C.POINTER(bf_sample_desc),
+                                      C.c_void_p]),
 }
 
 _lib = None
@@ -159,6 +173,8 @@ def load():
                         C.sizeof(bf_bpf_out)) != BF_OK:
         raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
     if lib.bf_smoother_abi_check(C.sizeof(bf_smooth_desc), C.sizeof(bf_smooth_carry)) != BF_OK:
+        raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
+    if lib.bf_sampler_abi_check(C.sizeof(bf_sample_desc), C.sizeof(bf_sample_carry)) != BF_OK:
         raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
     _lib = lib
     return lib

@@ -98,6 +98,8 @@ __global__ void canon_eval_kernel(int op, const float* __restrict__ in, long lon
 Option& rts_load_mode_option();  // rts_smoother.hip: -1 = from the layout, 0 = strided, 2 = LDS-staged
 static Option g_kf_small_mode{1, OPT_KF_SMALL_MODE};   // bf_set_option "kf_small_mode": 1 = one-wave matrix-core kernel for 9 <= n <= 32 (default), 0 = off
 static Option g_force_generic{0, OPT_FORCE_GENERIC};  // 1 = run the run-time-dimension kernel even where a compiled instance exists
+Option& force_generic_option() { return g_force_generic; }  // read by the samplers' entry points (ffbs_sampler.hip)
+Option& ffbs_spl_option();  // ffbs_sampler.hip: 0 = from S and n, else samples per lane of the register kernel
 
 // A shape / option the compiled instances do not cover falls through to the run-time-dimension kernel
 // (generic_scan.hip); if that cannot run it either, both reasons are reported.
@@ -192,6 +194,10 @@ static int set_option_impl(const char* name, int value, bool this_call_only) {
   if (name && std::strcmp(name, "rts_load_mode") == 0) {
     if (value != -1 && value != 0 && value != 2) return bf::set_error(BF_EINVAL, "rts_load_mode must be -1, 0 or 2");
     return assign(bf::rts_load_mode_option());
+  }
+  if (name && std::strcmp(name, "ffbs_spl") == 0) {
+    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return bf::set_error(BF_EINVAL, "ffbs_spl must be 0, 1, 2, 4 or 8");
+    return assign(bf::ffbs_spl_option());
   }
   if (name && std::strcmp(name, "gsf_structured") == 0) {
     if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "gsf_structured must be 0 or 1");

@@ -1,0 +1,381 @@
+// Host side of the posterior sampler (ffbs_sampler.hpp): the two C entry points, the register instances for n <= 8 and
+// the run-time-dimension kernel for every other n (one wave per trajectory, matrices and a block of samples in LDS).
+//
+// Register instances (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): every instance, n = 1 ... 8, SPL = 1, 2, 4, 8 samples
+// per lane, all three dynamics kinds, builds without scratch.  VGPRs (arch + acc) / waves per SIMD, range over the kinds:
+//   n    SPL = 1         SPL = 2         SPL = 4         SPL = 8
+//   1    61-83 / 5-8     89-113 / 4-5    133-157 / 3     95-114 / 4-5
+//   2    53-78 / 6-8     86-104 / 4-5    79-100 / 4-6    111-132 / 3-4
+//   3    70-99 / 4-7     108-133 / 3-4   102-125 / 4     142-165 / 3
+//   4    108-155 / 3-4   117-155 / 3-4   141-180 / 2-3   189-228 / 2
+//   5    146-193 / 2-3   147-186 / 2-3   184-214 / 2     240-268 / 1-2
+//   6    173-193 / 2     182-233 / 2     223-261 / 1-2   286-322 / 1
+//   7    218-266 / 1-2   225-280 / 1-2   266-308 / 1     334-370 / 1
+//   8    288-333 / 1     288-327 / 1     322-360 / 1     406-426 / 1
+// (above 256 the per-sample states and the step's matrices spill into the accumulation registers, not to memory).  The
+// run-time-dimension kernel: 116 VGPRs, 4 waves per SIMD.  "ffbs_spl" = 0 (default) picks the smallest compiled SPL that holds all S samples
+// of a trajectory in one lane, 8 for S > 8 (S = 5 runs SPL = 8 with three idle slots).  It rests on the one sweep of DESIGN.md
+// 6b (n = 4, B = 65 536, S = 8 and 64): SPL = 8 was the fastest there except in noise mode at S = 64.
+#include "ffbs_sampler.hpp"
+#include "rts_generic.hpp"
+
+namespace bf {
+
+// ---- run-time-dimension kernel -----------------------------------------------------------------------------------
+// One 64-lane workgroup per trajectory.  LDS: five n x ld matrices (P, P-, X, W, Sg), three vectors and three sample
+// buffers of SB x n (state x, noise xi, result).  Per step, with the smoother's helpers (rts_generic.hpp): W <- F_t,
+// X = F P, [recompute: P-, m-], W <- chol(P-), X <- L^-1 X, then Sg = P - X^T X (lower triangle), X <- L^-T X,
+// Sg <- psdchol(Sg; diag P) in place, then the samples in blocks of SB: lanes split over (sample, row) in
+// x = m + X^T (x+ - m-) + Sg xi.  With one block the state stays in LDS from step to step; with more, a block's x+ is read
+// back from the sample stream (each element by the lane that wrote it one step earlier).
+struct FfbsGen {
+  RtsGen r;
+  int S, SB;            // samples, samples per LDS block
+};
+
+static inline size_t ffbs_gen_mat_floats(int n) { return 5 * (size_t)n * rts_gen_ld(n) + 3 * (size_t)n; }
+
+__global__ void __launch_bounds__(64) ffbs_generic_kernel(FfbsGen fc, GenModel g, FfbsViews v, long long T) {
+  const RtsGen& c = fc.r;
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const int n = c.n, ld = rts_gen_ld(n), nn = n * n, S = fc.S, SB = fc.SB;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* P = lds;
+  float* Pp = P + n * ld;
+  float* X = Pp + n * ld;
+  float* W = X + n * ld;
+  float* Sg = W + n * ld;
+  float* m = Sg + n * ld;
+  float* mp = m + n;
+  float* tv = mp + n;
+  float* xs = tv + n;        // x_{t+1} of the block, then x_{t+1} - m-
+  float* xi = xs + SB * n;   // the block's noise
+  float* xo = xi + SB * n;   // x_t of the block
+  const bool one_block = SB >= S;
+  const bool keyed = v.xi.p == nullptr;
+  uint32_t k0 = 0, k1 = 0;
+  if (keyed) {
+    k0 = v.keys[2 * b];
+    k1 = v.keys[2 * b + 1];
+  }
+  const uint32_t count = (uint32_t)S * (uint32_t)T * (uint32_t)n;
+  auto at = [&](const SView& s, long long t, int e) { return b * s.sB + t * s.sT + e * s.sE; };
+  auto xat = [&](const SView& s, int smp, long long t, int e) { return b * s.sB + smp * s.sK + t * s.sT + e * s.sE; };
+
+  // the samples of step t in blocks: first = the chunk's last step without a carry (x = m + Sg xi)
+  auto samples = [&](long long t, bool first) {
+    for (int sb0 = 0; sb0 < S; sb0 += SB) {
+      const int ne = ((S - sb0) < SB ? (S - sb0) : SB) * n;
+      for (int e = tid; e < ne; e += 64) {
+        const int sl = e / n, i = e - sl * n, smp = sb0 + sl;
+        xi[e] = keyed ? bits_to_normal(threefry_bits(k0, k1, ((uint32_t)smp * (uint32_t)T + (uint32_t)t) * (uint32_t)n + i, count))
+                      : v.xi.p[xat(v.xi, smp, t, i)];
+        if (!first) {
+          float xn;
+          if (t == T - 1) xn = v.x_in[((long long)b * S + smp) * n + i];
+          else if (one_block) xn = xs[e];
+          else xn = v.x.p[xat(v.x, smp, t + 1, i)];
+          xs[e] = xn - mp[i];
+        }
+      }
+      wave_lds_sync();
+      for (int e = tid; e < ne; e += 64) {
+        const int sl = e / n, i = e - sl * n;
+        const float* z = xi + sl * n;
+        float s;
+        if (first) {
+          s = Sg[i * ld] * z[0];
+          for (int k = 1; k <= i; ++k) s = fmaf(Sg[i * ld + k], z[k], s);
+        } else {
+          const float* dx = xs + sl * n;
+          s = X[i] * dx[0];
+          for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], dx[k], s);
+          for (int k = 0; k <= i; ++k) s = fmaf(Sg[i * ld + k], z[k], s);
+        }
+        const float xv = m[i] + s;
+        xo[e] = xv;
+        v.x.p[xat(v.x, sb0 + sl, t, i)] = xv;
+        if (t == 0 && v.x_out) v.x_out[((long long)b * S + sb0 + sl) * n + i] = xv;
+      }
+      wave_lds_sync();
+      if (one_block) {
+        float* sw = xs;
+        xs = xo;
+        xo = sw;
+      }
+    }
+  };
+  // Sg (lower triangle) <- psdchol(Sg; diag P); every lane forms the pivot itself
+  auto psd_factor = [&]() {
+    for (int j = 0; j < n; ++j) {
+      float p = Sg[j * ld + j];
+      for (int k = 0; k < j; ++k) p = fmaf(-Sg[j * ld + k], Sg[j * ld + k], p);
+      const bool keep = p > BF_FFBS_TAU * P[j * ld + j];
+      const float r = keep ? fast_sqrt(p) : 0.f;
+      const float inv = keep ? fast_rcp(r) : 0.f;
+      for (int i = j + 1 + tid; i < n; i += 64) {
+        float s = Sg[i * ld + j];
+        for (int k = 0; k < j; ++k) s = fmaf(-Sg[i * ld + k], Sg[j * ld + k], s);
+        Sg[i * ld + j] = keep ? s * inv : 0.f;
+      }
+      wave_lds_sync();  // the pivot's reads of row j are done before its diagonal changes
+      if (tid == 0) Sg[j * ld + j] = r;
+      wave_lds_sync();
+    }
+  };
+
+  long long t = T - 1;
+  if (!v.x_in) {
+    for (int e = tid; e < n; e += 64) m[e] = v.m.p[at(v.m, t, e)];
+    for (int e = tid; e < nn; e += 64) {
+      const float x = v.P.p[at(v.P, t, e)];
+      P[(e / n) * ld + e % n] = x;
+      Sg[(e / n) * ld + e % n] = x;
+    }
+    wave_lds_sync();
+    psd_factor();
+    samples(t, true);
+    --t;
+  }
+  for (; t >= 0; --t) {
+    for (int e = tid; e < n; e += 64) m[e] = v.m.p[at(v.m, t, e)];
+    for (int e = tid; e < nn; e += 64) P[(e / n) * ld + e % n] = v.P.p[at(v.P, t, e)];
+    if (c.kind != RTS_LIN_RECOMPUTE) {
+      for (int e = tid; e < n; e += 64) mp[e] = v.pm.p[at(v.pm, t, e)];
+      for (int e = tid; e < nn; e += 64) Pp[(e / n) * ld + e % n] = v.pP.p[at(v.pP, t, e)];
+    }
+    wave_lds_sync();
+    const float u0 = (c.kind == RTS_EXT && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+    rts_gen_linearize(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid);
+    rts_gen_chol(n, Pp, W, tid);
+    rts_gen_solve_lower(n, W, X, tid);  // X <- L^-1 X
+    wave_lds_sync();
+    for (int e = tid; e < nn; e += 64) {  // Sg = P - X^T X, lower triangle
+      const int i = e / n, j = e - i * n;
+      if (j > i) continue;
+      float s = P[i * ld + j];
+      for (int k = 0; k < n; ++k) s = fmaf(-X[k * ld + i], X[k * ld + j], s);
+      Sg[i * ld + j] = s;
+    }
+    wave_lds_sync();
+    rts_gen_solve_upper(n, W, X, tid);  // X <- L^-T X
+    wave_lds_sync();
+    psd_factor();
+    samples(t, false);
+  }
+}
+
+// ---- host helpers --------------------------------------------------------------------------------------------------
+static Option g_ffbs_spl{0, OPT_FFBS_SPL};
+Option& ffbs_spl_option() { return g_ffbs_spl; }
+
+// the smallest compiled count that holds all S samples of a trajectory in one lane, 8 for S > 8 (header comment)
+static int ffbs_pick_spl(int S, int forced) {
+  if (forced) return forced;
+  int spl = 1;
+  while (spl < 8 && spl < S) spl *= 2;
+  return spl;
+}
+
+template <int N, int KIND, class Arg>
+static int launch_ffbs_n(const Arg& c, const float* d_gqg, const FfbsViews& v, long long B, long long T, int S, int forced_spl,
+                         hipStream_t stream) {
+  const int spl = ffbs_pick_spl(S, forced_spl);
+  const long long lanes = B * ((S + spl - 1) / spl);
+  if ((lanes + 63) / 64 > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B x S too large for one launch");
+  const dim3 grid((unsigned)((lanes + 63) / 64));
+  switch (spl) {
+    case 1: hipLaunchKernelGGL((ffbs_reg_kernel<N, 1, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S); break;
+    case 2: hipLaunchKernelGGL((ffbs_reg_kernel<N, 2, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S); break;
+    case 4: hipLaunchKernelGGL((ffbs_reg_kernel<N, 4, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S); break;
+    default: hipLaunchKernelGGL((ffbs_reg_kernel<N, 8, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S); break;
+  }
+  BF_HIP_CHECK(hipGetLastError());
+  return BF_OK;
+}
+
+static int launch_ffbs_generic(const FfbsGen& c0, const GenModel& g, const std::vector<float>& blk, const FfbsViews& v,
+                               long long B, long long T, hipStream_t stream) {
+  const size_t cap = 160 * 1024 / sizeof(float);
+  const int n = c0.r.n;
+  const size_t mat = ffbs_gen_mat_floats(n);
+  if (mat + 3 * (size_t)n > cap) {
+    int nmax = 1;
+    while (ffbs_gen_mat_floats(nmax + 1) + 3 * (size_t)(nmax + 1) <= cap) ++nmax;
+    return set_error(BF_EUNSUPPORTED, "sampler: n = %d needs %zu bytes of LDS (160 KiB per workgroup: n <= %d)", n,
+                     sizeof(float) * (mat + 3 * (size_t)n), nmax);
+  }
+  // samples per LDS block: up to 2048 floats per buffer (keeps several workgroups per CU), at least one sample
+  FfbsGen c = c0;
+  size_t sb = 2048 / (size_t)n;
+  if (sb < 1) sb = 1;
+  if (sb > (cap - mat) / (3 * (size_t)n)) sb = (cap - mat) / (3 * (size_t)n);
+  if (sb > (size_t)c.S) sb = (size_t)c.S;
+  c.SB = (int)sb;
+  const size_t lds = sizeof(float) * (mat + 3 * sb * n);
+  GenModel gg = g;
+  const int rc = rts_gen_upload(c.r, gg, blk, stream);
+  if (rc != BF_OK) return rc;
+  if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B too large for the run-time-dimension kernel");
+  if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ffbs_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(ffbs_generic_kernel, dim3((unsigned)B), dim3(64), lds, stream, c, gg, v, T);
+  BF_HIP_CHECK(hipGetLastError());
+  return BF_OK;
+}
+
+static int launch_ffbs_linear(const bf_lgssm* p, const FfbsViews& v, long long B, long long T, int S, bool recompute,
+                              bool force_generic, int spl, hipStream_t stream) {
+  const int n = p->n;
+  std::vector<float> A, GQG, Gq0;
+  rts_lin_fill(p, A, GQG, Gq0);
+  const bool tv = recompute && p->Q_steps > 1;
+  if (!force_generic && n <= 8) {
+    const float* d_gqg = nullptr;
+    if (tv) {
+      const void* dv = nullptr;
+      const int rc = device_constants(GQG.data(), sizeof(float) * GQG.size(), stream, &dv);
+      if (rc != BF_OK) return rc;
+      d_gqg = static_cast<const float*>(dv);
+    }
+    auto go = [&](auto NC) -> int {
+      constexpr int N = decltype(NC)::value;
+      const RtsLin<N> c = rts_lin_arg<N>(A, GQG, Gq0);
+      if (recompute) return launch_ffbs_n<N, RTS_LIN_RECOMPUTE>(c, d_gqg, v, B, T, S, spl, stream);
+      return launch_ffbs_n<N, RTS_LIN>(c, nullptr, v, B, T, S, spl, stream);
+    };
+    BF_RTS_DIMS(n, go)
+  }
+  std::vector<float> blk;
+  FfbsGen c;
+  std::memset(&c, 0, sizeof(c));
+  rts_gen_lin_block(p, recompute, A, GQG, Gq0, c.r, blk);
+  c.S = S;
+  GenModel g;
+  std::memset(&g, 0, sizeof(g));
+  return launch_ffbs_generic(c, g, blk, v, B, T, stream);
+}
+
+static int launch_ffbs_ext(const bf_model* p, const FfbsViews& v, long long B, long long T, int S, bool force_generic, int spl,
+                           hipStream_t stream) {
+  GenModel g;
+  std::vector<float> blk;
+  int rc = gen_fill(p, T, g, blk);  // validates the registry ids and theta layouts
+  if (rc != BF_OK) return rc;
+  const int n = p->n;
+  if (!force_generic && n <= 8) {
+    auto go = [&](auto NC) -> int {
+      constexpr int N = decltype(NC)::value;
+      return launch_ffbs_n<N, RTS_EXT>(rts_ekf_arg<N>(p, g), nullptr, v, B, T, S, spl, stream);
+    };
+    BF_RTS_DIMS(n, go)
+  }
+  FfbsGen c;
+  std::memset(&c, 0, sizeof(c));
+  c.r.n = n;
+  c.r.kind = RTS_EXT;
+  c.S = S;
+  return launch_ffbs_generic(c, g, blk, v, B, T, stream);
+}
+
+// bf_out_desc / bf_sample_carry / bf_sample_desc -> FfbsViews, with the checks both entry points share
+static int ffbs_views(const bf_out_desc* f, const bf_sample_carry* carry, const bf_sample_desc* out, const bf_cstream* u,
+                      long long B, long long T, int S, int n, bool need_pred, FfbsViews& v) {
+  if (B <= 0 || T <= 0) return set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", B, T);
+  if (S <= 0) return set_error(BF_EINVAL, "the number of samples S must be positive (S=%d)", S);
+  if (!f->means.ptr || !f->covs.ptr) return set_error(BF_EINVAL, "filtered means and covariances are required");
+  const bool has_pm = f->pred_means.ptr != nullptr, has_pP = f->pred_covs.ptr != nullptr;
+  if (has_pm != has_pP) return set_error(BF_EINVAL, "pred_means and pred_covs are given together or not at all");
+  if (need_pred && !has_pm) return set_error(BF_EINVAL, "the extended sampler needs the predicted means and covariances");
+  if (!out->samples.ptr) return set_error(BF_EINVAL, "the samples stream is a required output");
+  if (!out->noise.ptr && !out->keys) return set_error(BF_EINVAL, "give the noise stream or the keys");
+  if (!out->noise.ptr && (long long)S * T * n > 0x7fffffffLL)
+    return set_error(BF_EINVAL, "drawing from keys serves S*T*n <= 2^31 - 1 values per trajectory; sample in chunks of T");
+  if (S > 0x7fffffff / n) return set_error(BF_EINVAL, "S too large");
+  std::memset(&v, 0, sizeof(v));
+  v.m = make_sview(f->means);
+  v.P = make_sview(f->covs);
+  v.pm = make_sview(f->pred_means);
+  v.pP = make_sview(f->pred_covs);
+  v.x = make_sview(out->samples);
+  v.xi = SView{const_cast<float*>(out->noise.ptr), out->noise.sB, out->noise.sK, out->noise.sT, out->noise.sE};
+  v.keys = out->keys;
+  if (carry) {
+    v.x_in = carry->x_in;
+    v.x_out = carry->x_out;
+  }
+  if (u && u->ptr) {
+    v.u = u->ptr;
+    v.u_sB = u->sB;
+    v.u_sT = u->sT;
+  }
+  return BF_OK;
+}
+
+static int ffbs_spl_checked(int* spl) {
+  *spl = g_ffbs_spl.load();
+  if (*spl != 0 && *spl != 1 && *spl != 2 && *spl != 4 && *spl != 8)
+    return set_error(BF_EINVAL, "ffbs_spl must be 0 or one of the compiled counts 1, 2, 4, 8");
+  return BF_OK;
+}
+
+Option& force_generic_option();  // bf_api.hip
+
+}  // namespace bf
+
+extern "C" {
+
+int bf_sampler_abi_check(size_t sizeof_sample_desc, size_t sizeof_sample_carry) {
+#define BF_ABI_SIZE(NAME_, T_)                                                                                  \
+  if (NAME_ != 0 && NAME_ != sizeof(T_)) \
+    return bf::set_error(BF_EINVAL, "binding's sizeof(" #T_ ") = %zu, the library's is %zu: the struct layouts differ", NAME_, sizeof(T_));
+  BF_ABI_SIZE(sizeof_sample_desc, bf_sample_desc)
+  BF_ABI_SIZE(sizeof_sample_carry, bf_sample_carry)
+#undef BF_ABI_SIZE
+  return BF_OK;
+}
+
+int bf_ffbs_sample_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T, int32_t S,
+                       const bf_sample_carry* carry, const bf_sample_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  if (!model || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (model->n <= 0 || model->dq <= 0) return bf::set_error(BF_EINVAL, "non-positive model dimension");
+  if (!model->A) return bf::set_error(BF_EINVAL, "A is required");
+  if (!model->G && model->dq != model->n) return bf::set_error(BF_EINVAL, "G == NULL requires dq == n");
+  bf::FfbsViews v;
+  int rc = bf::ffbs_views(filtered, carry, out, nullptr, B, T, S, model->n, false, v);
+  if (rc != BF_OK) return rc;
+  const bool recompute = v.pm.p == nullptr;
+  if (recompute) {
+    if (!model->Q) return bf::set_error(BF_EINVAL, "recomputing the predictions needs Q");
+    if (model->Q_steps < 1 || (model->Q_steps > 1 && model->Q_steps != T))
+      return bf::set_error(BF_EINVAL, "Q_steps must be 1 or T = %lld", (long long)T);
+  }
+  int spl;
+  if ((rc = bf::ffbs_spl_checked(&spl)) != BF_OK) return rc;
+  bf_lgssm lg = *model;
+  if (!recompute || lg.Q_steps < 1) lg.Q_steps = 1;  // the table is read on the recompute path only
+  return bf::launch_ffbs_linear(&lg, v, B, T, S, recompute, bf::force_generic_option().load() != 0, spl,
+                                static_cast<hipStream_t>(stream));
+}
+
+int bf_effbs_sample_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
+                        int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  if (!model || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (model->user || model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER)
+    return bf::set_error(BF_EUNSUPPORTED, "the extended sampler serves registry dynamics; functions given as source are not supported");
+  if (model->flags != 0)
+    return bf::set_error(BF_EUNSUPPORTED, "the extended sampler needs the JAX path's update -> predict streams (flags = 0)");
+  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
+    return bf::set_error(BF_EINVAL, "non-positive model dimension");
+  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
+  bf::FfbsViews v;
+  int rc = bf::ffbs_views(filtered, carry, out, u, B, T, S, model->n, true, v);
+  if (rc != BF_OK) return rc;
+  int spl;
+  if ((rc = bf::ffbs_spl_checked(&spl)) != BF_OK) return rc;
+  return bf::launch_ffbs_ext(model, v, B, T, S, bf::force_generic_option().load() != 0, spl, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -7,30 +7,15 @@
 // n x n matrices of a step plus the carry spill into the accumulation registers, not to memory).  Staged path (n <= 4,
 // plus the chunk's prefetch registers): n = 1: 76-114 / 4-6, n = 2: 125-180 / 2-4, n = 3: 261-357 / 1, n = 4: 255-343 / 1-2.
 // The run-time-dimension kernel serves n > 8 and "force_generic" = 1.
-#include <cstring>
-#include <vector>
-#include "rts_smoother.hpp"
-#include "generic_device.hpp"
+#include "rts_generic.hpp"
 #include "lgssm_pack.hpp"
 
 namespace bf {
 
-int gen_fill(const bf_model* p, long long T, GenModel& g, std::vector<float>& blk);  // generic_scan.hip
-
 // ---- run-time-dimension kernel -----------------------------------------------------------------------------------
-// One 64-lane workgroup per trajectory.  LDS: five n x ld matrices (P, P^s, P-, X, W) and four vectors.  Per step:
-// W <- F_t (registry dynamics; linear: A read from the constant block), X = F P, [recompute: P- = X F^T + GQG_t,
-// m- = F m + G q0], W <- chol(P-) left-looking (one column per barrier), X <- L^-T L^-1 X (a column per lane),
+// One 64-lane workgroup per trajectory.  LDS: five n x ld matrices (P, P^s, P-, X, W) and four vectors.  Per step, with
+// the helpers of rts_generic.hpp: W <- F_t, X = F P, [recompute: P-, m-], W <- chol(P-), X <- L^-T L^-1 X,
 // C = X^T P^s (straight to HBM), m^s <- m + X^T (m^s - m-), P^s <- P^s - P-, P- <- X^T (P^s), P <- P + P- X, swap P / P^s.
-struct RtsGen {
-  int n, kind;          // RTS_LIN, RTS_LIN_RECOMPUTE, RTS_EXT
-  const float* A;       // [n][n]            (linear kinds)
-  const float* GQG;     // [q_steps][n][n]   (recompute)
-  const float* Gq0;     // [n]               (recompute)
-  int q_tv;
-};
-
-__host__ __device__ inline int rts_gen_ld(int n) { return n + 1; }
 static inline size_t rts_gen_lds_floats(int n) { return 5 * (size_t)n * rts_gen_ld(n) + 4 * (size_t)n; }
 
 __global__ void __launch_bounds__(64) rts_generic_kernel(RtsGen c, GenModel g, RtsViews v, long long T) {
@@ -68,66 +53,11 @@ __global__ void __launch_bounds__(64) rts_generic_kernel(RtsGen c, GenModel g, R
       for (int e = tid; e < nn; e += 64) Pp[(e / n) * ld + e % n] = v.pP.p[at(v.pP, t, e)];
     }
     wave_lds_sync();
-    const float* F;
-    int ldf;
-    if (c.kind == RTS_EXT) {
-      const float u0 = v.u ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
-      gen_dyn_linearize<64>(g, m, u0, W, ld, tv, tid);
-      wave_lds_sync();
-      F = W;
-      ldf = ld;
-    } else {
-      F = c.A;
-      ldf = n;
-    }
-    for (int e = tid; e < nn; e += 64) {  // X = F P
-      const int i = e / n, j = e - i * n;
-      float s = F[i * ldf] * P[j];
-      for (int k = 1; k < n; ++k) s = fmaf(F[i * ldf + k], P[k * ld + j], s);
-      X[i * ld + j] = s;
-    }
-    wave_lds_sync();
-    if (c.kind == RTS_LIN_RECOMPUTE) {
-      const float* q = c.GQG + (c.q_tv ? t * nn : 0);
-      for (int e = tid; e < nn; e += 64) {  // P- = (F P) F^T + G Q_t G^T
-        const int i = e / n, j = e - i * n;
-        float s = X[i * ld] * F[j * ldf];
-        for (int k = 1; k < n; ++k) s = fmaf(X[i * ld + k], F[j * ldf + k], s);
-        Pp[i * ld + j] = s + q[e];
-      }
-      for (int i = tid; i < n; i += 64) {
-        float s = F[i * ldf] * m[0];
-        for (int k = 1; k < n; ++k) s = fmaf(F[i * ldf + k], m[k], s);
-        mp[i] = s + c.Gq0[i];
-      }
-      wave_lds_sync();
-    }
-    // Cholesky of P- into W (lower triangle); every lane forms the pivot itself
-    for (int j = 0; j < n; ++j) {
-      float d = Pp[j * ld + j];
-      for (int k = 0; k < j; ++k) d = fmaf(-W[j * ld + k], W[j * ld + k], d);
-      d = fast_sqrt(d);
-      const float inv = fast_rcp(d);
-      for (int i = j + 1 + tid; i < n; i += 64) {
-        float s = Pp[i * ld + j];
-        for (int k = 0; k < j; ++k) s = fmaf(-W[i * ld + k], W[j * ld + k], s);
-        W[i * ld + j] = s * inv;
-      }
-      if (tid == 0) W[j * ld + j] = inv;  // the diagonal holds the reciprocal pivot
-      wave_lds_sync();
-    }
-    for (int cc = tid; cc < n; cc += 64) {  // X <- L^-T L^-1 X, a column per lane
-      for (int i = 0; i < n; ++i) {
-        float s = X[i * ld + cc];
-        for (int k = 0; k < i; ++k) s = fmaf(-W[i * ld + k], X[k * ld + cc], s);
-        X[i * ld + cc] = s * W[i * ld + i];
-      }
-      for (int i = n - 1; i >= 0; --i) {
-        float s = X[i * ld + cc];
-        for (int k = i + 1; k < n; ++k) s = fmaf(-W[k * ld + i], X[k * ld + cc], s);
-        X[i * ld + cc] = s * W[i * ld + i];
-      }
-    }
+    const float u0 = (c.kind == RTS_EXT && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+    rts_gen_linearize(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid);
+    rts_gen_chol(n, Pp, W, tid);
+    rts_gen_solve_lower(n, W, X, tid);  // X <- L^-T L^-1 X
+    rts_gen_solve_upper(n, W, X, tid);
     wave_lds_sync();
     if (want_c) {
       for (int e = tid; e < nn; e += 64) {  // C = G P^s = X^T P^s
@@ -175,14 +105,44 @@ __global__ void __launch_bounds__(64) rts_generic_kernel(RtsGen c, GenModel g, R
 }
 
 // ---- host helpers --------------------------------------------------------------------------------------------------
-// A, G Q_s G^T for every step s of Q, G q0 (lgssm_pack.hpp: the bits the filters upload)
-static void rts_lin_fill(const bf_lgssm* p, std::vector<float>& A, std::vector<float>& GQG, std::vector<float>& Gq0) {
+// host helpers shared with the sampler (rts_generic.hpp)
+void rts_lin_fill(const bf_lgssm* p, std::vector<float>& A, std::vector<float>& GQG, std::vector<float>& Gq0) {
   const int n = p->n, dq = p->dq, qs = p->Q_steps;
   A.assign(p->A, p->A + (size_t)n * n);
   GQG.assign((size_t)qs * n * n, 0.f);
-  for (int s = 0; s < qs; ++s) noise_cov(p->G, p->Q + (size_t)s * dq * dq, n, dq, &GQG[(size_t)s * n * n], n);
+  if (p->Q) for (int s = 0; s < qs; ++s) noise_cov(p->G, p->Q + (size_t)s * dq * dq, n, dq, &GQG[(size_t)s * n * n], n);
   Gq0.assign(n, 0.f);
   noise_mean(p->G, p->q0, n, dq, Gq0.data());
+}
+
+void rts_gen_lin_block(const bf_lgssm* p, bool recompute, const std::vector<float>& A, const std::vector<float>& GQG,
+                       const std::vector<float>& Gq0, RtsGen& c, std::vector<float>& blk) {
+  const int n = p->n;
+  blk.clear();
+  blk.insert(blk.end(), A.begin(), A.end());
+  blk.insert(blk.end(), Gq0.begin(), Gq0.end());
+  blk.insert(blk.end(), GQG.begin(), GQG.end());
+  c.n = n;
+  c.kind = recompute ? RTS_LIN_RECOMPUTE : RTS_LIN;
+  c.A = reinterpret_cast<const float*>((size_t)0);
+  c.Gq0 = reinterpret_cast<const float*>((size_t)n * n);
+  c.GQG = reinterpret_cast<const float*>((size_t)n * n + n);
+  c.q_tv = p->Q_steps > 1;
+}
+
+int rts_gen_upload(RtsGen& c, GenModel& gg, const std::vector<float>& blk, hipStream_t stream) {
+  const void* dv = nullptr;
+  const int rc = device_constants(blk.data(), sizeof(float) * blk.size(), stream, &dv);
+  if (rc != BF_OK) return rc;
+  const float* base = static_cast<const float*>(dv);
+  auto fix = [&](const float*& q) { q = base + reinterpret_cast<size_t>(q); };
+  if (c.kind == RTS_EXT) {
+    fix(gg.A); fix(gg.Hm); fix(gg.Gq0); fix(gg.Dr0); fix(gg.R); fix(gg.r0); fix(gg.GQG); fix(gg.DRD);
+    fix(gg.q0); fix(gg.Q); fix(gg.dyn_theta); fix(gg.emi_theta);
+  } else {
+    fix(c.A); fix(c.GQG); fix(c.Gq0);
+  }
+  return BF_OK;
 }
 
 static inline bool rts_ref_stream(const SView& s, long long E, long long T) {
@@ -236,20 +196,12 @@ static int launch_rts_generic(const RtsGen& c0, const GenModel& g, const std::ve
   const size_t lds = sizeof(float) * rts_gen_lds_floats(c0.n);
   if (lds > 160 * 1024)
     return set_error(BF_EUNSUPPORTED, "smoother: n = %d needs %zu bytes of LDS (160 KiB per workgroup)", c0.n, lds);
-  const void* dv = nullptr;
-  const int rc = device_constants(blk.data(), sizeof(float) * blk.size(), stream, &dv);
-  if (rc != BF_OK) return rc;
-  const float* base = static_cast<const float*>(dv);
   RtsGen c = c0;
   GenModel gg = g;
-  auto fix = [&](const float*& q) { q = base + reinterpret_cast<size_t>(q); };
-  if (c.kind == RTS_EXT) {
-    fix(gg.A); fix(gg.Hm); fix(gg.Gq0); fix(gg.Dr0); fix(gg.R); fix(gg.r0); fix(gg.GQG); fix(gg.DRD);
-    fix(gg.q0); fix(gg.Q); fix(gg.dyn_theta); fix(gg.emi_theta);
-  } else {
-    fix(c.A); fix(c.GQG); fix(c.Gq0);
-  }
+  const int rc = rts_gen_upload(c, gg, blk, stream);
+  if (rc != BF_OK) return rc;
   if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "smoother: B too large for the run-time-dimension kernel");
+  if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(rts_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(rts_generic_kernel, dim3((unsigned)B), dim3(64), lds, stream, c, gg, v, T);
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;
@@ -271,37 +223,16 @@ int launch_rts_linear(const bf_lgssm* p, const RtsViews& v, long long B, long lo
     }
     auto go = [&](auto NC) -> int {
       constexpr int N = decltype(NC)::value;
-      RtsLin<N> c;
-      std::memcpy(c.A, A.data(), sizeof(c.A));
-      std::memcpy(c.GQG, GQG.data(), sizeof(c.GQG));
-      std::memcpy(c.Gq0, Gq0.data(), sizeof(c.Gq0));
+      const RtsLin<N> c = rts_lin_arg<N>(A, GQG, Gq0);
       if (recompute) return launch_rts_n<N, RTS_LIN_RECOMPUTE>(c, d_gqg, v, B, T, load_mode, stream);
       return launch_rts_n<N, RTS_LIN>(c, nullptr, v, B, T, load_mode, stream);
     };
-    switch (n) {
-      case 1: return go(std::integral_constant<int, 1>{});
-      case 2: return go(std::integral_constant<int, 2>{});
-      case 3: return go(std::integral_constant<int, 3>{});
-      case 4: return go(std::integral_constant<int, 4>{});
-      case 5: return go(std::integral_constant<int, 5>{});
-      case 6: return go(std::integral_constant<int, 6>{});
-      case 7: return go(std::integral_constant<int, 7>{});
-      default: return go(std::integral_constant<int, 8>{});
-    }
+    BF_RTS_DIMS(n, go)
   }
   if (load_mode == RTS_STAGED) return set_error(BF_EINVAL, "rts_load_mode = 2 needs n <= 4 on the register kernel");
-  // constant block A | Gq0 | GQG[qs] (offsets, fixed up once uploaded)
   std::vector<float> blk;
-  blk.insert(blk.end(), A.begin(), A.end());
-  blk.insert(blk.end(), Gq0.begin(), Gq0.end());
-  blk.insert(blk.end(), GQG.begin(), GQG.end());
   RtsGen c;
-  c.n = n;
-  c.kind = recompute ? RTS_LIN_RECOMPUTE : RTS_LIN;
-  c.A = reinterpret_cast<const float*>((size_t)0);
-  c.Gq0 = reinterpret_cast<const float*>((size_t)n * n);
-  c.GQG = reinterpret_cast<const float*>((size_t)n * n + n);
-  c.q_tv = p->Q_steps > 1;
+  rts_gen_lin_block(p, recompute, A, GQG, Gq0, c, blk);
   GenModel g;
   std::memset(&g, 0, sizeof(g));
   return launch_rts_generic(c, g, blk, v, B, T, stream);
@@ -317,23 +248,9 @@ int launch_rts_ext(const bf_model* p, const RtsViews& v, long long B, long long 
   if (!force_generic && n <= 8) {
     auto go = [&](auto NC) -> int {
       constexpr int N = decltype(NC)::value;
-      EkfModel<N, 1> e;
-      std::memset(&e, 0, sizeof(e));
-      e.dyn_id = p->dyn_id;
-      for (int i = 0; i < 8; ++i) e.dth[i] = g.dth[i];
-      if (p->dyn_id == DYN_LINEAR) for (int i = 0; i < N * N; ++i) e.A[i] = p->dyn_theta[i];
-      return launch_rts_n<N, RTS_EXT>(e, nullptr, v, B, T, load_mode, stream);
+      return launch_rts_n<N, RTS_EXT>(rts_ekf_arg<N>(p, g), nullptr, v, B, T, load_mode, stream);
     };
-    switch (n) {
-      case 1: return go(std::integral_constant<int, 1>{});
-      case 2: return go(std::integral_constant<int, 2>{});
-      case 3: return go(std::integral_constant<int, 3>{});
-      case 4: return go(std::integral_constant<int, 4>{});
-      case 5: return go(std::integral_constant<int, 5>{});
-      case 6: return go(std::integral_constant<int, 6>{});
-      case 7: return go(std::integral_constant<int, 7>{});
-      default: return go(std::integral_constant<int, 8>{});
-    }
+    BF_RTS_DIMS(n, go)
   }
   if (load_mode == RTS_STAGED) return set_error(BF_EINVAL, "rts_load_mode = 2 needs n <= 4 on the register kernel");
   RtsGen c;

@@ -133,6 +133,9 @@ int bf_device_count(void);
  *                   (bf_rts_smoother_f32, bf_eks_smoother_f32) honour it the same way.
  *   "rts_load_mode": the smoothers' data path: -1 = choose from the layout (default), 0 = strided per-lane loads and
  *                   stores, 2 = LDS-staged time chunks (contiguous reference layout, n <= 4 only).
+ *   "ffbs_spl":     samples per lane of the posterior samplers' register kernel (n <= 8): 0 = the smallest compiled count that holds all S
+ *                   samples of a trajectory in one lane, 8 for S > 8 (default),
+ *                   otherwise one of the compiled counts 1, 2, 4, 8 (the arithmetic of a sample does not depend on it).
  *   "gsf_structured": 1 (default) lets bf_gsf_ekf_f32 use the structure-aware kernel instances
  *                   (banded Lorenz-96 Jacobian, selection emission) when the model qualifies;
  *                   0 forces the dense generic instances.
@@ -152,7 +155,8 @@ int bf_device_count(void);
  * bf_set_option changes the PROCESS-WIDE default.  A library or a thread that must not disturb -- or be disturbed by -- other
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
  * called on that thread (bf_kalman_filter_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
- * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_eks_smoother_f32) and for that call only; every armed override is dropped when
+ * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_eks_smoother_f32,
+ * bf_ffbs_sample_f32, bf_effbs_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
 int bf_set_option(const char* name, int value);
 int bf_set_call_option(const char* name, int value);
@@ -426,6 +430,52 @@ int bf_rts_smoother_f32(const bf_lgssm* model, const bf_out_desc* filtered, int6
  * BF_EUNSUPPORTED for functions given as source (BF_FN_USER) and for model->flags != 0. */
 int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
                         const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream);
+
+/* ---- Posterior sampling: the backward half of forward-filter backward-sampling (dynamax's lgssm_posterior_sample) ----
+ * Draws S joint trajectories x_{0:T-1} ~ p(x_{0:T-1} | y_{0:T-1}) per filtered trajectory from the streams the smoothers
+ * read (same order, same F_t).  With xi_{s,t} in R^n standard normals:
+ *   t = T-1 (no carry):  x_{T-1} = m_{T-1} + psdchol(P_{T-1}; diag P_{T-1}) xi_{T-1}
+ *   t = T-2 ... 0:       Lp = chol(P-_{t+1})             (as the smoothers: lower triangle, no jitter, NaN if not PD)
+ *   (with a carry:       W  = Lp^-1 (F_t P_t),  X = Lp^-T W,  G_t = X^T
+ *    from t = T-1)       Sigma_t = P_t - W^T W           (symmetric by construction)
+ *                        L_t = psdchol(Sigma_t; diag P_t)
+ *                        x_t = m_t + G_t (x_{t+1} - m-_{t+1}) + L_t xi_t
+ * psdchol(S; d): left-looking Cholesky without pivoting; when the pivot p_j = S_jj - sum_k L_jk^2 is not greater than
+ * tau d_j, tau = 2^-17, column j of L is zero, diagonal included (a zero pivot of a PSD matrix implies a zero column:
+ * singular G Q G^T, e.g. the constant-velocity model, is part of the definition and not an error).  xi = 0 gives the RTS
+ * smoothed means.  One component (K = 1), flags == 0.
+ * With bf_sampler_abi_check and the two samplers below this header declares 30 entry points. */
+typedef struct bf_sample_desc {
+  bf_stream samples;    /* E = n; the K axis is the sample s: ptr[b*sB + s*sK + t*sT + e*sE]; required */
+  bf_cstream noise;     /* standard normals, same indexing; ptr == NULL: drawn from keys */
+  const uint32_t* keys; /* DEVICE [B][2], required when noise.ptr == NULL: trajectory b uses the S*T*n values
+                           bf_random_normal_f32(keys[b], S*T*n, ...) writes, element (s, t, i) at (s*T + t)*n + i */
+} bf_sample_desc;
+
+/* Backward chunking (as bf_smooth_carry).  DEVICE pointers, contiguous [B][S][n].
+ * x_in: the samples at the first step AFTER this chunk (NULL: the chunk ends at T-1).
+ * x_out: receives the samples at the chunk's first step (NULL = not written).
+ * The two fields are independent, unlike the m / P pairs of bf_smooth_carry: x_in without x_out (a chunk that takes a carry
+ * and hands none on) and x_out without x_in are both valid calls, so there is no "half a carry" to reject. */
+typedef struct bf_sample_carry {
+  const float* x_in;
+  float* x_out;
+} bf_sample_carry;
+
+/* ABI guard of the two sampler structs; a size of 0 = not mirrored. */
+int bf_sampler_abi_check(size_t sizeof_sample_desc, size_t sizeof_sample_carry);
+
+/* Posterior samples of the linear model.  filtered as in bf_rts_smoother_f32 (pred_* both NULL: recomputed, Q_steps
+ * honoured).  carry may be NULL.  Asynchronous on `stream`, no allocation.  n <= 8: registers, one lane per (trajectory,
+ * block of samples); other n and "force_generic": one workgroup per trajectory, matrices and samples in LDS
+ * (BF_EUNSUPPORTED when n exceeds its capacity). */
+int bf_ffbs_sample_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T, int32_t S,
+                       const bf_sample_carry* carry, const bf_sample_desc* out, void* stream);
+
+/* Posterior samples for registry dynamics (extended Kalman streams, pred_* required).  BF_EUNSUPPORTED for functions
+ * given as source (BF_FN_USER) and for model->flags != 0. */
+int bf_effbs_sample_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
+                        int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream);
 
 /* Bytes one (trajectory, timestep) moves for the streams enabled in `out`: the algorithmic
  * traffic figure of SURVEY.md 8(d)  (4m + 4K(1 + 2n + 2n^2) for all five streams). */
