@@ -12,6 +12,7 @@ from .inference import (PosteriorGaussianSumFiltered, gaussian_sum_filter, unsce
 from .smoother import (PosteriorGaussianSmoothed, SmootherCarry, rts_smoother, kalman_smoother,
                        extended_kalman_smoother)
 from .sampler import (SamplerCarry, posterior_sample, kalman_posterior_sample, extended_kalman_posterior_sample)
+from .particle_sampler import (ParticleSamplerCarry, particle_posterior_sample, bootstrap_particle_posterior_sample)
 from ._lib import BayesFiltError
 from . import nonlinearities, utils
 
@@ -20,4 +21,5 @@ __all__ = ["ParamsNLSSM", "ParamsBPF", "NonlinearSSM", "GaussianComponent", "Gau
            "sample_initial_component_means", "bootstrap_particle_filter", "ParticleCarry", "resample_indices",
            "nonlinearities", "utils", "BayesFiltError",
            "PosteriorGaussianSmoothed", "SmootherCarry", "rts_smoother", "kalman_smoother", "extended_kalman_smoother",
-           "SamplerCarry", "posterior_sample", "kalman_posterior_sample", "extended_kalman_posterior_sample"]
+           "SamplerCarry", "posterior_sample", "kalman_posterior_sample", "extended_kalman_posterior_sample",
+           "ParticleSamplerCarry", "particle_posterior_sample", "bootstrap_particle_posterior_sample"]

@@ -58,6 +58,22 @@ class bf_sample_carry(C.Structure):
     _fields_ = [("x_in", C.c_void_p), ("x_out", C.c_void_p)]
 
 
+class bf_pf_history(C.Structure):
+    _fields_ = [("weights", C.c_void_p), ("w_sB", C.c_int64), ("w_sN", C.c_int64), ("w_sT", C.c_int64),
+                ("particles", C.c_void_p), ("x_sB", C.c_int64), ("x_sN", C.c_int64), ("x_sT", C.c_int64),
+                ("ancestors", C.c_void_p)]
+
+
+class bf_pf_sample_desc(C.Structure):
+    _fields_ = [("samples", bf_stream), ("indices", C.c_void_p), ("noise", C.c_void_p), ("z_sB", C.c_int64),
+                ("z_sS", C.c_int64), ("z_sT", C.c_int64), ("keys", C.c_void_p)]
+
+
+class bf_pf_sample_carry(C.Structure):
+    _fields_ = [("x_in", C.c_void_p), ("u_in", C.c_void_p), ("a_in", C.c_void_p), ("x_out", C.c_void_p),
+                ("a_out", C.c_void_p)]
+
+
 class bf_lgssm(C.Structure):
     _fields_ = [("n", C.c_int32), ("dq", C.c_int32), ("m", C.c_int32), ("dr", C.c_int32),
                 ("A", _FP), ("G", _FP), ("H", _FP), ("D", _FP), ("q0", _FP), ("r0", _FP), ("Q", _FP), ("R", _FP),
@@ -145,6 +161,13 @@ SYMBOLS = {
     "bf_effbs_sample_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_out_desc), C.c_int64,
                                       C.c_int64, C.c_int32, C.POINTER(bf_sample_carry), C.POINTER(bf_sample_desc),
                                       C.c_void_p]),
+    "bf_pf_sampler_abi_check": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t]),
+    "bf_pf_backward_sample_f32": (C.c_int, [C.POINTER(bf_bpf_model), C.POINTER(bf_cstream), C.POINTER(bf_pf_history), C.c_int64,
+                                            C.c_int64, C.c_int32, C.c_int32, C.POINTER(bf_pf_sample_carry),
+                                            C.POINTER(bf_pf_sample_desc), C.c_void_p]),
+    "bf_pf_trace_sample_f32": (C.c_int, [C.POINTER(bf_pf_history), C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(bf_pf_sample_carry), C.POINTER(bf_pf_sample_desc), C.c_void_p]),
+    "bf_random_uniform_f32": (C.c_int, [C.POINTER(C.c_uint32), C.c_int64, _FP]),
 }
 
 _lib = None
@@ -175,6 +198,8 @@ def load():
     if lib.bf_smoother_abi_check(C.sizeof(bf_smooth_desc), C.sizeof(bf_smooth_carry)) != BF_OK:
         raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
     if lib.bf_sampler_abi_check(C.sizeof(bf_sample_desc), C.sizeof(bf_sample_carry)) != BF_OK:
+        raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
+    if lib.bf_pf_sampler_abi_check(C.sizeof(bf_pf_history), C.sizeof(bf_pf_sample_desc), C.sizeof(bf_pf_sample_carry)) != BF_OK:
         raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
     _lib = lib
     return lib

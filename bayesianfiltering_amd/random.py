@@ -1,6 +1,6 @@
 """``import bayesianfiltering_amd.random as jr`` -- the handful of ``jax.random`` calls the reference's scripts make around the
 filters (docs/experiments/*.py: ``jr.PRNGKey``, ``jr.split``, ``jr.normal``, ``jr.multivariate_normal``), on the engine's own
-Threefry-2x32 (the library's host functions ``bf_random_split`` / ``bf_random_normal_f32``: JAX's counter layout and bits -> normal
+Threefry-2x32 (the library's host functions ``bf_random_split`` / ``bf_random_normal_f32`` / ``bf_random_uniform_f32``: JAX's counter layout and bits -> normal
 mapping, pinned against keys and draws the reference recorded -- tests/test_oracle_rng.py, tests/test_sample_gpu.py).  Keys are
 ``(2,) uint32`` arrays as in JAX's raw form.
 """
@@ -29,6 +29,17 @@ def normal(key, shape=()):
     count = int(np.prod(shape)) if shape else 1
     z = _random_normal(key, count)
     return z.reshape(shape) if shape else F32(z[0])
+
+
+def uniform(key, shape=()):
+    """``jax.random.uniform(key, shape)`` in float32, [0, 1)."""
+    shape = (shape,) if isinstance(shape, (int, np.integer)) else tuple(shape)
+    count = int(np.prod(shape)) if shape else 1
+    lib = _lib.load()
+    key = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
+    out = np.empty(count, dtype=F32)
+    _lib.check(lib.bf_random_uniform_f32(key.ctypes.data_as(C.POINTER(C.c_uint32)), count, out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out.reshape(shape) if shape else F32(out[0])
 
 
 def multivariate_normal(key, mean, cov, shape=()):

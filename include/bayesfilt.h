@@ -156,7 +156,7 @@ int bf_device_count(void);
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
  * called on that thread (bf_kalman_filter_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
  * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_eks_smoother_f32,
- * bf_ffbs_sample_f32, bf_effbs_sample_f32) and for that call only; every armed override is dropped when
+ * bf_ffbs_sample_f32, bf_effbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
 int bf_set_option(const char* name, int value);
 int bf_set_call_option(const char* name, int value);
@@ -444,7 +444,8 @@ int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out
  * tau d_j, tau = 2^-17, column j of L is zero, diagonal included (a zero pivot of a PSD matrix implies a zero column:
  * singular G Q G^T, e.g. the constant-velocity model, is part of the definition and not an error).  xi = 0 gives the RTS
  * smoothed means.  One component (K = 1), flags == 0.
- * With bf_sampler_abi_check and the two samplers below this header declares 30 entry points. */
+ * With bf_sampler_abi_check, the two samplers below and the four entry points of the particle smoother this header declares
+ * 34 entry points. */
 typedef struct bf_sample_desc {
   bf_stream samples;    /* E = n; the K axis is the sample s: ptr[b*sB + s*sK + t*sT + e*sE]; required */
   bf_cstream noise;     /* standard normals, same indexing; ptr == NULL: drawn from keys */
@@ -476,6 +477,74 @@ int bf_ffbs_sample_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64
  * given as source (BF_FN_USER) and for model->flags != 0. */
 int bf_effbs_sample_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
                         int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream);
+
+/* ---- Particle smoothing: joint draws from a bootstrap particle filter's stored history -------------------------------
+ * S joint trajectories x_{0:T-1} ~ p(x_{0:T-1} | y_{0:T-1}) per filtered trajectory from what bf_bpf_f32 wrote: weights
+ * w[i,t], particles x[i,t,:] and (genealogy only) ancestors a[i,t] (identity on steps that did not resample).  Per sample s
+ * and step t a uniform v[s,t] in [0,1) is given.
+ *   draw(l, v):  M = max_i l_i;  e_i = exp(l_i - M);  c = inclusive cumulative sum of e in index order; the result is the
+ *                smallest j with c_j > v c_{N-1}, clamped to N-1 ("greater than": in exact arithmetic a drawn particle never has e_j = 0).
+ *                M not finite: the draw is INVALID.
+ *   Backward simulation (bf_pf_backward_sample_f32):
+ *     t = T-1 without a carry:   l_i = log w[i,T-1]
+ *     every other step, and T-1 with a carry:
+ *                                l_i = log w[i,t] - 1/2 |L^-1 (x~_{t+1} - mu_i)|^2,  mu_i = f(x[i,t], q0, u_{t+1}),
+ *                                L = lower Cholesky factor of F_q Q F_q^T (the common normalising constant is dropped)
+ *     j_t = draw(l, v[s,t]),  x~_t = x[j_t,t,:]: an exact copy of a stored particle.
+ *   Genealogy (bf_pf_trace_sample_f32): j_{T-1} = draw(log w[:,T-1], v[s,T-1]) (only that uniform is used),
+ *     j_{t-1} = a[j_t,t], x~_t = x[j_t,t,:].  With the same uniforms both methods return the same x~_{T-1}.
+ *   An invalid draw (the filter went NaN, or every logit overflowed) writes NaN and index -1 at that step and at every earlier
+ *   step of that sample, and into the carry; other samples and trajectories are untouched.
+ *   The arithmetic is fp32 with the hardware's log / exp; the order of the maximum and of the cumulative sum depends on N
+ *   alone (csrc/pf_sampler.hpp), so a sample's bits do not depend on S, on B or on which samples share a launch. */
+typedef struct bf_pf_history {
+  const float* weights;   /* element (b,i,t) at weights[b*w_sB + i*w_sN + t*w_sT]: the strides of bf_bpf_out */
+  int64_t w_sB, w_sN, w_sT;
+  const float* particles; /* element (b,i,t,d) at particles[b*x_sB + i*x_sN + t*x_sT + d] */
+  int64_t x_sB, x_sN, x_sT;
+  const int32_t* ancestors; /* the weights' strides; required by bf_pf_trace_sample_f32 only */
+} bf_pf_history;
+
+typedef struct bf_pf_sample_desc {
+  bf_stream samples;    /* E = n; the K axis is the sample s: ptr[b*sB + s*sK + t*sT + e*sE]; required */
+  int32_t* indices;     /* optional: the drawn particle indices j, contiguous [B][S][T] */
+  const float* noise;   /* uniforms in [0,1), element (b,s,t) at noise[b*z_sB + s*z_sS + t*z_sT]; or NULL and keys given */
+  int64_t z_sB, z_sS, z_sT;
+  const uint32_t* keys; /* DEVICE [B][2]: trajectory b uses the S*T values bf_random_uniform_f32(keys[b], S*T, ...) writes,
+                           element (s,t) at s*T + t.  Exactly one of noise and keys. */
+} bf_pf_sample_desc;
+
+/* Backward chunking: the LAST chunk of steps first; its outputs are the next (earlier) chunk's inputs.  DEVICE pointers.
+ * x_in [B][S][n]: the samples at the first step AFTER this chunk (NULL: the chunk ends at T-1); u_in [B]: the input u of that
+ * step (NULL = zeros); a_in [B][S] (genealogy): the slot a[j,t] of that step, i.e. this chunk's j at its last step.
+ * x_out / a_out: receive x~ at this chunk's first step and the slot a[j_{t0},t0] (NULL = not written).  Backward simulation reads
+ * x_in / u_in and writes x_out; the genealogy reads a_in and writes x_out / a_out. */
+typedef struct bf_pf_sample_carry {
+  const float* x_in;
+  const float* u_in;
+  const int32_t* a_in;
+  float* x_out;
+  int32_t* a_out;
+} bf_pf_sample_carry;
+
+/* ABI guard of the three particle-smoother structs; a size of 0 = not mirrored. */
+int bf_pf_sampler_abi_check(size_t sizeof_history, size_t sizeof_sample_desc, size_t sizeof_sample_carry);
+
+/* Backward simulation.  model->ssm carries the registry dynamics, q0 and a constant Q (m0 / P0 / lp_cov and the emission are
+ * not read); u: the filter's inputs (NULL or u->ptr == NULL = zeros).  State dimensions 1 ... 16, N <= 4096.
+ * BF_EUNSUPPORTED, each naming the genealogy method: F_q Q F_q^T not positive definite (float64 Cholesky, pivot <= 2^-17 of
+ * the diagonal: e.g. the constant-velocity and manoeuvring-target models, dq < n), dynamics given as source, N > 4096; also
+ * for model->ssm.flags != 0 and Q_steps > 1.  Asynchronous on `stream`, no allocation. */
+int bf_pf_backward_sample_f32(const bf_bpf_model* model, const bf_cstream* u, const bf_pf_history* history, int64_t B, int64_t T,
+                              int32_t N, int32_t S, const bf_pf_sample_carry* carry, const bf_pf_sample_desc* out, void* stream);
+
+/* Genealogy tracing: needs no model (any f, any Q, any N); n = the state dimension.  An ancestor entry outside [0, N) ends
+ * the path as an invalid draw does. */
+int bf_pf_trace_sample_f32(const bf_pf_history* history, int64_t B, int64_t T, int32_t N, int32_t n, int32_t S,
+                           const bf_pf_sample_carry* carry, const bf_pf_sample_desc* out, void* stream);
+
+/* jax.random.uniform(key, (count,)) in [0, 1), written to a HOST buffer (beside bf_random_normal_f32). */
+int bf_random_uniform_f32(const uint32_t key[2], int64_t count, float* host_out);
 
 /* Bytes one (trajectory, timestep) moves for the streams enabled in `out`: the algorithmic
  * traffic figure of SURVEY.md 8(d)  (4m + 4K(1 + 2n + 2n^2) for all five streams). */
