@@ -92,6 +92,17 @@ def _stream_desc(t, n_event_dims):
     return s
 
 
+def _check_out_tensor(name, t, device):
+    """Refuse an ``out=`` tensor the kernels cannot write: they store float32 through raw pointers on the call's device."""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"out.{name} must be a torch tensor; got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"out.{name} must be float32; got {t.dtype}")
+    if t.device != device:
+        raise ValueError(f"out.{name} must be on {device}; got a tensor on {t.device}")
+
+
 def _time_varying(x, d):
     x = _host_f32(x)
     if x.ndim == 3:
@@ -191,6 +202,7 @@ def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=
         if name in fields:
             reuse = getattr(out, name, None) if out is not None else None
             if reuse is not None:
+                _check_out_tensor(name, reuse, y.device)
                 if tuple(reuse.shape) != (B, 1, T) + ev[name]:
                     raise ValueError(f"out.{name} has shape {tuple(reuse.shape)}")
                 bufs[name] = reuse
@@ -325,6 +337,7 @@ def _alloc_outputs(B, K, T, n, fields, layout, out, return_loglik, device):
         if name in fields:
             reuse = getattr(out, name, None) if out is not None else None
             if reuse is not None:
+                _check_out_tensor(name, reuse, device)
                 if tuple(reuse.shape) != (B, K, T) + ev[name]:
                     raise ValueError(f"out.{name} has shape {tuple(reuse.shape)}, expected {(B, K, T) + ev[name]}")
                 bufs[name] = reuse
