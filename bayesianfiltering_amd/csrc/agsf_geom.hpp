@@ -52,6 +52,14 @@ static inline int prepare_agsf(int n, const bf_cstream* y, const bf_cstream* u, 
   L.grid = (unsigned)((B + tpb - 1) / tpb);
   return BF_OK;
 }
+
+// agsf_generic.hip: the same filters on the run-time-dimension kernel (the node in turn in LDS; registry functions, any of n, dq, m,
+// dr above 8 -- or bf_set_option "agsf_force_generic" = 1).  up == NULL: extended-Kalman nodes, else unscented nodes.
+extern Option g_agsf_force_generic;
+int launch_agsf_generic(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
+                        const int32_t nc[3], const uint32_t key[2], const float opt[2], const bf_carry* carry, const bf_out_desc* out,
+                        int* d_leaf_idx, int variant, hipStream_t stream);
+static inline bool agsf_beyond_registers(const bf_model* p) { return p->n > 8 || p->dq > 8 || p->m > 8 || p->dr > 8; }
 #endif
 
 }  // namespace bf

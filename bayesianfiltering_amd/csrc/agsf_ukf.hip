@@ -39,6 +39,9 @@ int launch_agsf_user_impl(const bf_model* p, const bf_ukf_params* up, const bf_c
 int launch_agsf_ukf(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
                     const int32_t nc[3], const uint32_t key[2], const float opt[2], const bf_carry* carry, const bf_out_desc* out,
                     int* d_leaf_idx, int variant, hipStream_t stream) {
+  // beyond the registers (or on request), registry functions: the node in turn in LDS (agsf_generic.hip)
+  if (agsf_beyond_registers(p) || (!p->user && g_agsf_force_generic.load() != 0))
+    return launch_agsf_generic(p, up, y, u, B, T, nc, key, opt, carry, out, d_leaf_idx, variant, stream);
   if (p->user) return launch_agsf_user_impl(p, up, y, u, B, T, nc, key, opt, carry, out, d_leaf_idx, variant, stream);
 #define BF_CASE(N_, DQ_, M_, DR_)                                     \
   if (p->n == N_ && p->dq == DQ_ && p->m == M_ && p->dr == DR_)       \

@@ -74,6 +74,7 @@ extern Option g_bpf_spec;
 extern Option g_bpf_arith;
 extern Option g_gsf_structured;
 extern Option g_ugsf_force_generic;   // ugsf_generic.hip
+extern Option g_agsf_force_generic;   // agsf_generic.hip
 static Option g_kf_emit_mode{-1, OPT_KF_EMIT_MODE};  // -1 = choose from the layout
 static Option g_kf_lanes{0, OPT_KF_LANES};       // 0 = default lanes per trajectory for the (n, m) pair
 // op 0 log, 1 exp, 2 bits -> normal, 3 sin, 4 cos, 5 atan2(in[i], in[n + i])
@@ -190,6 +191,10 @@ static int set_option_impl(const char* name, int value, bool this_call_only) {
   if (name && std::strcmp(name, "ugsf_force_generic") == 0) {
     if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "ugsf_force_generic must be 0 or 1");
     return assign(bf::g_ugsf_force_generic);
+  }
+  if (name && std::strcmp(name, "agsf_force_generic") == 0) {
+    if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "agsf_force_generic must be 0 or 1");
+    return assign(bf::g_agsf_force_generic);
   }
   if (name && std::strcmp(name, "rts_load_mode") == 0) {
     if (value != -1 && value != 0 && value != 2) return bf::set_error(BF_EINVAL, "rts_load_mode must be -1, 0 or 2");

@@ -58,6 +58,41 @@ static int ug_nt64_max() {
 
 Option g_ugsf_force_generic{0, OPT_UGSF_FORCE_GENERIC};   // bf_set_option "ugsf_force_generic": 1 = this kernel also where every dimension is <= 8
 
+// The kernel-argument model of the run-time-dimension unscented kernels (this file's and agsf_generic.hip's): one constant block
+// on the device -- the flat words of a UkfModel<n, dq, m, dr> (validation, sqrtm(Q) / sqrtm(R) and the unscented constants:
+// fill_ukf_model_view), then the caller's parameter vectors at full length -- and the per-step sqrtm tables.
+int ug_model_prepare(const bf_model* p, const bf_ukf_params* up, int user_flags, hipStream_t stream, UgModel& g) {
+  const int n = p->n, dq = p->dq, m = p->m, dr = p->dr;
+  const bool udyn = (user_flags & 1) != 0, uemi = (user_flags & 2) != 0;
+  bf_model q = *p;
+  if (udyn) q.n_dyn_theta = 0;
+  if (uemi) q.n_emi_theta = 0;
+  const size_t nw = ukf_model_words(n, dq, m, dr);
+  const size_t nth_d = udyn && p->n_dyn_theta > 0 ? (size_t)p->n_dyn_theta : 0, nth_e = uemi && p->n_emi_theta > 0 ? (size_t)p->n_emi_theta : 0;
+  std::vector<uint32_t> words(nw + nth_d + nth_e + 2, 0u);
+  std::vector<float> tvq, tvr;
+  const UkfModelView e = ukf_model_view_flat(words.data(), n, dq, m, dr);
+  int rc = fill_ukf_model_view(&q, up, e, user_flags, &tvq, &tvr);
+  if (rc != BF_OK) return rc;
+  float* thd = reinterpret_cast<float*>(words.data()) + nw;
+  float* the = thd + nth_d + 1;
+  for (size_t i = 0; i < nth_d; ++i) thd[i] = p->dyn_theta[i];
+  for (size_t i = 0; i < nth_e; ++i) the[i] = p->emi_theta[i];
+  const void* dv = nullptr;
+  if ((rc = device_constants(words.data(), sizeof(uint32_t) * words.size(), stream, &dv)) != BF_OK) return rc;
+  g.dyn_id = p->dyn_id; g.emi_id = p->emi_id; g.n = n; g.dq = dq; g.m = m; g.dr = dr;
+  for (int i = 0; i < 8; ++i) { g.dth[i] = e.dth[i]; g.eth[i] = e.eth[i]; }
+  const float* base = static_cast<const float*>(dv);
+  const float* host = reinterpret_cast<const float*>(words.data());
+  auto dev = [&](const float* h) { return base + (h - host); };
+  g.A = dev(e.A); g.Gm = dev(e.Gm); g.Hm = dev(e.Hm); g.Dm = dev(e.Dm); g.q0 = dev(e.q0); g.r0 = dev(e.r0); g.sQ = dev(e.sQ); g.sR = dev(e.sR);
+  g.dyn_theta = dev(thd); g.emi_theta = dev(the);
+  g.c_u = e.cu[0]; g.ws_u = e.cu[1]; g.w0_u = e.cu[2]; g.wc_u = e.cu[3];
+  g.c_p = e.cp[0]; g.ws_p = e.cp[1]; g.w0_p = e.cp[2]; g.wc_p = e.cp[3];
+  if ((rc = upload_table(tvq, stream, &g.tvsq)) != BF_OK || (rc = upload_table(tvr, stream, &g.tvsr)) != BF_OK) return rc;
+  return BF_OK;
+}
+
 int launch_ugsf_generic(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
                         int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
   const int n = p->n, dq = p->dq, m = p->m, dr = p->dr;
@@ -86,35 +121,9 @@ int launch_ugsf_generic(const bf_model* p, const bf_ukf_params* up, const bf_cst
     return set_error(BF_EUNSUPPORTED, "run-time-dimension unscented filter: n = %d, dq = %d, m = %d, dr = %d, K = %d need %zu bytes of LDS (160 KiB per workgroup)",
                      n, dq, m, dr, K, lds_bytes);
 
-  // constant block: the flat words of a UkfModel<n, dq, m, dr> (validation, sqrtm(Q) / sqrtm(R) and the unscented constants:
-  // fill_ukf_model_view), then the caller's parameter vectors at full length
-  bf_model q = *p;
-  if (udyn) q.n_dyn_theta = 0;
-  if (uemi) q.n_emi_theta = 0;
-  const size_t nw = ukf_model_words(n, dq, m, dr);
-  const size_t nth_d = udyn && p->n_dyn_theta > 0 ? (size_t)p->n_dyn_theta : 0, nth_e = uemi && p->n_emi_theta > 0 ? (size_t)p->n_emi_theta : 0;
-  std::vector<uint32_t> words(nw + nth_d + nth_e + 2, 0u);
-  std::vector<float> tvq, tvr;
-  const UkfModelView e = ukf_model_view_flat(words.data(), n, dq, m, dr);
-  int rc = fill_ukf_model_view(&q, up, e, user_flags, &tvq, &tvr);
-  if (rc != BF_OK) return rc;
-  float* thd = reinterpret_cast<float*>(words.data()) + nw;
-  float* the = thd + nth_d + 1;
-  for (size_t i = 0; i < nth_d; ++i) thd[i] = p->dyn_theta[i];
-  for (size_t i = 0; i < nth_e; ++i) the[i] = p->emi_theta[i];
-  const void* dv = nullptr;
-  if ((rc = device_constants(words.data(), sizeof(uint32_t) * words.size(), stream, &dv)) != BF_OK) return rc;
   UgModel g;
-  g.dyn_id = p->dyn_id; g.emi_id = p->emi_id; g.n = n; g.dq = dq; g.m = m; g.dr = dr;
-  for (int i = 0; i < 8; ++i) { g.dth[i] = e.dth[i]; g.eth[i] = e.eth[i]; }
-  const float* base = static_cast<const float*>(dv);
-  const float* host = reinterpret_cast<const float*>(words.data());
-  auto dev = [&](const float* h) { return base + (h - host); };
-  g.A = dev(e.A); g.Gm = dev(e.Gm); g.Hm = dev(e.Hm); g.Dm = dev(e.Dm); g.q0 = dev(e.q0); g.r0 = dev(e.r0); g.sQ = dev(e.sQ); g.sR = dev(e.sR);
-  g.dyn_theta = dev(thd); g.emi_theta = dev(the);
-  g.c_u = e.cu[0]; g.ws_u = e.cu[1]; g.w0_u = e.cu[2]; g.wc_u = e.cu[3];
-  g.c_p = e.cp[0]; g.ws_p = e.cp[1]; g.w0_p = e.cp[2]; g.wc_p = e.cp[3];
-  if ((rc = upload_table(tvq, stream, &g.tvsq)) != BF_OK || (rc = upload_table(tvr, stream, &g.tvsr)) != BF_OK) return rc;
+  int rc = ug_model_prepare(p, up, user_flags, stream, g);
+  if (rc != BF_OK) return rc;
 
   // K > 1: carried means / covariances of the components that are not in the LDS tile (launch_gsf_generic's scheme)
   float* gm = nullptr;

@@ -489,7 +489,8 @@ def unscented_gaussian_sum_filter(params, uparams, emissions, num_components: in
 def speedy_augmented_gaussian_sum_filter(params, emissions, num_components, rng_key=None, num_iter: int = 1,
                                          opt_args=(0.1, 0.1), inputs=None, *, initial_means=None,
                                          initial_covariances=None, carry=None, return_carry: bool = False,
-                                         return_leaf_indices: bool = False, device="cuda", _variant=0, _uparams=None):
+                                         return_leaf_indices: bool = False, device="cuda", options=None, _variant=0,
+                                         _uparams=None):
     """"Speedy" augmented Gaussian-sum filter, gaussfiltax/inference.py:621-812, on the HIP engine.
 
     Same positional signature as the reference: ``num_components = (N0, N1, N2)``, ``rng_key`` defaults to
@@ -500,7 +501,14 @@ def speedy_augmented_gaussian_sum_filter(params, emissions, num_components, rng_
     that holds ``'leaf_indices'`` (T, N0) when ``return_leaf_indices`` (the reference's per-step debugging
     outputs -- Deltas, Lambdas, Jacobians, gains -- are not materialised) and ``'carry'`` when
     ``return_carry``.  ``initial_means`` (N0, n) overrides the fixed ``MVN(m0, P0).sample(N0, PRNGKey(0))``
-    draw (:799).  N0 * N1 * N2 <= 64 in general, <= 1024 for state_dim <= 4 (one workgroup per trajectory).
+    draw (:799).  ``options``: tuning options for this call only, as in :func:`gaussian_sum_filter`.
+
+    Limits.  While the state, noise and observation dimensions are all <= 8 a leaf lives in the registers of one lane:
+    N0 * N1 * N2 <= 64 in general, <= 1024 for state_dim <= 4; a nonlinear registry model needs one of the compiled
+    (state_dim, obs_dim) pairs.  Any dimension above 8 -- or ``options={"agsf_force_generic": 1}`` for a small model -- runs on
+    the run-time-dimension kernel (the tree's nodes take turns in LDS): registry functions at any dimension the 160 KiB of LDS
+    of a workgroup hold (n = 76 with n / 2 observations for extended nodes, n = 63 for unscented ones; the error names the
+    bytes needed), N0 * N1 * N2 <= 256.  Functions from source and recorded Python functions stay at dimensions up to 8.
     """
     torch = _torch()
     lib = _lib.require_gpu()
@@ -563,6 +571,7 @@ def speedy_augmented_gaussian_sum_filter(params, emissions, num_components, rng_
     leaf = torch.empty((B, T, N0), dtype=torch.int32, device=y.device) if return_leaf_indices else None
     stream = torch.cuda.current_stream(y.device).cuda_stream
     leaf_ptr = C.c_void_p(leaf.data_ptr() if leaf is not None else None)
+    _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
     if _uparams is None:
         _lib.check(lib.bf_agsf_ekf_f32(C.byref(mdl.c), C.byref(yd), C.byref(ud), B, T, nc.ctypes.data_as(C.POINTER(C.c_int32)),
                                        key.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(opt), C.byref(cr), C.byref(od),

@@ -131,6 +131,9 @@ int bf_device_count(void);
  *   "force_generic": 1 = bf_kalman_filter_f32 / bf_gsf_ekf_f32 run the run-time-dimension kernel (any n, m, K; state in
  *                   LDS) even where a compile-time-dimension instance exists (test hook; default 0).  The smoothers
  *                   (bf_rts_smoother_f32, bf_eks_smoother_f32) honour it the same way.
+ *   "agsf_force_generic": 1 = bf_agsf_ekf_f32 / bf_agsf_ukf_f32 run the run-time-dimension kernel (the node in turn in LDS, up
+ *                   to 256 leaves per trajectory, registry functions) even where every dimension is <= 8 (default 0): the two
+ *                   kernels on one model, or more than 64 leaves at 5 <= n <= 8.
  *   "rts_load_mode": the smoothers' data path: -1 = choose from the layout (default), 0 = strided per-lane loads and
  *                   stores, 2 = LDS-staged time chunks (contiguous reference layout, n <= 4 only).
  *   "ffbs_spl":     samples per lane of the posterior samplers' register kernel (n <= 8): 0 = the smallest compiled count that holds all S
@@ -215,7 +218,7 @@ int bf_user_model_create(const char* dynamics_src, const char* emission_src, int
  * the same handle also compiles the particle-filter kernel with the caller's functions, on first use and per particle
  * capacity (particles in registers up to 4096 for state_dim <= 16 / 1024 beyond; above that the particles-in-HBM kernel, up to
  * 2^20 per trajectory) -- and, likewise on first use, the unscented (bf_ugsf_ukf_f32) and augmented (bf_agsf_ekf_f32 /
- * bf_agsf_ukf_f32) scans and the data generator (bf_sample_ssm_f32) around the same functions (augmented scans: dimensions up to 8; sampler 32).  The density is either Gaussian around the (registry or
+ * bf_agsf_ukf_f32) scans and the data generator (bf_sample_ssm_f32) around the same functions (augmented scans around functions from source: dimensions up to 8 -- registry functions run at any dimension, see bf_agsf_ekf_f32; sampler 32).  The density is either Gaussian around the (registry or
  * source) emission function, MVN(h(x, r_eval, u), lp_cov) as for registry models, or -- log_prob_src -- the caller's own
  *
  *     template <class T> __device__ T log_prob(const T* x, const float* y, T u, const float* theta);   // theta = bf_bpf_model.lp_theta
@@ -268,7 +271,9 @@ int bf_ugsf_ukf_f32(const bf_model* model, const bf_ukf_params* uparams, const b
  * never advanced: the same normals at every step).  The carry holds N0 components per trajectory;
  * out: weights / means / covs with K = N0 (the other streams must be unset).  leaf_idx: optional
  * DEVICE int32 [B][T][N0], the leaf each carried component was drawn from.  N0*N1*N2 <= 64 in general,
- * <= 1024 for state_dim <= 4 (one workgroup per trajectory; every variant).
+ * <= 1024 for state_dim <= 4 (one workgroup per trajectory; every variant) while every dimension is <= 8: a leaf per lane,
+ * in registers.  Any of n, dq, m, dr above 8 (or option "agsf_force_generic" = 1): the node in turn in LDS, N0*N1*N2 <= 256,
+ * registry functions, bounded by the 160 KiB of LDS of a workgroup (BF_EUNSUPPORTED names the bytes needed).
  * variant: 0 = the speedy filter's two shared normal arrays (:672-688, :716-726); 1 = the branches of
  * augmented_gaussian_sum_filter (inference.py:458-620) through containers._branches_from_tree1/2
  * (containers.py:63-140): one key per node, jr.multivariate_normal per node, NaN samples replaced by the mean;
