@@ -145,9 +145,10 @@ int rts_gen_upload(RtsGen& c, GenModel& gg, const std::vector<float>& blk, hipSt
   return BF_OK;
 }
 
-static inline bool rts_ref_stream(const SView& s, long long E, long long T) {
-  return s.p == nullptr || (s.sE == 1 && s.sT == E && s.sB == T * E && (reinterpret_cast<uintptr_t>(s.p) % 16 == 0) &&
-                            (T * E) % 4 == 0);
+// contiguous reference rows of `rows` steps, every row 16-byte aligned
+static inline bool rts_ref_stream(const SView& s, long long E, long long rows) {
+  return s.p == nullptr || (s.sE == 1 && s.sT == E && s.sB == rows * E && (reinterpret_cast<uintptr_t>(s.p) % 16 == 0) &&
+                            (rows * E) % 4 == 0);
 }
 
 static Option g_rts_load_mode{-1, OPT_RTS_LOAD_MODE};
@@ -157,8 +158,11 @@ template <int N, int KIND, class Arg>
 static int launch_rts_n(const Arg& c, const float* d_gqg, const RtsViews& v, long long B, long long T, int load_mode,
                         hipStream_t stream) {
   using S = RtsStage<N>;
+  // without a carry the cross-covariances have T-1 entries: their rows may be T-1 steps long as well as T (the kernel
+  // takes the row pitch from the view and never touches entry T-1; rts_ref_stream's ((T-1) E) % 4 test keeps every row on 16 bytes)
+  const bool cs_ok = rts_ref_stream(v.Cs, N * N, T) || (v.m_in == nullptr && T > 1 && rts_ref_stream(v.Cs, N * N, T - 1));
   bool staged_ok = S::OK && rts_ref_stream(v.m, N, T) && rts_ref_stream(v.P, N * N, T) && rts_ref_stream(v.ms, N, T) &&
-                   rts_ref_stream(v.Ps, N * N, T) && rts_ref_stream(v.Cs, N * N, T);
+                   rts_ref_stream(v.Ps, N * N, T) && cs_ok;
   if (KIND != RTS_LIN_RECOMPUTE) staged_ok = staged_ok && rts_ref_stream(v.pm, N, T) && rts_ref_stream(v.pP, N * N, T);
   if (load_mode == RTS_STAGED && !staged_ok)
     return set_error(BF_EINVAL, "rts_load_mode = 2 needs n <= 4 and the contiguous reference layout with 16-byte aligned rows");

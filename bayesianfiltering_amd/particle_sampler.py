@@ -115,9 +115,13 @@ def particle_posterior_sample(params, filtered, num_samples: int = 1, *, method:
 
     keep = []
     if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise ValueError(f"out must be a torch tensor; got {type(out).__name__}")
         xs = out.unsqueeze(0) if out.dim() == 3 else out
         if tuple(xs.shape) != (B, S, T, n) or xs.dtype != torch.float32 or not xs.is_cuda:
             raise ValueError(f"out has shape {tuple(out.shape)}, expected a float32 device tensor {(B, S, T, n)}")
+        if xs.device != dev:
+            raise ValueError(f"out is on {xs.device}, but the history lives on {dev}: the kernel stores where its history is")
     else:
         xs = torch.empty((B, S, T, n), dtype=torch.float32, device=dev)
     sd = _lib.bf_pf_sample_desc()

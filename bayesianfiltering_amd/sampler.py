@@ -100,9 +100,13 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
 
     keep = []
     if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise ValueError(f"out must be a torch tensor; got {type(out).__name__}")
         xs = out.unsqueeze(0) if out.dim() == 3 else out
         if tuple(xs.shape) != (B, S, T, n) or xs.dtype != torch.float32 or not xs.is_cuda:
             raise ValueError(f"out has shape {tuple(out.shape)}, expected a float32 device tensor {(B, S, T, n)}")
+        if xs.device != dev:
+            raise ValueError(f"out is on {xs.device}, but the posterior lives on {dev}: the kernel stores where its streams are")
     else:
         xs = _alloc_stream((B, S, T), (n,), layout, dev)
     sd = _lib.bf_sample_desc()

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .inference import (_torch, _dev_f32, _host_f32, _fp, _alloc_stream, _stream_desc, _time_varying, _Model,
-                        kalman_filter, gaussian_sum_filter)
+                        _check_out_tensor, kalman_filter, gaussian_sum_filter)
 from .nonlinearities import DYN_LINEAR, require_device_function
 
 
@@ -68,8 +68,11 @@ def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariance
     used it) and need the predicted streams; ``extended=True`` sends a linear model there too.
     ``carry``: the :class:`SmootherCarry` returned (``return_carry=True``) by the smoothing of the steps that FOLLOW
     these (backward chunking); the chunk's last step then gets a cross-covariance too, so the cross-covariances cover
-    all T steps of the chunk instead of T-1.  ``out``: a previous :class:`PosteriorGaussianSmoothed` whose buffers are
-    reused.  Returns :class:`PosteriorGaussianSmoothed` (and the carry when ``return_carry``).
+    all T steps of the chunk instead of T-1.  ``out``: a previous :class:`PosteriorGaussianSmoothed` whose smoothed
+    buffers are reused: float32 tensors on the posterior's device in exactly the shapes this call returns
+    (``smoothed_cross_covariances`` with T-1 steps, T with a carry; giving it asks for the cross-covariances; at T = 1
+    without a carry that is the empty (B, 1, 0, n, n) tensor and nothing is stored into it), anything else is refused
+    before a kernel is launched.  Returns :class:`PosteriorGaussianSmoothed` (and the carry when ``return_carry``).
     """
     torch = _torch()
     f = require_device_function(params.dynamics_function, "dynamics", "params.dynamics_function")
@@ -103,21 +106,32 @@ def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariance
     fd.means, fd.covs = _stream_desc(m_b, 1), _stream_desc(P_b, 2)
     fd.pred_means, fd.pred_covs = _stream_desc(pm_b, 1), _stream_desc(pP_b, 2)
 
-    def buf(name, ev):
+    def buf(name, ev, steps):
+        """out.<name> after the checks a raw-pointer store needs (float32, the streams' device, the exact shape), or None."""
         reuse = getattr(out, name, None) if out is not None else None
-        if reuse is not None:
-            reuse = _batched(reuse, len(ev))
-            if tuple(reuse.shape[:3]) != (B, 1, T) and name != "smoothed_cross_covariances":
-                raise ValueError(f"out.{name} has shape {tuple(reuse.shape)}")
-            return reuse
-        return _alloc_stream((B, 1, T), ev, layout, dev)
+        if reuse is None:
+            return None
+        _check_out_tensor(name, reuse, dev)
+        want = (B, 1, steps) + ev
+        if squeeze and tuple(reuse.shape) == want[1:]:
+            return reuse.unsqueeze(0)
+        if tuple(reuse.shape) != want:
+            raise ValueError(f"out.{name} has shape {tuple(reuse.shape)}, expected {want[1:] if squeeze else want}")
+        return reuse
 
-    ms, Ps = buf("smoothed_means", (n,)), buf("smoothed_covariances", (n, n))
-    Cs = None
-    if cross_covariances:
-        Cs = _alloc_stream((B, 1, T), (n, n), layout, dev)
+    ms, Ps = buf("smoothed_means", (n,), T), buf("smoothed_covariances", (n, n), T)
+    # the cross-covariances a call returns have T-1 steps, T with a carry: that is the shape a given buffer must have
+    c_steps = T if carry is not None else T - 1
+    Cs = buf("smoothed_cross_covariances", (n, n), c_steps)
+    if ms is None:
+        ms = _alloc_stream((B, 1, T), (n,), layout, dev)
+    if Ps is None:
+        Ps = _alloc_stream((B, 1, T), (n, n), layout, dev)
+    if Cs is None and cross_covariances:
+        Cs = _alloc_stream((B, 1, T), (n, n), layout, dev)[:, :, :c_steps]
     sd = _lib.bf_smooth_desc()
-    sd.means, sd.covs, sd.cross_covs = _stream_desc(ms, 1), _stream_desc(Ps, 2), _stream_desc(Cs, 2)
+    # (T = 1 without a carry: the cross-covariances have no step, the kernel is not given the empty stream)
+    sd.means, sd.covs, sd.cross_covs = _stream_desc(ms, 1), _stream_desc(Ps, 2), _stream_desc(Cs if c_steps > 0 else None, 2)
 
     cr = _lib.bf_smooth_carry()
     keep = []
@@ -160,8 +174,6 @@ def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariance
     for t_ in keep:  # buffers made for this call stay allocated until the asynchronous launch has read them
         t_.record_stream(torch.cuda.current_stream(dev))
 
-    if Cs is not None and carry is None:
-        Cs = Cs[:, :, :T - 1]
     sq = (lambda x: x[0] if (squeeze and x is not None) else x)
     post = PosteriorGaussianSmoothed(sq(m_b), sq(P_b), sq(ms), sq(Ps), sq(Cs))
     return (post, c_out) if return_carry else post

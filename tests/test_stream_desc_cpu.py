@@ -2,8 +2,9 @@
 bayesianfiltering_amd/inference.py on CPU tensors.  A kernel addresses element (b, k, t, e) of a stream as
 ``ptr + 4 (b sB + k sK + t sT + e sE)`` with e the row-major index into the event (include/bayesfilt.h: bf_stream), so the
 descriptor of a view is right exactly when that address is the view's own element -- checked here for both layouts, for 0-,
-1- and 2-dimensional events and for the guarded views of tests/test_output_contract_gpu.py, which imports the builders
-below (``SENTINEL_BITS``, ``sentinel_buffer``, ``guarded``) and relies on these descriptors."""
+1- and 2-dimensional events and for the guarded views of tests/test_output_contract_gpu.py and
+tests/test_backward_contract_gpu.py, which import the builders below (``SENTINEL_BITS``, ``sentinel_buffer``, ``guarded``,
+``assert_guards_intact``) and rely on these descriptors."""
 import itertools
 
 import numpy as np
@@ -164,3 +165,42 @@ def test_the_guard_check_sees_a_store_one_row_too_far(geometry):
         else:
             with pytest.raises(AssertionError, match="outside the view overwritten"):
                 assert_guards_intact({"covariances": flat}, {"covariances": carve})
+
+
+def _replay(flat, view, nev, elements):
+    """Store float(e) at every (b, k, t, e) of ``elements`` through the view's descriptor, as a kernel would."""
+    s = inf._stream_desc(view, nev)
+    base = (s.ptr - flat.data_ptr()) // 4
+    for b, k, t, e in elements:
+        flat[base + b * s.sB + k * s.sK + t * s.sT + e * s.sE] = float(e)
+
+
+@pytest.mark.parametrize("geometry", ["slice", "foreign"])
+def test_the_guard_check_sees_a_cross_covariance_in_slot_T_minus_1_and_a_sample_in_slot_S(geometry):
+    """The two stores tests/test_backward_contract_gpu.py must catch, replayed on the CPU.
+    (1) Without a carry the smoother's cross-covariances are a (B, 1, T-1, n, n) view: a kernel that also writes entry T-1
+    (the staged flush of the last time chunk with ``vs`` rows instead of ``vs - 1``) lands on the next trajectory's entry 0,
+    which that trajectory overwrites -- except behind the last trajectory, in the guard rows (slice) -- and in the time
+    padding of every trajectory (foreign).
+    (2) The samples are (B, S, T, n) with the sample axis in the K position: a register sampler whose idle sample slots
+    (ffbs_spl = 8 at S = 5) are not masked writes sample S, the next trajectory's sample 0 (slice) or the guard component
+    behind the view (foreign).  Correct stores pass the same check."""
+    n, B, T, S = 3, 5, 7, 5
+    for steps, ok in ((T - 1, True), (T, False)):
+        numel, carve = guarded(geometry, B, 1, T - 1, (n, n))
+        flat = sentinel_buffer(numel, "cpu")
+        _replay(flat, carve(flat), 2, itertools.product(range(B), range(1), range(steps), range(n * n)))   # trajectories ascending
+        if ok:
+            assert_guards_intact({"cross": flat}, {"cross": carve})
+        else:
+            with pytest.raises(AssertionError, match="outside the view overwritten"):
+                assert_guards_intact({"cross": flat}, {"cross": carve})
+    for slots, ok in ((S, True), (S + 1, False)):
+        numel, carve = guarded(geometry, B, S, T, (n,))
+        flat = sentinel_buffer(numel, "cpu")
+        _replay(flat, carve(flat), 1, itertools.product(range(B), range(slots), range(T), range(n)))
+        if ok:
+            assert_guards_intact({"samples": flat}, {"samples": carve})
+        else:
+            with pytest.raises(AssertionError, match="outside the view overwritten"):
+                assert_guards_intact({"samples": flat}, {"samples": carve})
