@@ -10,8 +10,9 @@ from .inference import (PosteriorGaussianSumFiltered, gaussian_sum_filter, unsce
                         FULL5, FILTERED, PRNGKey, sample_initial_component_means,
                         bootstrap_particle_filter, ParticleCarry, resample_indices)
 from .smoother import (PosteriorGaussianSmoothed, SmootherCarry, rts_smoother, kalman_smoother,
-                       extended_kalman_smoother)
-from .sampler import (SamplerCarry, posterior_sample, kalman_posterior_sample, extended_kalman_posterior_sample)
+                       extended_kalman_smoother, unscented_kalman_smoother)
+from .sampler import (SamplerCarry, posterior_sample, kalman_posterior_sample, extended_kalman_posterior_sample,
+                      unscented_kalman_posterior_sample)
 from .particle_sampler import (ParticleSamplerCarry, particle_posterior_sample, bootstrap_particle_posterior_sample)
 from ._lib import BayesFiltError
 from . import nonlinearities, utils
@@ -20,6 +21,6 @@ __all__ = ["ParamsNLSSM", "ParamsBPF", "NonlinearSSM", "GaussianComponent", "Gau
            "gaussian_sum_filter", "unscented_gaussian_sum_filter", "ParamsUKF", "speedy_augmented_gaussian_sum_filter", "augmented_gaussian_sum_filter", "speedy_unscented_agsf", "unscented_agsf", "augmented_gaussian_sum_filter_optimal", "optimal_resampling", "kalman_filter", "FilterCarry", "FULL5", "FILTERED", "PRNGKey",
            "sample_initial_component_means", "bootstrap_particle_filter", "ParticleCarry", "resample_indices",
            "nonlinearities", "utils", "BayesFiltError",
-           "PosteriorGaussianSmoothed", "SmootherCarry", "rts_smoother", "kalman_smoother", "extended_kalman_smoother",
-           "SamplerCarry", "posterior_sample", "kalman_posterior_sample", "extended_kalman_posterior_sample",
+           "PosteriorGaussianSmoothed", "SmootherCarry", "rts_smoother", "kalman_smoother", "extended_kalman_smoother", "unscented_kalman_smoother",
+           "SamplerCarry", "posterior_sample", "kalman_posterior_sample", "extended_kalman_posterior_sample", "unscented_kalman_posterior_sample",
            "ParticleSamplerCarry", "particle_posterior_sample", "bootstrap_particle_posterior_sample"]

@@ -155,12 +155,18 @@ SYMBOLS = {
                                       C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p]),
     "bf_eks_smoother_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_out_desc), C.c_int64,
                                       C.c_int64, C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p]),
+    "bf_uks_smoother_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_ukf_params), C.POINTER(bf_cstream),
+                                      C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.POINTER(bf_smooth_carry),
+                                      C.POINTER(bf_smooth_desc), C.c_void_p]),
     "bf_sampler_abi_check": (C.c_int, [C.c_size_t, C.c_size_t]),
     "bf_ffbs_sample_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.c_int32,
                                      C.POINTER(bf_sample_carry), C.POINTER(bf_sample_desc), C.c_void_p]),
     "bf_effbs_sample_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_out_desc), C.c_int64,
                                       C.c_int64, C.c_int32, C.POINTER(bf_sample_carry), C.POINTER(bf_sample_desc),
                                       C.c_void_p]),
+    "bf_uffbs_sample_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_ukf_params), C.POINTER(bf_cstream),
+                                      C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.c_int32, C.POINTER(bf_sample_carry),
+                                      C.POINTER(bf_sample_desc), C.c_void_p]),
     "bf_pf_sampler_abi_check": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t]),
     "bf_pf_backward_sample_f32": (C.c_int, [C.POINTER(bf_bpf_model), C.POINTER(bf_cstream), C.POINTER(bf_pf_history), C.c_int64,
                                             C.c_int64, C.c_int32, C.c_int32, C.POINTER(bf_pf_sample_carry),

@@ -59,6 +59,8 @@ int launch_rts_linear(const bf_lgssm* p, const RtsViews& v, long long B, long lo
                       int load_mode, hipStream_t stream);
 int launch_rts_ext(const bf_model* p, const RtsViews& v, long long B, long long T, bool force_generic, int load_mode,
                    hipStream_t stream);
+int launch_rts_unsc(const bf_model* p, const bf_ukf_params* up, const RtsViews& v, long long B, long long T, bool force_generic,
+                    int load_mode, hipStream_t stream);
 int rts_views(const bf_out_desc* f, const bf_smooth_carry* carry, const bf_smooth_desc* out, const bf_cstream* u, long long B,
               long long T, int n, bool need_pred, int (*launch)(const RtsViews&, void*), void* ctx);
 
@@ -437,6 +439,25 @@ int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out
   return bf::rts_views(filtered, carry, out, u, B, T, model->n, true, [](const bf::RtsViews& v, void* c) {
     const Ctx& x = *static_cast<const Ctx*>(c);
     return bf::launch_rts_ext(x.p, v, x.B, x.T, bf::g_force_generic.load() != 0, bf::rts_load_mode_option().load(), x.s);
+  }, &ctx);
+}
+
+int bf_uks_smoother_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* u, const bf_out_desc* filtered,
+                        int64_t B, int64_t T, const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  if (!model || !uparams || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (model->user || model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER)
+    return bf::set_error(BF_EUNSUPPORTED, "the unscented smoother serves registry dynamics; functions given as source are not supported");
+  if (model->flags != 0)
+    return bf::set_error(BF_EUNSUPPORTED, "the unscented smoother needs the JAX path's update -> predict streams (flags = 0)");
+  if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
+  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
+    return bf::set_error(BF_EINVAL, "non-positive model dimension");
+  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
+  struct Ctx { const bf_model* p; const bf_ukf_params* up; long long B, T; hipStream_t s; } ctx{model, uparams, B, T, static_cast<hipStream_t>(stream)};
+  return bf::rts_views(filtered, carry, out, u, B, T, model->n, true, [](const bf::RtsViews& v, void* c) {
+    const Ctx& x = *static_cast<const Ctx*>(c);
+    return bf::launch_rts_unsc(x.p, x.up, v, x.B, x.T, bf::g_force_generic.load() != 0, bf::rts_load_mode_option().load(), x.s);
   }, &ctx);
 }
 

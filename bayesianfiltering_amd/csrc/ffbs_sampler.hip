@@ -16,6 +16,21 @@
 // run-time-dimension kernel: 116 VGPRs, 4 waves per SIMD.  "ffbs_spl" = 0 (default) picks the smallest compiled SPL that holds all S samples
 // of a trajectory in one lane, 8 for S > 8 (S = 5 runs SPL = 8 with three idle slots).  It rests on the one sweep of DESIGN.md
 // 6b (n = 4, B = 65 536, S = 8 and 64): SPL = 8 was the fastest there except in noise mode at S = 64.
+//
+// Unscented route (RTS_UNSC: X_t through rts_linearize, the root and the sigma-point images before the factorization): every
+// instance n = 1 ... 8 at every SPL builds without scratch, so the register limit is 8 for all four counts
+// (ffbs_unsc_reg_max).  VGPRs (arch + acc) / waves per SIMD:
+//   n    SPL = 1    SPL = 2    SPL = 4    SPL = 8
+//   1    72 / 7     101 / 4    145 / 3    102 / 4
+//   2    80 / 6     102 / 4    98 / 4     130 / 3
+//   3    103 / 4    119 / 4    139 / 3    179 / 2
+//   4    160 / 3    178 / 2    202 / 2    250 / 2
+//   5    207 / 2    225 / 2    253 / 2    310 / 1
+//   6    293 / 1    315 / 1    349 / 1    414 / 1
+//   7    360 / 1    380 / 1    408 / 1    469 / 1
+//   8    388 / 1    406 / 1    440 / 1    500 / 1
+// Run-time-dimension kernel: ffbs_generic_kernel<true> 134 VGPRs, 3 waves per SIMD; ffbs_generic_kernel<false> (every other
+// kind) 116 VGPRs, 4 waves, as before the route existed.
 #include "ffbs_sampler.hpp"
 #include "rts_generic.hpp"
 
@@ -23,7 +38,8 @@ namespace bf {
 
 // ---- run-time-dimension kernel -----------------------------------------------------------------------------------
 // One 64-lane workgroup per trajectory.  LDS: five n x ld matrices (P, P-, X, W, Sg), three vectors and three sample
-// buffers of SB x n (state x, noise xi, result).  Per step, with the smoother's helpers (rts_generic.hpp): W <- F_t,
+// buffers of SB x n (state x, noise xi, result); RTS_UNSC: one more matrix (the root Rt) and the root's vectors -- its
+// iterate, Newton scratch and eigenvectors alias W, X and Sg, dead until the solve -- which bounds the route at n <= 81.  Per step, with the smoother's helpers (rts_generic.hpp): W <- F_t,
 // X = F P, [recompute: P-, m-], W <- chol(P-), X <- L^-1 X, then Sg = P - X^T X (lower triangle), X <- L^-T X,
 // Sg <- psdchol(Sg; diag P) in place, then the samples in blocks of SB: lanes split over (sample, row) in
 // x = m + X^T (x+ - m-) + Sg xi.  With one block the state stays in LDS from step to step; with more, a block's x+ is read
@@ -33,8 +49,15 @@ struct FfbsGen {
   int S, SB;            // samples, samples per LDS block
 };
 
-static inline size_t ffbs_gen_mat_floats(int n) { return 5 * (size_t)n * rts_gen_ld(n) + 3 * (size_t)n; }
+// RTS_UNSC: one more matrix (the root; Sg holds the eigenvectors while it is taken) and the root's vectors (rts_generic.hpp)
+static inline size_t ffbs_gen_unsc_floats(int n, int kind) {
+  return kind == RTS_UNSC ? (size_t)n * rts_gen_ld(n) + (size_t)rts_unsc_vec_floats(n) : 0;
+}
+static inline size_t ffbs_gen_mat_floats(int n, int kind) {
+  return 5 * (size_t)n * rts_gen_ld(n) + 3 * (size_t)n + ffbs_gen_unsc_floats(n, kind);
+}
 
+template <bool UNSC>
 __global__ void __launch_bounds__(64) ffbs_generic_kernel(FfbsGen fc, GenModel g, FfbsViews v, long long T) {
   const RtsGen& c = fc.r;
   const int tid = threadIdx.x;
@@ -49,7 +72,8 @@ __global__ void __launch_bounds__(64) ffbs_generic_kernel(FfbsGen fc, GenModel g
   float* m = Sg + n * ld;
   float* mp = m + n;
   float* tv = mp + n;
-  float* xs = tv + n;        // x_{t+1} of the block, then x_{t+1} - m-
+  const RtsUnscLds ul = rts_unsc_carve(Sg, tv + n, tv + n + n * ld, n);  // carved for RTS_UNSC only
+  float* xs = tv + n + (UNSC ? n * ld + rts_unsc_vec_floats(n) : 0);  // x_{t+1} of the block, then x_{t+1} - m-
   float* xi = xs + SB * n;   // the block's noise
   float* xo = xi + SB * n;   // x_t of the block
   const bool one_block = SB >= S;
@@ -146,8 +170,8 @@ __global__ void __launch_bounds__(64) ffbs_generic_kernel(FfbsGen fc, GenModel g
       for (int e = tid; e < nn; e += 64) Pp[(e / n) * ld + e % n] = v.pP.p[at(v.pP, t, e)];
     }
     wave_lds_sync();
-    const float u0 = (c.kind == RTS_EXT && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
-    rts_gen_linearize(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid);
+    const float u0 = ((UNSC || c.kind == RTS_EXT) && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+    rts_gen_linearize<UNSC>(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid, ul);
     rts_gen_chol(n, Pp, W, tid);
     rts_gen_solve_lower(n, W, X, tid);  // X <- L^-1 X
     wave_lds_sync();
@@ -170,6 +194,10 @@ __global__ void __launch_bounds__(64) ffbs_generic_kernel(FfbsGen fc, GenModel g
 static Option g_ffbs_spl{0, OPT_FFBS_SPL};
 Option& ffbs_spl_option() { return g_ffbs_spl; }
 
+// Largest n of the unscented route on the register kernel for a samples-per-lane count: every instance up to it builds
+// without scratch (header comment).  All four counts reach n = 8.
+constexpr int ffbs_unsc_reg_max(int /* spl */) { return 8; }
+
 // the smallest compiled count that holds all S samples of a trajectory in one lane, 8 for S > 8 (header comment)
 static int ffbs_pick_spl(int S, int forced) {
   if (forced) return forced;
@@ -185,11 +213,17 @@ static int launch_ffbs_n(const Arg& c, const float* d_gqg, const FfbsViews& v, l
   const long long lanes = B * ((S + spl - 1) / spl);
   if ((lanes + 63) / 64 > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B x S too large for one launch");
   const dim3 grid((unsigned)((lanes + 63) / 64));
+  // an unscented instance exists only up to its SPL's limit (ffbs_unsc_reg_max; the host sends the rest to the other kernel)
+  auto go = [&](auto SC) {
+    constexpr int SPL = decltype(SC)::value;
+    if constexpr (KIND != RTS_UNSC || N <= ffbs_unsc_reg_max(SPL))
+      hipLaunchKernelGGL((ffbs_reg_kernel<N, SPL, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S);
+  };
   switch (spl) {
-    case 1: hipLaunchKernelGGL((ffbs_reg_kernel<N, 1, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S); break;
-    case 2: hipLaunchKernelGGL((ffbs_reg_kernel<N, 2, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S); break;
-    case 4: hipLaunchKernelGGL((ffbs_reg_kernel<N, 4, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S); break;
-    default: hipLaunchKernelGGL((ffbs_reg_kernel<N, 8, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S); break;
+    case 1: go(std::integral_constant<int, 1>{}); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    case 4: go(std::integral_constant<int, 4>{}); break;
+    default: go(std::integral_constant<int, 8>{}); break;
   }
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;
@@ -199,10 +233,11 @@ static int launch_ffbs_generic(const FfbsGen& c0, const GenModel& g, const std::
                                long long B, long long T, hipStream_t stream) {
   const size_t cap = 160 * 1024 / sizeof(float);
   const int n = c0.r.n;
-  const size_t mat = ffbs_gen_mat_floats(n);
+  const int kind = c0.r.kind;
+  const size_t mat = ffbs_gen_mat_floats(n, kind);
   if (mat + 3 * (size_t)n > cap) {
     int nmax = 1;
-    while (ffbs_gen_mat_floats(nmax + 1) + 3 * (size_t)(nmax + 1) <= cap) ++nmax;
+    while (ffbs_gen_mat_floats(nmax + 1, kind) + 3 * (size_t)(nmax + 1) <= cap) ++nmax;
     return set_error(BF_EUNSUPPORTED, "sampler: n = %d needs %zu bytes of LDS (160 KiB per workgroup: n <= %d)", n,
                      sizeof(float) * (mat + 3 * (size_t)n), nmax);
   }
@@ -218,8 +253,9 @@ static int launch_ffbs_generic(const FfbsGen& c0, const GenModel& g, const std::
   const int rc = rts_gen_upload(c.r, gg, blk, stream);
   if (rc != BF_OK) return rc;
   if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B too large for the run-time-dimension kernel");
-  if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ffbs_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(ffbs_generic_kernel, dim3((unsigned)B), dim3(64), lds, stream, c, gg, v, T);
+  auto kern = kind == RTS_UNSC ? ffbs_generic_kernel<true> : ffbs_generic_kernel<false>;
+  if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), lds, stream, c, gg, v, T);
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;
 }
@@ -278,6 +314,29 @@ static int launch_ffbs_ext(const bf_model* p, const FfbsViews& v, long long B, l
   return launch_ffbs_generic(c, g, blk, v, B, T, stream);
 }
 
+static int launch_ffbs_unsc(const bf_model* p, const bf_ukf_params* up, const FfbsViews& v, long long B, long long T, int S,
+                            bool force_generic, int spl, hipStream_t stream) {
+  RtsUnscHost h;
+  int rc = rts_unsc_fill(p, up, h);
+  if (rc != BF_OK) return rc;
+  const int n = p->n;
+  if (!force_generic && n <= ffbs_unsc_reg_max(ffbs_pick_spl(S, spl))) {
+    auto go = [&](auto NC) -> int {
+      constexpr int N = decltype(NC)::value;
+      return launch_ffbs_n<N, RTS_UNSC>(rts_unsc_arg<N>(h), nullptr, v, B, T, S, spl, stream);
+    };
+    BF_RTS_DIMS(n, go)
+  }
+  FfbsGen c;
+  std::memset(&c, 0, sizeof(c));
+  std::vector<float> blk;
+  if ((rc = rts_gen_unsc_block(h, n, c.r, blk)) != BF_OK) return rc;
+  c.S = S;
+  GenModel g;
+  std::memset(&g, 0, sizeof(g));
+  return launch_ffbs_generic(c, g, blk, v, B, T, stream);
+}
+
 // bf_out_desc / bf_sample_carry / bf_sample_desc -> FfbsViews, with the checks both entry points share
 static int ffbs_views(const bf_out_desc* f, const bf_sample_carry* carry, const bf_sample_desc* out, const bf_cstream* u,
                       long long B, long long T, int S, int n, bool need_pred, FfbsViews& v) {
@@ -286,7 +345,7 @@ static int ffbs_views(const bf_out_desc* f, const bf_sample_carry* carry, const 
   if (!f->means.ptr || !f->covs.ptr) return set_error(BF_EINVAL, "filtered means and covariances are required");
   const bool has_pm = f->pred_means.ptr != nullptr, has_pP = f->pred_covs.ptr != nullptr;
   if (has_pm != has_pP) return set_error(BF_EINVAL, "pred_means and pred_covs are given together or not at all");
-  if (need_pred && !has_pm) return set_error(BF_EINVAL, "the extended sampler needs the predicted means and covariances");
+  if (need_pred && !has_pm) return set_error(BF_EINVAL, "the extended and the unscented sampler need the predicted means and covariances");
   if (!out->samples.ptr) return set_error(BF_EINVAL, "the samples stream is a required output");
   if (!out->noise.ptr && !out->keys) return set_error(BF_EINVAL, "give the noise stream or the keys");
   if (!out->noise.ptr && (long long)S * T * n > 0x7fffffffLL)
@@ -376,6 +435,25 @@ int bf_effbs_sample_f32(const bf_model* model, const bf_cstream* u, const bf_out
   int spl;
   if ((rc = bf::ffbs_spl_checked(&spl)) != BF_OK) return rc;
   return bf::launch_ffbs_ext(model, v, B, T, S, bf::force_generic_option().load() != 0, spl, static_cast<hipStream_t>(stream));
+}
+
+int bf_uffbs_sample_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* u, const bf_out_desc* filtered,
+                        int64_t B, int64_t T, int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  if (!model || !uparams || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (model->user || model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER)
+    return bf::set_error(BF_EUNSUPPORTED, "the unscented sampler serves registry dynamics; functions given as source are not supported");
+  if (model->flags != 0)
+    return bf::set_error(BF_EUNSUPPORTED, "the unscented sampler needs the JAX path's update -> predict streams (flags = 0)");
+  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
+    return bf::set_error(BF_EINVAL, "non-positive model dimension");
+  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
+  bf::FfbsViews v;
+  int rc = bf::ffbs_views(filtered, carry, out, u, B, T, S, model->n, true, v);
+  if (rc != BF_OK) return rc;
+  int spl;
+  if ((rc = bf::ffbs_spl_checked(&spl)) != BF_OK) return rc;
+  return bf::launch_ffbs_unsc(model, uparams, v, B, T, S, bf::force_generic_option().load() != 0, spl, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -6,26 +6,119 @@
 #include <vector>
 #include "rts_smoother.hpp"
 #include "generic_device.hpp"
+#include "ugsf_generic_device.hpp"
 
 namespace bf {
 
 struct RtsGen {
-  int n, kind;          // RTS_LIN, RTS_LIN_RECOMPUTE, RTS_EXT
-  const float* A;       // [n][n]            (linear kinds)
+  int n, kind;          // RTS_LIN, RTS_LIN_RECOMPUTE, RTS_EXT, RTS_UNSC
+  const float* A;       // [n][n]            (linear kinds; RTS_UNSC: linear dynamics)
   const float* GQG;     // [q_steps][n][n]   (recompute)
-  const float* Gq0;     // [n]               (recompute)
+  const float* Gq0;     // [n]               (recompute; RTS_UNSC: F_q q0)
   int q_tv;
+  // RTS_UNSC: the registry dynamics and the prediction's unscented constants c = sqrt(L + lambda), w = 1 / (2 (L + lambda))
+  int dyn_id;
+  float dth[8];
+  float cu, wu;
 };
 
 __host__ __device__ inline int rts_gen_ld(int n) { return n + 1; }
 
+// RTS_UNSC on the run-time-dimension kernels: LDS of the symmetric square root (ug_sym_sqrt) beyond what the kernels own.
+// Its iterate lives in W, its Newton scratch in X (both are outputs of the step's linearisation, dead until then); the
+// eigenvectors V and the root Rt are n x ld matrices of the caller's (the sampler lends Sg as V); the vectors follow.
+struct RtsUnscLds {
+  float *V, *Rt, *sd, *red, *rot;
+};
+__host__ __device__ inline int rts_unsc_vec_floats(int n) {
+  const int nv = (n + 3) & ~3, h4 = (((n + 1) >> 1) + 3) & ~3;
+  return 3 * nv + 4 * h4;  // sd [nv], red [2][nv], rot [ceil(n / 2)][4]
+}
+__host__ __device__ inline RtsUnscLds rts_unsc_carve(float* V, float* Rt, float* vec, int n) {
+  const int nv = (n + 3) & ~3;
+  return RtsUnscLds{V, Rt, vec, vec + nv, vec + 3 * nv};
+}
+
 #ifdef __HIPCC__
+// The differences of the images of the n sigma-point pairs, D[j][k] = f_k(m + s_j, q0, u) - f_k(m - s_j, q0, u) with
+// s_j = cu Rt[j, :] (pitch ld).  Linear, Lorenz-96 and sine dynamics: one work item per (pair, output row), the formulas and
+// the per-entry operation order of ug_eval_dyn, whose points these are.  The registry functions of one fixed dimension
+// (Lorenz-63, manoeuvring target, growth): a lane per pair, the point in registers (dyn_base_t).
+template <int N>
+__device__ __forceinline__ void rts_gen_unsc_pair(const RtsGen& c, float u0, const float* m, const float* row, float* Drow) {
+#pragma clang fp contract(off)
+  float xp[N], xm[N], fp[N], fm[N];
+  BF_UNROLL for (int k = 0; k < N; ++k) {
+    xp[k] = m[k] + c.cu * row[k];
+    xm[k] = m[k] + (-c.cu) * row[k];
+  }
+  dyn_base_t<N, N, RtsGen>(c, xp, u0, fp);
+  dyn_base_t<N, N, RtsGen>(c, xm, u0, fm);
+  BF_UNROLL for (int k = 0; k < N; ++k) Drow[k] = (fp[k] + c.Gq0[k]) - (fm[k] + c.Gq0[k]);
+}
+__device__ __forceinline__ void rts_gen_unsc_images(const RtsGen& c, float u0, const float* m, const float* Rt, int ld, float* D,
+                                                    int tid) {
+#pragma clang fp contract(off)
+  const int n = c.n;
+  if (c.dyn_id == DYN_LORENZ63 || c.dyn_id == DYN_MANEUVER_BOT || c.dyn_id == DYN_GROWTH) {
+    if (tid < n) {
+      if (c.dyn_id == DYN_LORENZ63) rts_gen_unsc_pair<3>(c, u0, m, Rt + tid * ld, D + tid * ld);
+      else if (c.dyn_id == DYN_MANEUVER_BOT) rts_gen_unsc_pair<4>(c, u0, m, Rt + tid * ld, D + tid * ld);
+      else rts_gen_unsc_pair<1>(c, u0, m, Rt + tid * ld, D + tid * ld);
+    }
+    return;
+  }
+  for (int e = tid; e < n * n; e += 64) {
+    const int j = e / n, i = e - j * n;
+    const float* row = Rt + j * ld;
+    float o[2];
+    for (int sg = 0; sg < 2; ++sg) {
+      const float cs = sg == 0 ? c.cu : -c.cu;
+      auto X = [&](int k) { return m[k] + cs * row[k]; };
+      float v;
+      if (c.dyn_id == DYN_LINEAR) {
+        float s = c.A[i * n] * X(0);
+        for (int k = 1; k < n; ++k) s = fmaf(c.A[i * n + k], X(k), s);
+        v = s + c.Gq0[i];
+      } else if (c.dyn_id == DYN_LORENZ96) {
+        const float alpha = c.dth[0], beta = c.dth[1], gamma = c.dth[2], dt = c.dth[3];
+        const float xi = X(i), ax = X((i + n - 1) % n);
+        const float bx = (c.dth[4] != 0.f) ? (X((i + 1) % n) - X((i + 2 * n - 2) % n)) : 0.f;
+        v = xi + dt * (alpha * (ax * bx) - beta * xi + gamma);
+        v += c.Gq0[i];
+      } else {  // DYN_SINE
+        v = sinf(c.dth[0] * X(i));
+        v += c.Gq0[i];
+      }
+      o[sg] = v;
+    }
+    D[j * ld + i] = o[0] - o[1];
+  }
+}
+
 // W <- F_t (registry dynamics; linear: A is read from the constant block), X = F P, [recompute: P- = X F^T + GQG_t,
 // m- = F m + G q0].  One 64-lane wave; m, P (and, unless recomputed, m-, P-) are in LDS and synchronised on entry; X
-// (and P-, m-) are synchronised on return.
+// (and P-, m-) are synchronised on return.  RTS_UNSC: X = X_t of rts_smoother.hpp's contract instead -- Rt <- the root of P
+// (ug_sym_sqrt, the filter's, Newton step included), W <- the image differences, X = w W^T (c Rt) as an LDS product.
+// UNSC is a template parameter: the kernels of the other kinds carry none of the root's code or registers.
+template <bool UNSC>
 __device__ __forceinline__ void rts_gen_linearize(const RtsGen& c, const GenModel& g, float u0, long long t, const float* m,
-                                                  const float* P, float* mp, float* Pp, float* X, float* W, float* tv, int tid) {
+                                                  const float* P, float* mp, float* Pp, float* X, float* W, float* tv, int tid,
+                                                  const RtsUnscLds& ul) {
   const int n = c.n, ld = rts_gen_ld(n), nn = n * n;
+  if constexpr (UNSC) {
+    ug_sym_sqrt<64>(P, ld, W, ul.V, ul.Rt, X, ld, ul.sd, ul.red, ul.rot, n, tid);
+    rts_gen_unsc_images(c, u0, m, ul.Rt, ld, W, tid);
+    wave_lds_sync();
+    for (int e = tid; e < nn; e += 64) {  // X[k][i] = w sum_j D[j][k] s_j[i]
+      const int k = e / n, i = e - k * n;
+      float s = W[k] * (c.cu * ul.Rt[i]);
+      for (int j = 1; j < n; ++j) s = fmaf(W[j * ld + k], c.cu * ul.Rt[j * ld + i], s);
+      X[k * ld + i] = s * c.wu;
+    }
+    wave_lds_sync();
+    return;
+  }
   const float* F;
   int ldf;
   if (c.kind == RTS_EXT) {
@@ -110,7 +203,30 @@ void rts_lin_fill(const bf_lgssm* p, std::vector<float>& A, std::vector<float>& 
 // the linear kinds' constant block A | Gq0 | GQG[qs], with c's pointers as offsets into it
 void rts_gen_lin_block(const bf_lgssm* p, bool recompute, const std::vector<float>& A, const std::vector<float>& GQG,
                        const std::vector<float>& Gq0, RtsGen& c, std::vector<float>& blk);
-// uploads blk (content-keyed cache) and turns the offsets of c (linear kinds) or g (RTS_EXT) into device pointers
+// The unscented route's model on the host: the filter's own model fill (ugsf_scan.hpp: fill_ukf_model_view validates the
+// registry ids and forms the constants), reduced to what X_t reads.  BF_EINVAL for ParamsUKF values with L + lambda <= 0.
+struct RtsUnscHost {
+  int dyn_id;
+  float dth[8];
+  std::vector<float> A, Gq0;
+  float cu, wu;
+};
+int rts_unsc_fill(const bf_model* p, const bf_ukf_params* up, RtsUnscHost& h);
+// the run-time-dimension kernels' constant block A | Gq0 and c for RTS_UNSC; BF_EUNSUPPORTED for dynamics they do not hold
+int rts_gen_unsc_block(const RtsUnscHost& h, int n, RtsGen& c, std::vector<float>& blk);
+template <int N>
+inline RtsUnsc<N> rts_unsc_arg(const RtsUnscHost& h) {
+  RtsUnsc<N> c;
+  std::memset(&c, 0, sizeof(c));
+  c.dyn_id = h.dyn_id;
+  for (int i = 0; i < 8; ++i) c.dth[i] = h.dth[i];
+  std::memcpy(c.A, h.A.data(), sizeof(c.A));
+  std::memcpy(c.Gq0, h.Gq0.data(), sizeof(c.Gq0));
+  c.c = h.cu;
+  c.w = h.wu;
+  return c;
+}
+// uploads blk (content-keyed cache) and turns the offsets of c (linear kinds, RTS_UNSC) or g (RTS_EXT) into device pointers
 int rts_gen_upload(RtsGen& c, GenModel& g, const std::vector<float>& blk, hipStream_t stream);
 
 template <int N>

@@ -7,17 +7,31 @@
 // n x n matrices of a step plus the carry spill into the accumulation registers, not to memory).  Staged path (n <= 4,
 // plus the chunk's prefetch registers): n = 1: 76-114 / 4-6, n = 2: 125-180 / 2-4, n = 3: 261-357 / 1, n = 4: 255-343 / 1-2.
 // The run-time-dimension kernel serves n > 8 and "force_generic" = 1.
+//
+// Unscented route (RTS_UNSC: sym_sqrt<N> and the 2 n sigma-point images before the step; strided path only -- the route is
+// bound by the root's arithmetic, not by its loads).  The predictions are loaded after the root, when its 2 n^2 registers
+// are free again; with that every instance n = 1 ... 8 builds without scratch, so the register limit is 8 (RTS_UNSC_REG_MAX).
+// VGPRs (arch + acc) / waves per SIMD: n = 1: 35 / 8, n = 2: 62 / 8, n = 3: 105 / 4, n = 4: 170 / 2, n = 5: 235 / 2,
+// n = 6: 346 / 1, n = 7: 447 / 1, n = 8: 496 / 1.  Run-time-dimension kernel: rts_generic_kernel<true> 130 VGPRs, 3 waves per
+// SIMD; rts_generic_kernel<false> (every other kind) 112 VGPRs, 4 waves, as before the route existed.
 #include "rts_generic.hpp"
 #include "lgssm_pack.hpp"
 
 namespace bf {
 
 // ---- run-time-dimension kernel -----------------------------------------------------------------------------------
-// One 64-lane workgroup per trajectory.  LDS: five n x ld matrices (P, P^s, P-, X, W) and four vectors.  Per step, with
+// One 64-lane workgroup per trajectory.  LDS: five n x ld matrices (P, P^s, P-, X, W) and four vectors; RTS_UNSC: two more
+// matrices (V, Rt) and the root's vectors -- the root's iterate and its Newton scratch alias W and X, dead until the solve --
+// which bounds the route at n <= 75 in 160 KiB (the host computes it from rts_gen_lds_floats).  Per step, with
 // the helpers of rts_generic.hpp: W <- F_t, X = F P, [recompute: P-, m-], W <- chol(P-), X <- L^-T L^-1 X,
 // C = X^T P^s (straight to HBM), m^s <- m + X^T (m^s - m-), P^s <- P^s - P-, P- <- X^T (P^s), P <- P + P- X, swap P / P^s.
-static inline size_t rts_gen_lds_floats(int n) { return 5 * (size_t)n * rts_gen_ld(n) + 4 * (size_t)n; }
+// RTS_UNSC: two more matrices (the root's eigenvectors and the root) and the root's vectors (rts_generic.hpp: RtsUnscLds)
+static inline size_t rts_gen_lds_floats(int n, int kind) {
+  const size_t base = 5 * (size_t)n * rts_gen_ld(n) + 4 * (size_t)n;
+  return kind == RTS_UNSC ? base + 2 * (size_t)n * rts_gen_ld(n) + (size_t)rts_unsc_vec_floats(n) : base;
+}
 
+template <bool UNSC>
 __global__ void __launch_bounds__(64) rts_generic_kernel(RtsGen c, GenModel g, RtsViews v, long long T) {
   const int tid = threadIdx.x;
   const long long b = blockIdx.x;
@@ -32,6 +46,7 @@ __global__ void __launch_bounds__(64) rts_generic_kernel(RtsGen c, GenModel g, R
   float* ms = m + n;
   float* mp = ms + n;
   float* tv = mp + n;
+  const RtsUnscLds ul = rts_unsc_carve(tv + n, tv + n + n * ld, tv + n + 2 * n * ld, n);  // carved for RTS_UNSC only
   const bool want_c = v.Cs.p != nullptr;
   auto at = [&](const SView& s, long long t, int e) { return b * s.sB + t * s.sT + e * s.sE; };
 
@@ -53,8 +68,8 @@ __global__ void __launch_bounds__(64) rts_generic_kernel(RtsGen c, GenModel g, R
       for (int e = tid; e < nn; e += 64) Pp[(e / n) * ld + e % n] = v.pP.p[at(v.pP, t, e)];
     }
     wave_lds_sync();
-    const float u0 = (c.kind == RTS_EXT && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
-    rts_gen_linearize(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid);
+    const float u0 = ((UNSC || c.kind == RTS_EXT) && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+    rts_gen_linearize<UNSC>(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid, ul);
     rts_gen_chol(n, Pp, W, tid);
     rts_gen_solve_lower(n, W, X, tid);  // X <- L^-T L^-1 X
     rts_gen_solve_upper(n, W, X, tid);
@@ -128,6 +143,56 @@ void rts_gen_lin_block(const bf_lgssm* p, bool recompute, const std::vector<floa
   c.Gq0 = reinterpret_cast<const float*>((size_t)n * n);
   c.GQG = reinterpret_cast<const float*>((size_t)n * n + n);
   c.q_tv = p->Q_steps > 1;
+  c.dyn_id = 0;
+  for (int i = 0; i < 8; ++i) c.dth[i] = 0.f;
+  c.cu = c.wu = 0.f;
+}
+
+int rts_unsc_fill(const bf_model* p, const bf_ukf_params* up, RtsUnscHost& h) {
+  const int n = p->n, dq = p->dq;
+  if (!(up->alpha > 0.f)) return set_error(BF_EINVAL, "ParamsUKF.alpha must be positive");
+  bf_model q = *p;
+  q.Q_steps = q.R_steps = 1;  // the noise covariances never enter X_t; the fill reads their first matrices only
+  std::vector<uint32_t> words(ukf_model_words(n, dq, p->m, p->dr), 0u);
+  const UkfModelView e = ukf_model_view_flat(words.data(), n, dq, p->m, p->dr);
+  const int rc = fill_ukf_model_view(&q, up, e, 0);
+  if (rc != BF_OK) return rc;
+  h.cu = e.cp[0];
+  h.wu = e.cp[1];
+  if (!(h.cu > 0.f) || !std::isfinite(h.cu) || !std::isfinite(h.wu))
+    return set_error(BF_EINVAL, "ParamsUKF: L + lambda = alpha^2 (n + dq + kappa) must be positive and finite (alpha = %g, kappa = %g, n + dq = %d)",
+                     (double)up->alpha, (double)up->kappa, n + dq);
+  h.dyn_id = p->dyn_id;
+  for (int i = 0; i < 8; ++i) h.dth[i] = e.dth[i];
+  h.A.assign(e.A, e.A + (size_t)n * n);
+  h.Gq0.assign(n, 0.f);
+  for (int i = 0; i < n; ++i) {  // F_q q0 as ukf_dyn adds it
+    if (*e.g_identity) {
+      h.Gq0[i] = e.q0[i];
+    } else {
+      float s = 0.f;
+      for (int k = 0; k < dq; ++k) s = std::fmaf(e.Gm[i * dq + k], e.q0[k], s);
+      h.Gq0[i] = s;
+    }
+  }
+  return BF_OK;
+}
+
+int rts_gen_unsc_block(const RtsUnscHost& h, int n, RtsGen& c, std::vector<float>& blk) {
+  std::memset(&c, 0, sizeof(c));
+  blk.clear();
+  blk.insert(blk.end(), h.A.begin(), h.A.end());
+  blk.insert(blk.end(), h.Gq0.begin(), h.Gq0.end());
+  c.n = n;
+  c.kind = RTS_UNSC;
+  c.A = reinterpret_cast<const float*>((size_t)0);
+  c.Gq0 = reinterpret_cast<const float*>((size_t)n * n);
+  c.GQG = reinterpret_cast<const float*>((size_t)0);
+  c.dyn_id = h.dyn_id;
+  for (int i = 0; i < 8; ++i) c.dth[i] = h.dth[i];
+  c.cu = h.cu;
+  c.wu = h.wu;
+  return BF_OK;
 }
 
 int rts_gen_upload(RtsGen& c, GenModel& gg, const std::vector<float>& blk, hipStream_t stream) {
@@ -178,7 +243,7 @@ static int launch_rts_n(const Arg& c, const float* d_gqg, const RtsViews& v, lon
     return w;
   };
   long long b_main = 0;
-  if constexpr (S::OK) {
+  if constexpr (S::OK && KIND != RTS_UNSC) {  // (the unscented route is compute-bound: strided loads only)
     if (staged) {
       // the staged kernel takes whole waves; a ragged remainder goes through the strided one
       b_main = (B / 64) * 64;
@@ -197,16 +262,23 @@ static int launch_rts_n(const Arg& c, const float* d_gqg, const RtsViews& v, lon
 
 static int launch_rts_generic(const RtsGen& c0, const GenModel& g, const std::vector<float>& blk, const RtsViews& v,
                               long long B, long long T, hipStream_t stream) {
-  const size_t lds = sizeof(float) * rts_gen_lds_floats(c0.n);
-  if (lds > 160 * 1024)
+  const size_t lds = sizeof(float) * rts_gen_lds_floats(c0.n, c0.kind);
+  if (lds > 160 * 1024) {
+    if (c0.kind == RTS_UNSC) {
+      int nmax = 1;
+      while (sizeof(float) * rts_gen_lds_floats(nmax + 1, RTS_UNSC) <= 160 * 1024) ++nmax;
+      return set_error(BF_EUNSUPPORTED, "unscented smoother: n = %d needs %zu bytes of LDS (160 KiB per workgroup: n <= %d)", c0.n, lds, nmax);
+    }
     return set_error(BF_EUNSUPPORTED, "smoother: n = %d needs %zu bytes of LDS (160 KiB per workgroup)", c0.n, lds);
+  }
   RtsGen c = c0;
   GenModel gg = g;
   const int rc = rts_gen_upload(c, gg, blk, stream);
   if (rc != BF_OK) return rc;
   if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "smoother: B too large for the run-time-dimension kernel");
-  if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(rts_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(rts_generic_kernel, dim3((unsigned)B), dim3(64), lds, stream, c, gg, v, T);
+  auto kern = c.kind == RTS_UNSC ? rts_generic_kernel<true> : rts_generic_kernel<false>;
+  if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), lds, stream, c, gg, v, T);
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;
 }
@@ -264,6 +336,32 @@ int launch_rts_ext(const bf_model* p, const RtsViews& v, long long B, long long 
   return launch_rts_generic(c, g, blk, v, B, T, stream);
 }
 
+// Largest n of the unscented route on the register kernel: every instance up to it builds without scratch (header comment)
+enum { RTS_UNSC_REG_MAX = 8 };
+
+int launch_rts_unsc(const bf_model* p, const bf_ukf_params* up, const RtsViews& v, long long B, long long T, bool force_generic,
+                    int load_mode, hipStream_t stream) {
+  RtsUnscHost h;
+  int rc = rts_unsc_fill(p, up, h);
+  if (rc != BF_OK) return rc;
+  const int n = p->n;
+  if (load_mode == RTS_STAGED) return set_error(BF_EINVAL, "rts_load_mode = 2 is not offered on the unscented route");
+  if (!force_generic && n <= RTS_UNSC_REG_MAX) {
+    auto go = [&](auto NC) -> int {
+      constexpr int N = decltype(NC)::value;
+      if constexpr (N <= RTS_UNSC_REG_MAX) return launch_rts_n<N, RTS_UNSC>(rts_unsc_arg<N>(h), nullptr, v, B, T, RTS_STRIDED, stream);
+      else return set_error(BF_EUNSUPPORTED, "no register instance");
+    };
+    BF_RTS_DIMS(n, go)
+  }
+  RtsGen c;
+  std::vector<float> blk;
+  if ((rc = rts_gen_unsc_block(h, n, c, blk)) != BF_OK) return rc;
+  GenModel g;
+  std::memset(&g, 0, sizeof(g));
+  return launch_rts_generic(c, g, blk, v, B, T, stream);
+}
+
 }  // namespace bf
 
 namespace bf {
@@ -273,7 +371,7 @@ int rts_views(const bf_out_desc* f, const bf_smooth_carry* carry, const bf_smoot
               long long T, int n, bool need_pred, int (*launch)(const RtsViews&, void*), void* ctx) {
   if (!f->means.ptr || !f->covs.ptr) return set_error(BF_EINVAL, "filtered means and covariances are required");
   if (need_pred && (!f->pred_means.ptr || !f->pred_covs.ptr))
-    return set_error(BF_EINVAL, "the extended smoother needs the predicted means and covariances");
+    return set_error(BF_EINVAL, "the extended and the unscented smoother need the predicted means and covariances");
   if (!out->means.ptr || !out->covs.ptr) return set_error(BF_EINVAL, "smoothed means and covariances are required outputs");
   if (carry && ((carry->m_in == nullptr) != (carry->P_in == nullptr)))
     return set_error(BF_EINVAL, "carry.m_in and carry.P_in are given together or not at all");

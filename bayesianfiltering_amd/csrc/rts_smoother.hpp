@@ -11,6 +11,19 @@
 //                        C_t  = G_t P^s_{t+1}                                   (optional lag-one cross-covariance)
 // A P- that is not positive definite gives NaN (sqrt of a negative pivot) from that step backwards.
 //
+// Unscented route (RTS_UNSC; bf_uks_smoother_f32, bf_uffbs_sample_f32).  Inputs are the streams of bf_ugsf_ukf_f32 with
+// K = 1 (update -> predict order): filtered m_t, P_t and the predictions m-_{t+1}, P-_{t+1} at index t, all required.  With
+// L = n + dq, lambda = alpha^2 (L + kappa) - L, c = sqrt(L + lambda) and w = 1 / (2 (L + lambda)) (UkfModel's c_p, ws_p):
+//   R_t = symmetric square root of P_t (eigenvalues clamped at 0): the root the filter's predict formed at step t --
+//         sym_sqrt<N> (ugsf_scan.hpp) here, ug_sym_sqrt with its Newton step on the run-time-dimension kernel (lower triangle read)
+//   s_j = c R_t[j, :],  j = 0 ... n-1
+//   X_t = w sum_j ( f(m_t + s_j, q0, u_t) - f(m_t - s_j, q0, u_t) ) s_j^T            (X[k][i] = Cov(x_{t+1,k}, x_{t,i} | y_{1:t}))
+// replaces F_t P_t; everything after it (the Cholesky of P-_{t+1}, G_t, m^s, P^s, C_t, the sampler's recursion) is unchanged.
+// The sigma points that perturb only the noise have zero state deviation, so neither Q nor its root is read; the centre
+// term and the predicted mean cancel by symmetry.  For f = A x + G q, X_t = A P_t exactly (2 w c^2 = 1).  X_t is a
+// difference of images 2 c |R_t| apart: its fp32 relative error is about 2^-24 |f(m_t)| / (c |P_t|^1/2), the cancellation
+// the filter's own moment sums have; alpha << 1 makes it large (1e-4 ... 2e-4 against float64 at alpha = 1e-3).
+//
 // Register kernel (this file, n <= 8): one lane per trajectory, 64-thread workgroups.  The carry (m^s, P^s) and the
 // step's P, P-, X, Cholesky factor live in VGPRs; every loop has compile-time bounds.  Two data paths, same arithmetic
 // (so the same bits):
@@ -29,11 +42,12 @@
 #include "kf_math.hpp"
 #include "models.hpp"
 #include "scan_common.hpp"
+#include "ugsf_scan.hpp"
 
 namespace bf {
 
 enum { RTS_STRIDED = 0, RTS_STAGED = 2 };
-enum { RTS_LIN = 0, RTS_LIN_RECOMPUTE = 1, RTS_EXT = 2 };
+enum { RTS_LIN = 0, RTS_LIN_RECOMPUTE = 1, RTS_EXT = 2, RTS_UNSC = 3 };
 
 // Linear dynamics: A, G Q G^T (constant part), G q0.
 template <int N>
@@ -41,6 +55,17 @@ struct RtsLin {
   float A[N * N];
   float GQG[N * N];
   float Gq0[N];
+};
+
+// Unscented route: what f(x, q0, u) of the registry dynamics reads (dyn_base_t's fields), F_q q0 and the prediction's
+// unscented constants c = sqrt(L + lambda), w = 1 / (2 (L + lambda)).
+template <int N>
+struct RtsUnsc {
+  int dyn_id;
+  float dth[8];
+  float A[N * N];
+  float Gq0[N];
+  float c, w;
 };
 
 struct RtsViews {
@@ -129,25 +154,54 @@ __device__ __forceinline__ void rts_step(float* X, const float* P, const float* 
   }
 }
 
-// F_t P_t and, for the recompute path, m-_{t+1} = A m + G q0, P-_{t+1} = (A P) A^T + G Q_t G^T (kf_math.hpp's
-// predict_cov association).
+// X_t of the unscented route (the contract above): the root of P_t, then one pair of sigma points at a time; no point set
+// is stored.  The points and their images are formed as the filter's predict forms them (ukf_predict: x = m + cs R[j, :],
+// ukf_dyn = dyn_base_t + F_q q0).
+template <int N>
+__device__ __forceinline__ void rts_unsc_cross(const RtsUnsc<N>& c, float u0, const float* m, const float* P, float* X) {
+#pragma clang fp contract(fast)
+  float R[N * N];
+  BF_UNROLL for (int i = 0; i < N * N; ++i) R[i] = P[i];
+  sym_sqrt<N>(R);
+  BF_UNROLL for (int i = 0; i < N * N; ++i) X[i] = 0.f;
+  BF_UNROLL for (int j = 0; j < N; ++j) {
+    float s[N], x[N], fp[N], fm[N];
+    BF_UNROLL for (int i = 0; i < N; ++i) s[i] = c.c * R[j * N + i];
+    BF_UNROLL for (int i = 0; i < N; ++i) x[i] = m[i] + s[i];
+    dyn_base_t<N, N, RtsUnsc<N>>(c, x, u0, fp);
+    BF_UNROLL for (int i = 0; i < N; ++i) x[i] = m[i] - s[i];
+    dyn_base_t<N, N, RtsUnsc<N>>(c, x, u0, fm);
+    BF_UNROLL for (int k = 0; k < N; ++k) {
+      const float d = (fp[k] + c.Gq0[k]) - (fm[k] + c.Gq0[k]);
+      BF_UNROLL for (int i = 0; i < N; ++i) X[k * N + i] = fmaf(d, s[i], X[k * N + i]);
+    }
+  }
+  BF_UNROLL for (int i = 0; i < N * N; ++i) X[i] *= c.w;
+}
+
+// F_t P_t (RTS_UNSC: X_t from the sigma points) and, for the recompute path, m-_{t+1} = A m + G q0,
+// P-_{t+1} = (A P) A^T + G Q_t G^T (kf_math.hpp's predict_cov association).
 template <int N, int KIND, class Arg>
 __device__ __forceinline__ void rts_linearize(const Arg& c, const float* gqg_t, long long t, float u0, const float* m,
                                               const float* P, float* X, float* mp, float* Pp) {
-  float F[N * N];
-  if constexpr (KIND == RTS_EXT) {
-    float fx[N];
-    dyn_linearize<N, 1>(c, m, u0, F, fx);
+  if constexpr (KIND == RTS_UNSC) {
+    rts_unsc_cross<N>(c, u0, m, P, X);
   } else {
-    BF_UNROLL for (int i = 0; i < N * N; ++i) F[i] = c.A[i];
-  }
-  mm<N, N, N>(F, P, X);
-  if constexpr (KIND == RTS_LIN_RECOMPUTE) {
-    mm_nt<N, N, N>(X, F, Pp);
-    const float* q = gqg_t ? gqg_t + t * (N * N) : c.GQG;
-    BF_UNROLL for (int i = 0; i < N * N; ++i) Pp[i] = Pp[i] + q[i];
-    mv<N, N>(F, m, mp);
-    BF_UNROLL for (int i = 0; i < N; ++i) mp[i] += c.Gq0[i];
+    float F[N * N];
+    if constexpr (KIND == RTS_EXT) {
+      float fx[N];
+      dyn_linearize<N, 1>(c, m, u0, F, fx);
+    } else {
+      BF_UNROLL for (int i = 0; i < N * N; ++i) F[i] = c.A[i];
+    }
+    mm<N, N, N>(F, P, X);
+    if constexpr (KIND == RTS_LIN_RECOMPUTE) {
+      mm_nt<N, N, N>(X, F, Pp);
+      const float* q = gqg_t ? gqg_t + t * (N * N) : c.GQG;
+      BF_UNROLL for (int i = 0; i < N * N; ++i) Pp[i] = Pp[i] + q[i];
+      mv<N, N>(F, m, mp);
+      BF_UNROLL for (int i = 0; i < N; ++i) mp[i] += c.Gq0[i];
+    }
   }
 }
 
@@ -219,12 +273,16 @@ __global__ void __launch_bounds__(64) rts_reg_kernel(Arg c, const float* __restr
       float m[N], P[NN], mp[N], Pp[NN], X[NN], C[NN];
       BF_UNROLL for (int i = 0; i < N; ++i) m[i] = ld(v.m, t, i);
       BF_UNROLL for (int i = 0; i < NN; ++i) P[i] = ld(v.P, t, i);
-      if constexpr (KIND != RTS_LIN_RECOMPUTE) {
+      if constexpr (KIND != RTS_LIN_RECOMPUTE && KIND != RTS_UNSC) {
         BF_UNROLL for (int i = 0; i < N; ++i) mp[i] = ld(v.pm, t, i);
         BF_UNROLL for (int i = 0; i < NN; ++i) Pp[i] = ld(v.pP, t, i);
       }
       const float u0 = v.u ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
       rts_linearize<N, KIND>(c, gqg_t, t, u0, m, P, X, mp, Pp);
+      if constexpr (KIND == RTS_UNSC) {  // after the root: its 2 n^2 registers are free again
+        BF_UNROLL for (int i = 0; i < N; ++i) mp[i] = ld(v.pm, t, i);
+        BF_UNROLL for (int i = 0; i < NN; ++i) Pp[i] = ld(v.pP, t, i);
+      }
       rts_step<N>(X, P, m, mp, Pp, ms, Ps, C, want_c);
       BF_UNROLL for (int i = 0; i < N; ++i) st(v.ms, t, i, ms[i]);
       BF_UNROLL for (int i = 0; i < NN; ++i) st(v.Ps, t, i, Ps[i]);

@@ -1,8 +1,9 @@
-"""Posterior sampling on the HIP engine: joint draws x_{0:T-1} ~ p(x_{0:T-1} | y_{0:T-1}) for the Kalman and
-extended-Kalman filters (dynamax's ``lgssm_posterior_sample``): the backward half of forward-filter backward-sampling.
+"""Posterior sampling on the HIP engine: joint draws x_{0:T-1} ~ p(x_{0:T-1} | y_{0:T-1}) for the Kalman,
+extended-Kalman and unscented Kalman filters (dynamax's ``lgssm_posterior_sample``): the backward half of forward-filter
+backward-sampling.
 
 The backward pass consumes the streams a filter already wrote, as the smoother does, and runs in ``bf_ffbs_sample_f32`` /
-``bf_effbs_sample_f32`` (include/bayesfilt.h, csrc/ffbs_sampler.hpp, where the recursion and its treatment of singular
+``bf_effbs_sample_f32`` / ``bf_uffbs_sample_f32`` (include/bayesfilt.h, csrc/ffbs_sampler.hpp, where the recursion and its treatment of singular
 conditional covariances are stated).  PyTorch only allocates and passes device buffers; there is no CPU path.
 """
 import ctypes as C
@@ -12,9 +13,9 @@ import numpy as np
 
 from . import _lib
 from .inference import (_torch, _dev_f32, _host_f32, _alloc_stream, _stream_desc, _Model, kalman_filter,
-                        gaussian_sum_filter)
+                        gaussian_sum_filter, unscented_gaussian_sum_filter)
 from .nonlinearities import DYN_LINEAR, require_device_function
-from .smoother import _LinearDynamics, _batched, _FILTER_KW
+from .smoother import _LinearDynamics, _batched, _FILTER_KW, _ukf_params, _inputs_desc
 
 
 class SamplerCarry(NamedTuple):
@@ -37,7 +38,7 @@ def _keys_for(key, B):
 
 def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise=None, inputs=None, carry=None,
                      return_carry: bool = False, layout: str = "reference", out=None, extended: Optional[bool] = None,
-                     device="cuda", options=None):
+                     uparams=None, device="cuda", options=None):
     """Draw ``num_samples`` joint trajectories per filtered trajectory of ``posterior`` (a ``PosteriorGaussianSumFiltered``
     of ``kalman_filter``, or of ``gaussian_sum_filter`` with one component) on the device.  Returns a float32 device
     tensor (S, T, n) for one trajectory, (B, S, T, n) for a batch.
@@ -47,6 +48,9 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
     ``random.normal(keys[b], (S, T, n))``; chunked calls take a key per chunk.
     Linear dynamics run ``bf_ffbs_sample_f32`` (without the predicted streams in ``posterior`` they are recomputed);
     other registry dynamics run ``bf_effbs_sample_f32`` and need them, ``extended=True`` sends a linear model there too.
+    ``uparams`` (a :class:`ParamsUKF` or a 3-tuple): the posterior is ``unscented_gaussian_sum_filter``'s with one component
+    and the gain uses the sigma-point cross-covariance of the filter's predict (``bf_uffbs_sample_f32``, the contract and
+    its float32 error model as in :func:`rts_smoother`); it needs the predicted streams and excludes ``extended=True``.
     ``carry``: the :class:`SamplerCarry` returned (``return_carry=True``) by the sampling of the steps that FOLLOW these.
     ``out``: a tensor a previous call returned, reused.  ``device`` must name the device the posterior's streams live on.
     ``options``: e.g. ``{"ffbs_spl": 4}``, ``{"force_generic": 1}``.
@@ -81,7 +85,10 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
         want = (S, T, n) if squeeze else (B, S, T, n)
         if tuple(noise.shape) != want:
             raise ValueError(f"noise has shape {tuple(noise.shape)}, expected {want}")
+    up = _ukf_params(uparams, extended) if uparams is not None else None
     use_ext = (f.fn_id != DYN_LINEAR) if extended is None else bool(extended)
+    if up is not None and pm_b is None:
+        raise ValueError("the unscented sampler needs the predicted means and covariances (filter with FULL5 fields)")
     if use_ext and pm_b is None:
         raise ValueError("the extended sampler needs the predicted means and covariances (filter with FULL5 fields)")
     for t_ in (m_b, P_b, pm_b, pP_b, noise):
@@ -135,19 +142,15 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
         cr.x_out = c_out.states.data_ptr()
 
     stream = cur.cuda_stream
-    if use_ext:
+    if up is not None:
         mdl = _Model(params)
-        ud = _lib.bf_cstream()
-        if inputs is not None:
-            u = _dev_f32(inputs, dev)
-            if u.dim() == 1:
-                u = u.reshape(1, T, 1)
-            elif u.dim() == 2:
-                u = u.reshape(1, T, -1)
-            if u.shape[1] != T or u.shape[0] not in (1, B):
-                raise ValueError(f"inputs must be (T,), (T,d) or (B,T,d); got {tuple(u.shape)}")
-            keep.append(u)
-            ud.ptr, ud.sB, ud.sT, ud.sE = u.data_ptr(), (u.stride(0) if u.shape[0] == B else 0), u.stride(1), 1
+        ud = _inputs_desc(inputs, B, T, dev, keep)
+        _lib.arm_call_options(lib, options)
+        _lib.check(lib.bf_uffbs_sample_f32(C.byref(mdl.c), C.byref(up), C.byref(ud), C.byref(fd), B, T, S, C.byref(cr),
+                                           C.byref(sd), C.c_void_p(stream)))
+    elif use_ext:
+        mdl = _Model(params)
+        ud = _inputs_desc(inputs, B, T, dev, keep)
         _lib.arm_call_options(lib, options)
         _lib.check(lib.bf_effbs_sample_f32(C.byref(mdl.c), C.byref(ud), C.byref(fd), B, T, S, C.byref(cr), C.byref(sd),
                                            C.c_void_p(stream)))
@@ -185,3 +188,16 @@ def extended_kalman_posterior_sample(params, emissions, num_samples, key, inputs
     post = gaussian_sum_filter(params, emissions, 1, inputs=inputs,
                                fields=("means", "covariances", "predicted_means", "predicted_covariances"), **fkw)
     return posterior_sample(params, post, num_samples, key=key, inputs=inputs, extended=True, **skw)
+
+
+def unscented_kalman_posterior_sample(params, uparams, emissions, num_samples, key, inputs=None, **kw):
+    """The unscented Kalman filter (``unscented_gaussian_sum_filter`` with one component, started from
+    ``params.initial_mean`` unless ``initial_means`` is given), then :func:`posterior_sample` through
+    ``bf_uffbs_sample_f32``."""
+    fkw = {k: kw[k] for k in _FILTER_KW if k in kw}
+    skw = {k: v for k, v in kw.items() if k not in ("initial_means", "initial_covariances")}
+    if "initial_means" not in fkw:
+        fkw["initial_means"] = _host_f32(params.initial_mean).reshape(1, -1)
+    post = unscented_gaussian_sum_filter(params, uparams, emissions, 1, inputs=inputs,
+                                         fields=("means", "covariances", "predicted_means", "predicted_covariances"), **fkw)
+    return posterior_sample(params, post, num_samples, key=key, inputs=inputs, uparams=uparams, **skw)

@@ -1,9 +1,9 @@
 """Rauch-Tung-Striebel smoothing on the HIP engine: the reference's ``SSM.smoother(params, emissions, inputs)``
-(gaussfiltax/ssm.py:55-61, 282-300), p(z_t | y_{1:T}), for the Kalman and extended-Kalman filters.
+(gaussfiltax/ssm.py:55-61, 282-300), p(z_t | y_{1:T}), for the Kalman, extended-Kalman and unscented Kalman filters.
 
-The backward pass consumes the streams a filter already wrote (``kalman_filter`` / ``gaussian_sum_filter`` with one
-component) and runs in ``bf_rts_smoother_f32`` / ``bf_eks_smoother_f32`` (include/bayesfilt.h, csrc/rts_smoother.hpp,
-where the recursion is stated).  PyTorch only allocates and passes device buffers; there is no CPU path.
+The backward pass consumes the streams a filter already wrote (``kalman_filter`` / ``gaussian_sum_filter`` /
+``unscented_gaussian_sum_filter`` with one component) and runs in ``bf_rts_smoother_f32`` / ``bf_eks_smoother_f32`` /
+``bf_uks_smoother_f32`` (include/bayesfilt.h, csrc/rts_smoother.hpp, where the recursion is stated).  PyTorch only allocates and passes device buffers; there is no CPU path.
 """
 import ctypes as C
 from typing import NamedTuple, Optional, Any
@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .inference import (_torch, _dev_f32, _host_f32, _fp, _alloc_stream, _stream_desc, _time_varying, _Model,
-                        _check_out_tensor, kalman_filter, gaussian_sum_filter)
+                        _check_out_tensor, kalman_filter, gaussian_sum_filter, unscented_gaussian_sum_filter, ParamsUKF)
 from .nonlinearities import DYN_LINEAR, require_device_function
 
 
@@ -57,8 +57,34 @@ def _batched(x, event_dims):
     return x.unsqueeze(0) if x.dim() == 2 + event_dims else x
 
 
+def _ukf_params(uparams, extended):
+    """``uparams`` (a :class:`ParamsUKF` or a 3-tuple) as the C struct; it excludes ``extended=True``."""
+    if extended:
+        raise ValueError("uparams selects the unscented route; it cannot be combined with extended=True")
+    if not isinstance(uparams, ParamsUKF):
+        uparams = ParamsUKF(*uparams)
+    return _lib.bf_ukf_params(float(uparams.alpha), float(uparams.beta), float(uparams.kappa))
+
+
+def _inputs_desc(inputs, B, T, dev, keep):
+    """bf_cstream of the filter's inputs ((T,), (T, d) or (B, T, d); None = zeros)."""
+    ud = _lib.bf_cstream()
+    if inputs is not None:
+        u = _dev_f32(inputs, dev)
+        if u.dim() == 1:
+            u = u.reshape(1, T, 1)
+        elif u.dim() == 2:
+            u = u.reshape(1, T, -1)
+        if u.shape[1] != T or u.shape[0] not in (1, B):
+            raise ValueError(f"inputs must be (T,), (T,d) or (B,T,d); got {tuple(u.shape)}")
+        keep.append(u)
+        ud.ptr, ud.sB, ud.sT, ud.sE = u.data_ptr(), (u.stride(0) if u.shape[0] == B else 0), u.stride(1), 1
+    return ud
+
+
 def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariances: bool = False, layout: str = "reference",
-                 out=None, return_carry: bool = False, extended: Optional[bool] = None, device="cuda", options=None):
+                 out=None, return_carry: bool = False, extended: Optional[bool] = None, uparams=None, device="cuda",
+                 options=None):
     """Smooth the filtered posterior ``posterior`` (a ``PosteriorGaussianSumFiltered`` of ``kalman_filter``, or of
     ``gaussian_sum_filter`` with one component) backwards in time on the device.
 
@@ -66,6 +92,12 @@ def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariance
     ``predicted_covariances`` in ``posterior`` the predictions are recomputed from the filtered streams.  Other registry
     dynamics run ``bf_eks_smoother_f32`` (F_t = the Jacobian at the filtered mean and ``inputs``, as the filter's predict
     used it) and need the predicted streams; ``extended=True`` sends a linear model there too.
+    ``uparams`` (a :class:`ParamsUKF` or a 3-tuple): the posterior is ``unscented_gaussian_sum_filter``'s with one component
+    and the backward gain uses the sigma-point cross-covariance of the filter's predict (``bf_uks_smoother_f32``; the
+    contract is in csrc/rts_smoother.hpp); it needs the predicted streams and excludes ``extended=True``.  For linear
+    dynamics it is the linear smoother's function of the streams.  The cross-covariance is a float32 difference of
+    sigma-point images: its relative error grows like 2^-24 |f(m)| / (alpha sqrt(n + dq + kappa) |P|^1/2), 1e-4 ... 2e-4
+    at alpha = 1e-3.
     ``carry``: the :class:`SmootherCarry` returned (``return_carry=True``) by the smoothing of the steps that FOLLOW
     these (backward chunking); the chunk's last step then gets a cross-covariance too, so the cross-covariances cover
     all T steps of the chunk instead of T-1.  ``out``: a previous :class:`PosteriorGaussianSmoothed` whose smoothed
@@ -93,7 +125,10 @@ def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariance
         raise ValueError(f"covariances have shape {tuple(covs.shape)}, expected {(B, 1, T, n, n)}")
     if f.out_dim != n:
         raise ValueError(f"the dynamics function has state dimension {f.out_dim}, the posterior {n}")
+    up = _ukf_params(uparams, extended) if uparams is not None else None
     use_ext = (f.fn_id != DYN_LINEAR) if extended is None else bool(extended)
+    if up is not None and pm_b is None:
+        raise ValueError("the unscented smoother needs the predicted means and covariances (filter with FULL5 fields)")
     if use_ext and pm_b is None:
         raise ValueError("the extended smoother needs the predicted means and covariances (filter with FULL5 fields)")
     for t_ in (m_b, P_b, pm_b, pP_b):
@@ -148,19 +183,15 @@ def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariance
         cr.m_out, cr.P_out = c_out.means.data_ptr(), c_out.covariances.data_ptr()
 
     stream = torch.cuda.current_stream(dev).cuda_stream
-    if use_ext:
+    if up is not None:
         mdl = _Model(params)
-        ud = _lib.bf_cstream()
-        if inputs is not None:
-            u = _dev_f32(inputs, dev)
-            if u.dim() == 1:
-                u = u.reshape(1, T, 1)
-            elif u.dim() == 2:
-                u = u.reshape(1, T, -1)
-            if u.shape[1] != T or u.shape[0] not in (1, B):
-                raise ValueError(f"inputs must be (T,), (T,d) or (B,T,d); got {tuple(u.shape)}")
-            keep.append(u)
-            ud.ptr, ud.sB, ud.sT, ud.sE = u.data_ptr(), (u.stride(0) if u.shape[0] == B else 0), u.stride(1), 1
+        ud = _inputs_desc(inputs, B, T, dev, keep)
+        _lib.arm_call_options(lib, options)
+        _lib.check(lib.bf_uks_smoother_f32(C.byref(mdl.c), C.byref(up), C.byref(ud), C.byref(fd), B, T, C.byref(cr),
+                                           C.byref(sd), C.c_void_p(stream)))
+    elif use_ext:
+        mdl = _Model(params)
+        ud = _inputs_desc(inputs, B, T, dev, keep)
         _lib.arm_call_options(lib, options)
         _lib.check(lib.bf_eks_smoother_f32(C.byref(mdl.c), C.byref(ud), C.byref(fd), B, T, C.byref(cr), C.byref(sd),
                                            C.c_void_p(stream)))
@@ -203,3 +234,16 @@ def extended_kalman_smoother(params, emissions, inputs=None, **kw):
     post = gaussian_sum_filter(params, emissions, 1, inputs=inputs,
                                fields=("means", "covariances", "predicted_means", "predicted_covariances"), **fkw)
     return rts_smoother(params, post, inputs=inputs, extended=True, **skw)
+
+
+def unscented_kalman_smoother(params, uparams, emissions, inputs=None, **kw):
+    """The unscented Kalman filter (``unscented_gaussian_sum_filter`` with one component, started from
+    ``params.initial_mean`` unless ``initial_means`` is given), then :func:`rts_smoother` through ``bf_uks_smoother_f32``
+    (dynamax's ``unscented_kalman_smoother``)."""
+    fkw = {k: kw[k] for k in _FILTER_KW if k in kw}
+    skw = {k: v for k, v in kw.items() if k not in ("initial_means", "initial_covariances")}
+    if "initial_means" not in fkw:
+        fkw["initial_means"] = _host_f32(params.initial_mean).reshape(1, -1)
+    post = unscented_gaussian_sum_filter(params, uparams, emissions, 1, inputs=inputs,
+                                         fields=("means", "covariances", "predicted_means", "predicted_covariances"), **fkw)
+    return rts_smoother(params, post, inputs=inputs, uparams=uparams, **skw)

@@ -159,7 +159,7 @@ int bf_device_count(void);
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
  * called on that thread (bf_kalman_filter_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
  * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_eks_smoother_f32,
- * bf_ffbs_sample_f32, bf_effbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
+ * bf_ffbs_sample_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
 int bf_set_option(const char* name, int value);
 int bf_set_call_option(const char* name, int value);
@@ -436,6 +436,25 @@ int bf_rts_smoother_f32(const bf_lgssm* model, const bf_out_desc* filtered, int6
 int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
                         const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream);
 
+/* Unscented RTS smoother for registry dynamics (K = 1; the streams of bf_ugsf_ukf_f32 with one component, update -> predict
+ * order: filtered m_t, P_t and the predictions m-_{t+1}, P-_{t+1} at index t, all required).  u: the filter's inputs.
+ * With L = n + dq, lambda = alpha^2 (L + kappa) - L, c = sqrt(L + lambda), w = 1 / (2 (L + lambda)) (the prediction's constants):
+ *   R_t = symmetric square root of P_t (eigenvalues clamped at 0, lower triangle read: the root the filter's predict formed at t)
+ *   s_j = c R_t[j, :],  j = 0 ... n-1
+ *   X_t = w sum_j ( f(m_t + s_j, q0, u_t) - f(m_t - s_j, q0, u_t) ) s_j^T      (X[k][i] = Cov(x_{t+1,k}, x_{t,i} | y_{1:t}))
+ * takes the place of F_t P_t above; everything after it is unchanged: Cholesky of P-_{t+1} without jitter, G_t = (P-^-1 X_t)^T,
+ * m^s, P^s, C_t = G_t P^s_{t+1}; the last step without a carry is copied; a P- that is not positive definite gives NaN from
+ * that step backwards.  The sigma points that perturb only the noise have zero state deviation: neither Q nor its root is
+ * read, and the centre term and the predicted mean cancel by symmetry.  For f = A x + G q, X_t = A P_t exactly (2 w c^2 = 1).
+ * X_t is a difference of images 2 c |R_t| apart: its fp32 relative error is about 2^-24 |f(m_t)| / (c |P_t|^1/2), large for
+ * alpha << 1 (1e-4 ... 2e-4 at alpha = 1e-3).
+ * n on the register kernel as far as every instance builds without scratch, other n and "force_generic": one workgroup per
+ * trajectory, state in LDS.  BF_EUNSUPPORTED for functions given as source (BF_FN_USER), for model->flags != 0 and for an n
+ * beyond the LDS capacity (the message names the limit); BF_EINVAL for missing predicted streams and for ParamsUKF values
+ * the filter refuses (alpha <= 0, L + lambda <= 0). */
+int bf_uks_smoother_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* u, const bf_out_desc* filtered,
+                        int64_t B, int64_t T, const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream);
+
 /* ---- Posterior sampling: the backward half of forward-filter backward-sampling (dynamax's lgssm_posterior_sample) ----
  * Draws S joint trajectories x_{0:T-1} ~ p(x_{0:T-1} | y_{0:T-1}) per filtered trajectory from the streams the smoothers
  * read (same order, same F_t).  With xi_{s,t} in R^n standard normals:
@@ -449,8 +468,8 @@ int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out
  * tau d_j, tau = 2^-17, column j of L is zero, diagonal included (a zero pivot of a PSD matrix implies a zero column:
  * singular G Q G^T, e.g. the constant-velocity model, is part of the definition and not an error).  xi = 0 gives the RTS
  * smoothed means.  One component (K = 1), flags == 0.
- * With bf_sampler_abi_check, the two samplers below and the four entry points of the particle smoother this header declares
- * 34 entry points. */
+ * With bf_sampler_abi_check, the three samplers below, the unscented smoother above and the four entry points of the particle
+ * smoother this header declares 36 entry points. */
 typedef struct bf_sample_desc {
   bf_stream samples;    /* E = n; the K axis is the sample s: ptr[b*sB + s*sK + t*sT + e*sE]; required */
   bf_cstream noise;     /* standard normals, same indexing; ptr == NULL: drawn from keys */
@@ -482,6 +501,12 @@ int bf_ffbs_sample_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64
  * given as source (BF_FN_USER) and for model->flags != 0. */
 int bf_effbs_sample_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
                         int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream);
+
+/* Posterior samples for registry dynamics over unscented streams (bf_ugsf_ukf_f32 with K = 1, pred_* required): the recursion
+ * above with X_t of bf_uks_smoother_f32 in place of F_t P_t (W = Lp^-1 X_t, Sigma_t = P_t - W^T W, psdchol with tau = 2^-17,
+ * x_t = m_t + G_t (x_{t+1} - m-_{t+1}) + L_t xi_t).  Errors as bf_uks_smoother_f32. */
+int bf_uffbs_sample_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* u, const bf_out_desc* filtered,
+                        int64_t B, int64_t T, int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream);
 
 /* ---- Particle smoothing: joint draws from a bootstrap particle filter's stored history -------------------------------
  * S joint trajectories x_{0:T-1} ~ p(x_{0:T-1} | y_{0:T-1}) per filtered trajectory from what bf_bpf_f32 wrote: weights
