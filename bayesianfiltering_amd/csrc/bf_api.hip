@@ -427,10 +427,15 @@ int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out
                         const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream) {
   bf::CallOptionScope call_option_scope;
   if (!model || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
-  if (model->user || model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER)
-    return bf::set_error(BF_EUNSUPPORTED, "the extended smoother serves registry dynamics; functions given as source are not supported");
+  if (!model->user && (model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER))
+    return bf::set_error(BF_EUNSUPPORTED, "the extended smoother serves functions given as source through bf_model.user (bf_user_model_create); it is NULL");
   if (model->flags != 0)
     return bf::set_error(BF_EUNSUPPORTED, "the extended smoother needs the JAX path's update -> predict streams (flags = 0)");
+  if (model->user) {  // dynamics from source: the kernels built around them; an emission from source is never read
+    int rc = bf::check_user_model(model->user, model);
+    if (rc == BF_OK && model->dyn_id == BF_FN_USER) rc = bf::check_user_device(model->user);
+    if (rc != BF_OK) return rc;
+  }
   if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
   if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
     return bf::set_error(BF_EINVAL, "non-positive model dimension");

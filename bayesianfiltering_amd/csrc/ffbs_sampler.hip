@@ -31,6 +31,20 @@
 //   8    388 / 1    406 / 1    440 / 1    500 / 1
 // Run-time-dimension kernel: ffbs_generic_kernel<true> 134 VGPRs, 3 waves per SIMD; ffbs_generic_kernel<false> (every other
 // kind) 116 VGPRs, 4 waves, as before the route existed.
+//
+// Source route (RTS_EXT_USER, kernels compiled at run time: jit_source.hip JIT_FFBS_REGS / JIT_FFBS_GENERIC), measured on a
+// Lorenz-96 twin written as source (dq = n, -ffp-contract=off): every instance builds without scratch, so the register limit
+// is 8 at all four counts (RTS_USER_REG_MAX).  VGPRs (arch + acc) / waves per SIMD:
+//   n    SPL = 1    SPL = 2    SPL = 4    SPL = 8
+//   1    65 / 7     93 / 5     137 / 3    99 / 4
+//   2    62 / 8     90 / 5     85 / 5     117 / 4
+//   3    76 / 6     113 / 4    105 / 4    145 / 3
+//   4    128 / 4    125 / 4    149 / 3    199 / 2
+//   5    185 / 2    171 / 2    199 / 2    255 / 2
+//   6    188 / 2    224 / 2    251 / 2    316 / 1
+//   7    246 / 2    272 / 1    306 / 1    372 / 1
+//   8    336 / 1    292 / 1    328 / 1    398 / 1
+// Run-time-dimension kernel: n = 3: 83 VGPRs / 5 waves, n = 10: 97 / 4, n = 64: 315 / 1, no scratch.
 #include "ffbs_sampler.hpp"
 #include "rts_generic.hpp"
 
@@ -44,150 +58,9 @@ namespace bf {
 // Sg <- psdchol(Sg; diag P) in place, then the samples in blocks of SB: lanes split over (sample, row) in
 // x = m + X^T (x+ - m-) + Sg xi.  With one block the state stays in LDS from step to step; with more, a block's x+ is read
 // back from the sample stream (each element by the lane that wrote it one step earlier).
-struct FfbsGen {
-  RtsGen r;
-  int S, SB;            // samples, samples per LDS block
-};
-
-// RTS_UNSC: one more matrix (the root; Sg holds the eigenvectors while it is taken) and the root's vectors (rts_generic.hpp)
-static inline size_t ffbs_gen_unsc_floats(int n, int kind) {
-  return kind == RTS_UNSC ? (size_t)n * rts_gen_ld(n) + (size_t)rts_unsc_vec_floats(n) : 0;
-}
-static inline size_t ffbs_gen_mat_floats(int n, int kind) {
-  return 5 * (size_t)n * rts_gen_ld(n) + 3 * (size_t)n + ffbs_gen_unsc_floats(n, kind);
-}
-
 template <bool UNSC>
 __global__ void __launch_bounds__(64) ffbs_generic_kernel(FfbsGen fc, GenModel g, FfbsViews v, long long T) {
-  const RtsGen& c = fc.r;
-  const int tid = threadIdx.x;
-  const long long b = blockIdx.x;
-  const int n = c.n, ld = rts_gen_ld(n), nn = n * n, S = fc.S, SB = fc.SB;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* P = lds;
-  float* Pp = P + n * ld;
-  float* X = Pp + n * ld;
-  float* W = X + n * ld;
-  float* Sg = W + n * ld;
-  float* m = Sg + n * ld;
-  float* mp = m + n;
-  float* tv = mp + n;
-  const RtsUnscLds ul = rts_unsc_carve(Sg, tv + n, tv + n + n * ld, n);  // carved for RTS_UNSC only
-  float* xs = tv + n + (UNSC ? n * ld + rts_unsc_vec_floats(n) : 0);  // x_{t+1} of the block, then x_{t+1} - m-
-  float* xi = xs + SB * n;   // the block's noise
-  float* xo = xi + SB * n;   // x_t of the block
-  const bool one_block = SB >= S;
-  const bool keyed = v.xi.p == nullptr;
-  uint32_t k0 = 0, k1 = 0;
-  if (keyed) {
-    k0 = v.keys[2 * b];
-    k1 = v.keys[2 * b + 1];
-  }
-  const uint32_t count = (uint32_t)S * (uint32_t)T * (uint32_t)n;
-  auto at = [&](const SView& s, long long t, int e) { return b * s.sB + t * s.sT + e * s.sE; };
-  auto xat = [&](const SView& s, int smp, long long t, int e) { return b * s.sB + smp * s.sK + t * s.sT + e * s.sE; };
-
-  // the samples of step t in blocks: first = the chunk's last step without a carry (x = m + Sg xi)
-  auto samples = [&](long long t, bool first) {
-    for (int sb0 = 0; sb0 < S; sb0 += SB) {
-      const int ne = ((S - sb0) < SB ? (S - sb0) : SB) * n;
-      for (int e = tid; e < ne; e += 64) {
-        const int sl = e / n, i = e - sl * n, smp = sb0 + sl;
-        xi[e] = keyed ? bits_to_normal(threefry_bits(k0, k1, ((uint32_t)smp * (uint32_t)T + (uint32_t)t) * (uint32_t)n + i, count))
-                      : v.xi.p[xat(v.xi, smp, t, i)];
-        if (!first) {
-          float xn;
-          if (t == T - 1) xn = v.x_in[((long long)b * S + smp) * n + i];
-          else if (one_block) xn = xs[e];
-          else xn = v.x.p[xat(v.x, smp, t + 1, i)];
-          xs[e] = xn - mp[i];
-        }
-      }
-      wave_lds_sync();
-      for (int e = tid; e < ne; e += 64) {
-        const int sl = e / n, i = e - sl * n;
-        const float* z = xi + sl * n;
-        float s;
-        if (first) {
-          s = Sg[i * ld] * z[0];
-          for (int k = 1; k <= i; ++k) s = fmaf(Sg[i * ld + k], z[k], s);
-        } else {
-          const float* dx = xs + sl * n;
-          s = X[i] * dx[0];
-          for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], dx[k], s);
-          for (int k = 0; k <= i; ++k) s = fmaf(Sg[i * ld + k], z[k], s);
-        }
-        const float xv = m[i] + s;
-        xo[e] = xv;
-        v.x.p[xat(v.x, sb0 + sl, t, i)] = xv;
-        if (t == 0 && v.x_out) v.x_out[((long long)b * S + sb0 + sl) * n + i] = xv;
-      }
-      wave_lds_sync();
-      if (one_block) {
-        float* sw = xs;
-        xs = xo;
-        xo = sw;
-      }
-    }
-  };
-  // Sg (lower triangle) <- psdchol(Sg; diag P); every lane forms the pivot itself
-  auto psd_factor = [&]() {
-    for (int j = 0; j < n; ++j) {
-      float p = Sg[j * ld + j];
-      for (int k = 0; k < j; ++k) p = fmaf(-Sg[j * ld + k], Sg[j * ld + k], p);
-      const bool keep = p > BF_FFBS_TAU * P[j * ld + j];
-      const float r = keep ? fast_sqrt(p) : 0.f;
-      const float inv = keep ? fast_rcp(r) : 0.f;
-      for (int i = j + 1 + tid; i < n; i += 64) {
-        float s = Sg[i * ld + j];
-        for (int k = 0; k < j; ++k) s = fmaf(-Sg[i * ld + k], Sg[j * ld + k], s);
-        Sg[i * ld + j] = keep ? s * inv : 0.f;
-      }
-      wave_lds_sync();  // the pivot's reads of row j are done before its diagonal changes
-      if (tid == 0) Sg[j * ld + j] = r;
-      wave_lds_sync();
-    }
-  };
-
-  long long t = T - 1;
-  if (!v.x_in) {
-    for (int e = tid; e < n; e += 64) m[e] = v.m.p[at(v.m, t, e)];
-    for (int e = tid; e < nn; e += 64) {
-      const float x = v.P.p[at(v.P, t, e)];
-      P[(e / n) * ld + e % n] = x;
-      Sg[(e / n) * ld + e % n] = x;
-    }
-    wave_lds_sync();
-    psd_factor();
-    samples(t, true);
-    --t;
-  }
-  for (; t >= 0; --t) {
-    for (int e = tid; e < n; e += 64) m[e] = v.m.p[at(v.m, t, e)];
-    for (int e = tid; e < nn; e += 64) P[(e / n) * ld + e % n] = v.P.p[at(v.P, t, e)];
-    if (c.kind != RTS_LIN_RECOMPUTE) {
-      for (int e = tid; e < n; e += 64) mp[e] = v.pm.p[at(v.pm, t, e)];
-      for (int e = tid; e < nn; e += 64) Pp[(e / n) * ld + e % n] = v.pP.p[at(v.pP, t, e)];
-    }
-    wave_lds_sync();
-    const float u0 = ((UNSC || c.kind == RTS_EXT) && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
-    rts_gen_linearize<UNSC>(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid, ul);
-    rts_gen_chol(n, Pp, W, tid);
-    rts_gen_solve_lower(n, W, X, tid);  // X <- L^-1 X
-    wave_lds_sync();
-    for (int e = tid; e < nn; e += 64) {  // Sg = P - X^T X, lower triangle
-      const int i = e / n, j = e - i * n;
-      if (j > i) continue;
-      float s = P[i * ld + j];
-      for (int k = 0; k < n; ++k) s = fmaf(-X[k * ld + i], X[k * ld + j], s);
-      Sg[i * ld + j] = s;
-    }
-    wave_lds_sync();
-    rts_gen_solve_upper(n, W, X, tid);  // X <- L^-T X
-    wave_lds_sync();
-    psd_factor();
-    samples(t, false);
-  }
+  ffbs_generic_body<UNSC, false>(fc, g, v, T);
 }
 
 // ---- host helpers --------------------------------------------------------------------------------------------------
@@ -229,11 +102,11 @@ static int launch_ffbs_n(const Arg& c, const float* d_gqg, const FfbsViews& v, l
   return BF_OK;
 }
 
-static int launch_ffbs_generic(const FfbsGen& c0, const GenModel& g, const std::vector<float>& blk, const FfbsViews& v,
-                               long long B, long long T, hipStream_t stream) {
+// c.SB and the LDS bytes of the run-time-dimension kernel; BF_EUNSUPPORTED with the byte count when 160 KiB do not hold the model
+static int ffbs_gen_plan(FfbsGen& c, size_t* lds_bytes) {
   const size_t cap = 160 * 1024 / sizeof(float);
-  const int n = c0.r.n;
-  const int kind = c0.r.kind;
+  const int n = c.r.n;
+  const int kind = c.r.kind;
   const size_t mat = ffbs_gen_mat_floats(n, kind);
   if (mat + 3 * (size_t)n > cap) {
     int nmax = 1;
@@ -242,13 +115,22 @@ static int launch_ffbs_generic(const FfbsGen& c0, const GenModel& g, const std::
                      sizeof(float) * (mat + 3 * (size_t)n), nmax);
   }
   // samples per LDS block: up to 2048 floats per buffer (keeps several workgroups per CU), at least one sample
-  FfbsGen c = c0;
   size_t sb = 2048 / (size_t)n;
   if (sb < 1) sb = 1;
   if (sb > (cap - mat) / (3 * (size_t)n)) sb = (cap - mat) / (3 * (size_t)n);
   if (sb > (size_t)c.S) sb = (size_t)c.S;
   c.SB = (int)sb;
-  const size_t lds = sizeof(float) * (mat + 3 * sb * n);
+  *lds_bytes = sizeof(float) * (mat + 3 * sb * n);
+  return BF_OK;
+}
+
+static int launch_ffbs_generic(const FfbsGen& c0, const GenModel& g, const std::vector<float>& blk, const FfbsViews& v,
+                               long long B, long long T, hipStream_t stream) {
+  const int kind = c0.r.kind;
+  FfbsGen c = c0;
+  size_t lds = 0;
+  const int prc = ffbs_gen_plan(c, &lds);
+  if (prc != BF_OK) return prc;
   GenModel gg = g;
   const int rc = rts_gen_upload(c.r, gg, blk, stream);
   if (rc != BF_OK) return rc;
@@ -292,8 +174,49 @@ static int launch_ffbs_linear(const bf_lgssm* p, const FfbsViews& v, long long B
   return launch_ffbs_generic(c, g, blk, v, B, T, stream);
 }
 
+// Source route (RTS_EXT_USER): the register kernel compiled at run time around the caller's dynamics, one entry point per
+// samples-per-lane count (jit_source.hip: JIT_FFBS_REGS)
+static int launch_ffbs_user(const bf_model* p, const FfbsViews& v, long long B, long long T, int S, bool force_generic, int forced_spl,
+                            hipStream_t stream) {
+  const int n = p->n;
+  if (force_generic || n > RTS_USER_REG_MAX) {  // the run-time-dimension kernel (JIT_FFBS_GENERIC), launch_ffbs_generic's LDS plan
+    FfbsGen c;
+    std::memset(&c, 0, sizeof(c));
+    c.r.n = n;
+    c.r.kind = RTS_EXT_USER;
+    c.S = S;
+    size_t lds = 0;
+    int rc = ffbs_gen_plan(c, &lds);
+    if (rc != BF_OK) return rc;
+    if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B too large for the run-time-dimension kernel");
+    GenModel g;
+    if ((rc = rts_user_gen_model(p, g, stream)) != BF_OK) return rc;
+    hipFunction_t fn = nullptr;
+    if ((rc = user_kernel(p->user, JIT_FFBS_GENERIC, 0, 0, JIT_SPEC_USER, &fn)) != BF_OK) return rc;
+    FfbsViews w = v;
+    long long T_ = T;
+    void* args[] = {&c, &g, &w, &T_};
+    return launch_user_kernel(p->user, 64, (unsigned)B, lds, stream, args, fn);
+  }
+  RtsUserHost h;
+  int rc = rts_user_fill(p, h);
+  if (rc != BF_OK) return rc;
+  const int spl = ffbs_pick_spl(S, forced_spl);
+  const long long lanes = B * ((S + spl - 1) / spl);
+  if ((lanes + 63) / 64 > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B x S too large for one launch");
+  hipFunction_t fn = nullptr;
+  if ((rc = user_kernel(p->user, JIT_FFBS_REGS, spl, 0, JIT_SPEC_USER, &fn)) != BF_OK) return rc;
+  FfbsViews w = v;
+  long long B_ = B, T_ = T;
+  int S_ = S;
+  void* args[] = {&h, &w, &B_, &T_, &S_};
+  BF_HIP_CHECK(hipModuleLaunchKernel(fn, (unsigned)((lanes + 63) / 64), 1, 1, 64, 1, 1, 0, stream, args, nullptr));
+  return BF_OK;
+}
+
 static int launch_ffbs_ext(const bf_model* p, const FfbsViews& v, long long B, long long T, int S, bool force_generic, int spl,
                            hipStream_t stream) {
+  if (p->user && p->dyn_id == BF_FN_USER) return launch_ffbs_user(p, v, B, T, S, force_generic, spl, stream);
   GenModel g;
   std::vector<float> blk;
   int rc = gen_fill(p, T, g, blk);  // validates the registry ids and theta layouts
@@ -422,10 +345,15 @@ int bf_effbs_sample_f32(const bf_model* model, const bf_cstream* u, const bf_out
                         int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream) {
   bf::CallOptionScope call_option_scope;
   if (!model || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
-  if (model->user || model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER)
-    return bf::set_error(BF_EUNSUPPORTED, "the extended sampler serves registry dynamics; functions given as source are not supported");
+  if (!model->user && (model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER))
+    return bf::set_error(BF_EUNSUPPORTED, "the extended sampler serves functions given as source through bf_model.user (bf_user_model_create); it is NULL");
   if (model->flags != 0)
     return bf::set_error(BF_EUNSUPPORTED, "the extended sampler needs the JAX path's update -> predict streams (flags = 0)");
+  if (model->user) {  // dynamics from source: the kernel built around them; an emission from source is never read
+    int rc = bf::check_user_model(model->user, model);
+    if (rc == BF_OK && model->dyn_id == BF_FN_USER) rc = bf::check_user_device(model->user);
+    if (rc != BF_OK) return rc;
+  }
   if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
     return bf::set_error(BF_EINVAL, "non-positive model dimension");
   if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");

@@ -26,7 +26,9 @@
 // lane repeats the factorization its trajectory shares (ALU time, no HBM traffic) and then serves its SPL samples from it.
 // Run-time-dimension kernel (ffbs_sampler.hip): one wave per trajectory, matrices and a block of samples in LDS.
 #pragma once
+#ifndef BF_JIT
 #include "bf_common.hpp"
+#endif
 #include "bf_rng.hpp"
 #include "rts_smoother.hpp"
 
@@ -106,9 +108,10 @@ __device__ __forceinline__ void ffbs_factor(float* X, const float* P, const floa
   psdchol<N>(Ls, d);
 }
 
+// (a device function, as rts_reg_body: shared by the ahead-of-time instances and the entry points compiled at run time)
 template <int N, int SPL, int KIND, class Arg>
-__global__ void __launch_bounds__(64) ffbs_reg_kernel(Arg c, const float* __restrict__ gqg_t, FfbsViews v, long long B,
-                                                      long long T, int S) {
+__device__ __forceinline__ void ffbs_reg_body(const Arg& c, const float* __restrict__ gqg_t, const FfbsViews& v, long long B,
+                                              long long T, int S) {
   constexpr int NN = N * N;
   const int NB = (S + SPL - 1) / SPL;  // sample blocks (lanes) per trajectory
   const long long g = (long long)blockIdx.x * 64 + threadIdx.x;
@@ -188,6 +191,12 @@ __global__ void __launch_bounds__(64) ffbs_reg_kernel(Arg c, const float* __rest
     BF_UNROLL for (int j = 0; j < SPL; ++j) if (s0 + j < S)
       BF_UNROLL for (int i = 0; i < N; ++i) v.x_out[(b * S + s0 + j) * N + i] = x[j][i];
   }
+}
+
+template <int N, int SPL, int KIND, class Arg>
+__global__ void __launch_bounds__(64) ffbs_reg_kernel(Arg c, const float* __restrict__ gqg_t, FfbsViews v, long long B,
+                                                      long long T, int S) {
+  ffbs_reg_body<N, SPL, KIND, Arg>(c, gqg_t, v, B, T, S);
 }
 
 }  // namespace bf

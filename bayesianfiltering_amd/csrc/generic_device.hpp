@@ -3,7 +3,7 @@
 // with a user's own dynamics / emission functions (jit_source.hip: BF_JIT, BF_USER_DYN / BF_USER_EMI) -- the text of this
 // file is embedded in the library for that purpose, so it must stay self-contained under BF_JIT.
 #pragma once
-#ifdef BF_JIT
+#if defined(BF_JIT) && !defined(BF_JIT_FULL_HEADERS)   // (BF_JIT_FULL_HEADERS: kf_math.hpp, scan_common.hpp and models.hpp themselves precede this text)
 // hiprtc build: the few helpers the ahead-of-time build takes from bf_common.hpp / kf_math.hpp / scan_common.hpp / models.hpp
 // (the kernel-argument views, bf_views.hpp, precede this text in both builds)
 namespace bf {

@@ -16,6 +16,9 @@ extern const char* const kAgsfSource;           // agsf_geom.hpp + agsf_scan.hpp
 extern const char* const kSampleSource;         // sample_ssm.hpp
 extern const char* const kBpfBigSource;         // bpf_big.hpp
 extern const char* const kUgsfSource;           // ugsf_scan.hpp
+extern const char* const kRtsSource;            // rts_smoother.hpp
+extern const char* const kFfbsSource;           // ffbs_sampler.hpp
+extern const char* const kRtsGenericSource;     // rts_generic.hpp
 
 namespace {
 
@@ -153,8 +156,12 @@ __device__ inline float pow(float x, float p) { return ::powf(x, p); }
 
 }  // namespace
 
-const char* jit_entry_name(int kind) {
+const char* jit_entry_name(int kind, int variant) {
   switch (kind) {
+    case JIT_RTS_GENERIC: return "bf_user_rts_generic";
+    case JIT_FFBS_GENERIC: return "bf_user_ffbs_generic";
+    case JIT_RTS_REGS: return variant == 2 ? "bf_user_rts_staged" : "bf_user_rts_strided";   // RTS_STAGED / RTS_STRIDED
+    case JIT_FFBS_REGS: return variant == 1 ? "bf_user_ffbs_spl1" : variant == 2 ? "bf_user_ffbs_spl2" : variant == 4 ? "bf_user_ffbs_spl4" : "bf_user_ffbs_spl8";
     case JIT_BPF: return "bf_user_bpf";
     case JIT_UGSF: return "bf_user_ugsf";
     case JIT_AGSF_UKF: case JIT_AGSF_EKF: return "bf_user_agsf";
@@ -169,6 +176,65 @@ const char* jit_entry_name(int kind) {
 std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int spec_id) {
   if (kind == JIT_GSF_GENERIC) return generic_scan_source(um, 0);
   if (kind == JIT_UGSF_GENERIC) return generic_scan_source(um, 64 * nw);   // nw = 1: one wave per trajectory, 4: four
+  if (kind == JIT_RTS_GENERIC || kind == JIT_FFBS_GENERIC) {
+    // The run-time-dimension kernels of the smoother / the posterior sampler around the caller's dynamics: libm's float functions
+    // under the dual numbers, as in JIT_GSF_GENERIC, whose streams they read; the kernel bodies are rts_generic.hpp's, with every
+    // header they include in front (BF_JIT_FULL_HEADERS: generic_device.hpp then brings no helpers of its own).
+    std::string s = "#define BF_JIT 1\n#define BF_JIT_FULL_HEADERS 1\n#include <cstdint>\n#include <type_traits>\n#define BF_USER_DYN 1\n";
+    s += "#define BF_N " + std::to_string(um.n) + "\n#define BF_DQ " + std::to_string(um.dq) + "\n#define BF_M " + std::to_string(um.m) +
+         "\n#define BF_DR " + std::to_string(um.dr) + "\n";
+    s += kViewsSource;
+    s += kSamplingSourceA;
+    s += "#pragma clang fp contract(off)\nnamespace bfu {\n";
+    s += kDualCore;
+    s += kLibmMath;
+    s += kDualMath;
+    s += "\n// ---- the caller's dynamics\n" + um.dyn_src + "\n}  // namespace bfu\n";
+    s += kSamplingSourceB;
+    s += kUgsfSource;
+    s += kRtsSource;
+    s += kFfbsSource;
+    s += kGenericDeviceSource;
+    s += kUgsfGenericSource;
+    s += kRtsGenericSource;
+    if (kind == JIT_RTS_GENERIC)
+      s += "extern \"C\" __global__ void __launch_bounds__(64) bf_user_rts_generic(bf::RtsGen c, bf::GenModel g, bf::RtsViews v, long long T) {\n"
+           "  bf::rts_generic_body<false, true>(c, g, v, T);\n}\n";
+    else
+      s += "extern \"C\" __global__ void __launch_bounds__(64) bf_user_ffbs_generic(bf::FfbsGen c, bf::GenModel g, bf::FfbsViews v, long long T) {\n"
+           "  bf::ffbs_generic_body<false, true>(c, g, v, T);\n}\n";
+    return s;
+  }
+  if (kind == JIT_RTS_REGS || kind == JIT_FFBS_REGS) {
+    // The register kernels of the smoother / the posterior sampler around the caller's dynamics (RTS_EXT_USER), assembled as
+    // JIT_GSF_REGS is: the caller's function sees the float functions of the register filter that produced the streams.  The
+    // emission is not read by a backward pass and is left out.  One module holds every data path / samples-per-lane count.
+    std::string s = "#define BF_JIT 1\n#include <cstdint>\n#include <type_traits>\n#define BF_USER_DYN 1\n";
+    s += "#define BF_N " + std::to_string(um.n) + "\n#define BF_DQ " + std::to_string(um.dq) + "\n#define BF_M " + std::to_string(um.m) +
+         "\n#define BF_DR " + std::to_string(um.dr) + "\n";
+    s += kViewsSource;
+    s += kSamplingSourceA;
+    s += kSamplingUserMath;
+    s += kDualCore;
+    s += kDualMath;
+    s += "\n// ---- the caller's dynamics\n" + um.dyn_src + "\n}  // namespace bfu\n";
+    s += kSamplingSourceB;
+    s += kUgsfSource;
+    s += kRtsSource;
+    if (kind == JIT_RTS_REGS) {
+      for (int mode : {0, 2})
+        s += std::string("extern \"C\" __global__ void __launch_bounds__(64) ") + jit_entry_name(kind, mode) +
+             "(bf::RtsUser<BF_DQ> c, bf::RtsViews v, long long B, long long T) {\n  bf::rts_reg_body<BF_N, " + std::to_string(mode) +
+             ", bf::RTS_EXT_USER>(c, nullptr, v, B, T);\n}\n";
+      return s;
+    }
+    s += kFfbsSource;
+    for (int spl : {1, 2, 4, 8})
+      s += std::string("extern \"C\" __global__ void __launch_bounds__(64) ") + jit_entry_name(kind, spl) +
+           "(bf::RtsUser<BF_DQ> c, bf::FfbsViews v, long long B, long long T, int S) {\n  bf::ffbs_reg_body<BF_N, " + std::to_string(spl) +
+           ", bf::RTS_EXT_USER>(c, nullptr, v, B, T, S);\n}\n";
+    return s;
+  }
   std::string s = "#define BF_JIT 1\n#include <cstdint>\n#include <type_traits>\n";
   if (um.hw_arith) s += "#define BF_BPF_HW_ARITH 1\n";
   if (um.has_dyn) s += "#define BF_USER_DYN 1\n";

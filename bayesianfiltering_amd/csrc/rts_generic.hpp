@@ -1,17 +1,26 @@
 // What the run-time-dimension kernels of the smoother (rts_smoother.hip) and of the posterior sampler (ffbs_sampler.hip)
 // share: the per-step gain work on n x (n + 1) matrices in LDS (F_t, X = F P, the recomputed prediction, the Cholesky of
 // P- and the two triangular solves), the constant block behind it and the model structs of the register kernels.
+//
+// The kernel bodies live here as device functions: the ahead-of-time kernels (rts_smoother.hip, ffbs_sampler.hip) and the
+// entry points hiprtc compiles around a caller's dynamics (jit_source.hip: JIT_RTS_GENERIC / JIT_FFBS_GENERIC, the
+// RTS_EXT_USER route for n above the register limit and "force_generic" = 1) are thin kernels around them.  The file is
+// embedded for that purpose (jit_embed.py), so the host side stays behind #ifndef BF_JIT.
 #pragma once
+#ifndef BF_JIT
 #include <cstring>
 #include <vector>
+#include "user_model.hpp"
+#endif
 #include "rts_smoother.hpp"
+#include "ffbs_sampler.hpp"
 #include "generic_device.hpp"
 #include "ugsf_generic_device.hpp"
 
 namespace bf {
 
 struct RtsGen {
-  int n, kind;          // RTS_LIN, RTS_LIN_RECOMPUTE, RTS_EXT, RTS_UNSC
+  int n, kind;          // RTS_LIN, RTS_LIN_RECOMPUTE, RTS_EXT, RTS_UNSC, RTS_EXT_USER
   const float* A;       // [n][n]            (linear kinds; RTS_UNSC: linear dynamics)
   const float* GQG;     // [q_steps][n][n]   (recompute)
   const float* Gq0;     // [n]               (recompute; RTS_UNSC: F_q q0)
@@ -39,7 +48,27 @@ __host__ __device__ inline RtsUnscLds rts_unsc_carve(float* V, float* Rt, float*
   return RtsUnscLds{V, Rt, vec, vec + nv, vec + 3 * nv};
 }
 
-#ifdef __HIPCC__
+// LDS floats of the smoother's run-time-dimension kernel
+__host__ __device__ inline size_t rts_gen_lds_floats(int n, int kind) {
+  const size_t base = 5 * (size_t)n * rts_gen_ld(n) + 4 * (size_t)n;
+  return kind == RTS_UNSC ? base + 2 * (size_t)n * rts_gen_ld(n) + (size_t)rts_unsc_vec_floats(n) : base;
+}
+
+// the sampler's run-time-dimension kernel: the smoother's constants and the sample blocking
+struct FfbsGen {
+  RtsGen r;
+  int S, SB;            // samples, samples per LDS block
+};
+
+// RTS_UNSC: one more matrix (the root; Sg holds the eigenvectors while it is taken) and the root's vectors
+__host__ __device__ inline size_t ffbs_gen_unsc_floats(int n, int kind) {
+  return kind == RTS_UNSC ? (size_t)n * rts_gen_ld(n) + (size_t)rts_unsc_vec_floats(n) : 0;
+}
+__host__ __device__ inline size_t ffbs_gen_mat_floats(int n, int kind) {
+  return 5 * (size_t)n * rts_gen_ld(n) + 3 * (size_t)n + ffbs_gen_unsc_floats(n, kind);
+}
+
+#if defined(__HIPCC__) || defined(BF_JIT)
 // The differences of the images of the n sigma-point pairs, D[j][k] = f_k(m + s_j, q0, u) - f_k(m - s_j, q0, u) with
 // s_j = cu Rt[j, :] (pitch ld).  Linear, Lorenz-96 and sine dynamics: one work item per (pair, output row), the formulas and
 // the per-entry operation order of ug_eval_dyn, whose points these are.  The registry functions of one fixed dimension
@@ -101,7 +130,24 @@ __device__ __forceinline__ void rts_gen_unsc_images(const RtsGen& c, float u0, c
 // (and P-, m-) are synchronised on return.  RTS_UNSC: X = X_t of rts_smoother.hpp's contract instead -- Rt <- the root of P
 // (ug_sym_sqrt, the filter's, Newton step included), W <- the image differences, X = w W^T (c Rt) as an LDS product.
 // UNSC is a template parameter: the kernels of the other kinds carry none of the root's code or registers.
-template <bool UNSC>
+#ifdef BF_USER_DYN
+// F_t of the source route (RTS_EXT_USER): lane d evaluates the caller's dynamics with the unit seed in state direction d and
+// writes column d of F -- the state half of user_dyn_linearize (generic_device.hpp): no F_q, no noise covariance, none of
+// its scratch.  g.q0 / g.dyn_theta: the noise bias and the caller's parameters in the constant block.
+__device__ __forceinline__ void rts_gen_user_jacobian(const GenModel& g, const float* m, float u0, float* F, int ld, int tid) {
+#pragma clang fp contract(off)
+  constexpr int N = BF_N, DQ = BF_DQ;
+  for (int d = tid; d < N; d += 64) {
+    bfu::Dual xs[N], qs[DQ], out[N];
+    BF_UNROLL for (int i = 0; i < N; ++i) xs[i] = bfu::Dual(m[i], i == d ? 1.0f : 0.0f);
+    BF_UNROLL for (int k = 0; k < DQ; ++k) qs[k] = bfu::Dual(g.q0[k]);
+    bfu::dynamics<bfu::Dual>(xs, qs, bfu::Dual(u0), g.dyn_theta, out);
+    BF_UNROLL for (int i = 0; i < N; ++i) F[i * ld + d] = out[i].d;
+  }
+}
+#endif
+
+template <bool UNSC, bool USER = false>
 __device__ __forceinline__ void rts_gen_linearize(const RtsGen& c, const GenModel& g, float u0, long long t, const float* m,
                                                   const float* P, float* mp, float* Pp, float* X, float* W, float* tv, int tid,
                                                   const RtsUnscLds& ul) {
@@ -121,7 +167,14 @@ __device__ __forceinline__ void rts_gen_linearize(const RtsGen& c, const GenMode
   }
   const float* F;
   int ldf;
-  if (c.kind == RTS_EXT) {
+  if constexpr (USER) {
+#ifdef BF_USER_DYN
+    rts_gen_user_jacobian(g, m, u0, W, ld, tid);
+#endif
+    wave_lds_sync();
+    F = W;
+    ldf = ld;
+  } else if (c.kind == RTS_EXT) {
     gen_dyn_linearize<64>(g, m, u0, W, ld, tv, tid);
     wave_lds_sync();
     F = W;
@@ -194,8 +247,234 @@ __device__ __forceinline__ void rts_gen_solve_upper(int n, const float* W, float
     }
   }
 }
+
+// The smoother's run-time-dimension kernel (rts_smoother.hip states its LDS carve-up): one 64-lane workgroup per trajectory
+template <bool UNSC, bool USER>
+__device__ __forceinline__ void rts_generic_body(const RtsGen& c, const GenModel& g, const RtsViews& v, long long T) {
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const int n = c.n, ld = rts_gen_ld(n), nn = n * n;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* P = lds;
+  float* Ps = P + n * ld;
+  float* Pp = Ps + n * ld;
+  float* X = Pp + n * ld;
+  float* W = X + n * ld;
+  float* m = W + n * ld;
+  float* ms = m + n;
+  float* mp = ms + n;
+  float* tv = mp + n;
+  const RtsUnscLds ul = rts_unsc_carve(tv + n, tv + n + n * ld, tv + n + 2 * n * ld, n);  // carved for RTS_UNSC only
+  const bool want_c = v.Cs.p != nullptr;
+  auto at = [&](const SView& s, long long t, int e) { return b * s.sB + t * s.sT + e * s.sE; };
+
+  long long t = T - 1;
+  if (v.m_in) {
+    for (int e = tid; e < n; e += 64) ms[e] = v.m_in[b * n + e];
+    for (int e = tid; e < nn; e += 64) Ps[(e / n) * ld + e % n] = v.P_in[b * nn + e];
+  } else {
+    for (int e = tid; e < n; e += 64) { const float x = v.m.p[at(v.m, t, e)]; ms[e] = x; v.ms.p[at(v.ms, t, e)] = x; }
+    for (int e = tid; e < nn; e += 64) { const float x = v.P.p[at(v.P, t, e)]; Ps[(e / n) * ld + e % n] = x; v.Ps.p[at(v.Ps, t, e)] = x; }
+    --t;
+  }
+  wave_lds_sync();
+  for (; t >= 0; --t) {
+    for (int e = tid; e < n; e += 64) m[e] = v.m.p[at(v.m, t, e)];
+    for (int e = tid; e < nn; e += 64) P[(e / n) * ld + e % n] = v.P.p[at(v.P, t, e)];
+    if (c.kind != RTS_LIN_RECOMPUTE) {
+      for (int e = tid; e < n; e += 64) mp[e] = v.pm.p[at(v.pm, t, e)];
+      for (int e = tid; e < nn; e += 64) Pp[(e / n) * ld + e % n] = v.pP.p[at(v.pP, t, e)];
+    }
+    wave_lds_sync();
+    const float u0 = ((UNSC || USER || c.kind == RTS_EXT) && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+    rts_gen_linearize<UNSC, USER>(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid, ul);
+    rts_gen_chol(n, Pp, W, tid);
+    rts_gen_solve_lower(n, W, X, tid);  // X <- L^-T L^-1 X
+    rts_gen_solve_upper(n, W, X, tid);
+    wave_lds_sync();
+    if (want_c) {
+      for (int e = tid; e < nn; e += 64) {  // C = G P^s = X^T P^s
+        const int i = e / n, j = e - i * n;
+        float s = X[i] * Ps[j];
+        for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], Ps[k * ld + j], s);
+        v.Cs.p[at(v.Cs, t, e)] = s;
+      }
+    }
+    for (int i = tid; i < n; i += 64) tv[i] = ms[i] - mp[i];
+    wave_lds_sync();
+    for (int i = tid; i < n; i += 64) {
+      float s = X[i] * tv[0];
+      for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], tv[k], s);
+      ms[i] = m[i] + s;
+    }
+    for (int e = tid; e < nn; e += 64) {
+      const int i = e / n, j = e - i * n;
+      Ps[i * ld + j] = Ps[i * ld + j] - Pp[i * ld + j];
+    }
+    wave_lds_sync();
+    for (int e = tid; e < nn; e += 64) {  // G D -> P-
+      const int i = e / n, j = e - i * n;
+      float s = X[i] * Ps[j];
+      for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], Ps[k * ld + j], s);
+      Pp[i * ld + j] = s;
+    }
+    wave_lds_sync();
+    for (int e = tid; e < nn; e += 64) {  // P + (G D) G^T -> P, which becomes P^s
+      const int i = e / n, j = e - i * n;
+      float s = Pp[i * ld] * X[j];
+      for (int k = 1; k < n; ++k) s = fmaf(Pp[i * ld + k], X[k * ld + j], s);
+      P[i * ld + j] = P[i * ld + j] + s;
+    }
+    wave_lds_sync();
+    float* sw = P;
+    P = Ps;
+    Ps = sw;
+    for (int e = tid; e < n; e += 64) v.ms.p[at(v.ms, t, e)] = ms[e];
+    for (int e = tid; e < nn; e += 64) v.Ps.p[at(v.Ps, t, e)] = Ps[(e / n) * ld + e % n];
+    wave_lds_sync();
+  }
+  if (v.m_out) for (int e = tid; e < n; e += 64) v.m_out[b * n + e] = ms[e];
+  if (v.P_out) for (int e = tid; e < nn; e += 64) v.P_out[b * nn + e] = Ps[(e / n) * ld + e % n];
+}
+
+
+// The sampler's run-time-dimension kernel (ffbs_sampler.hip states its LDS carve-up): one 64-lane workgroup per trajectory
+template <bool UNSC, bool USER>
+__device__ __forceinline__ void ffbs_generic_body(const FfbsGen& fc, const GenModel& g, const FfbsViews& v, long long T) {
+  const RtsGen& c = fc.r;
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const int n = c.n, ld = rts_gen_ld(n), nn = n * n, S = fc.S, SB = fc.SB;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* P = lds;
+  float* Pp = P + n * ld;
+  float* X = Pp + n * ld;
+  float* W = X + n * ld;
+  float* Sg = W + n * ld;
+  float* m = Sg + n * ld;
+  float* mp = m + n;
+  float* tv = mp + n;
+  const RtsUnscLds ul = rts_unsc_carve(Sg, tv + n, tv + n + n * ld, n);  // carved for RTS_UNSC only
+  float* xs = tv + n + (UNSC ? n * ld + rts_unsc_vec_floats(n) : 0);  // x_{t+1} of the block, then x_{t+1} - m-
+  float* xi = xs + SB * n;   // the block's noise
+  float* xo = xi + SB * n;   // x_t of the block
+  const bool one_block = SB >= S;
+  const bool keyed = v.xi.p == nullptr;
+  uint32_t k0 = 0, k1 = 0;
+  if (keyed) {
+    k0 = v.keys[2 * b];
+    k1 = v.keys[2 * b + 1];
+  }
+  const uint32_t count = (uint32_t)S * (uint32_t)T * (uint32_t)n;
+  auto at = [&](const SView& s, long long t, int e) { return b * s.sB + t * s.sT + e * s.sE; };
+  auto xat = [&](const SView& s, int smp, long long t, int e) { return b * s.sB + smp * s.sK + t * s.sT + e * s.sE; };
+
+  // the samples of step t in blocks: first = the chunk's last step without a carry (x = m + Sg xi)
+  auto samples = [&](long long t, bool first) {
+    for (int sb0 = 0; sb0 < S; sb0 += SB) {
+      const int ne = ((S - sb0) < SB ? (S - sb0) : SB) * n;
+      for (int e = tid; e < ne; e += 64) {
+        const int sl = e / n, i = e - sl * n, smp = sb0 + sl;
+        xi[e] = keyed ? bits_to_normal(threefry_bits(k0, k1, ((uint32_t)smp * (uint32_t)T + (uint32_t)t) * (uint32_t)n + i, count))
+                      : v.xi.p[xat(v.xi, smp, t, i)];
+        if (!first) {
+          float xn;
+          if (t == T - 1) xn = v.x_in[((long long)b * S + smp) * n + i];
+          else if (one_block) xn = xs[e];
+          else xn = v.x.p[xat(v.x, smp, t + 1, i)];
+          xs[e] = xn - mp[i];
+        }
+      }
+      wave_lds_sync();
+      for (int e = tid; e < ne; e += 64) {
+        const int sl = e / n, i = e - sl * n;
+        const float* z = xi + sl * n;
+        float s;
+        if (first) {
+          s = Sg[i * ld] * z[0];
+          for (int k = 1; k <= i; ++k) s = fmaf(Sg[i * ld + k], z[k], s);
+        } else {
+          const float* dx = xs + sl * n;
+          s = X[i] * dx[0];
+          for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], dx[k], s);
+          for (int k = 0; k <= i; ++k) s = fmaf(Sg[i * ld + k], z[k], s);
+        }
+        const float xv = m[i] + s;
+        xo[e] = xv;
+        v.x.p[xat(v.x, sb0 + sl, t, i)] = xv;
+        if (t == 0 && v.x_out) v.x_out[((long long)b * S + sb0 + sl) * n + i] = xv;
+      }
+      wave_lds_sync();
+      if (one_block) {
+        float* sw = xs;
+        xs = xo;
+        xo = sw;
+      }
+    }
+  };
+  // Sg (lower triangle) <- psdchol(Sg; diag P); every lane forms the pivot itself
+  auto psd_factor = [&]() {
+    for (int j = 0; j < n; ++j) {
+      float p = Sg[j * ld + j];
+      for (int k = 0; k < j; ++k) p = fmaf(-Sg[j * ld + k], Sg[j * ld + k], p);
+      const bool keep = p > BF_FFBS_TAU * P[j * ld + j];
+      const float r = keep ? fast_sqrt(p) : 0.f;
+      const float inv = keep ? fast_rcp(r) : 0.f;
+      for (int i = j + 1 + tid; i < n; i += 64) {
+        float s = Sg[i * ld + j];
+        for (int k = 0; k < j; ++k) s = fmaf(-Sg[i * ld + k], Sg[j * ld + k], s);
+        Sg[i * ld + j] = keep ? s * inv : 0.f;
+      }
+      wave_lds_sync();  // the pivot's reads of row j are done before its diagonal changes
+      if (tid == 0) Sg[j * ld + j] = r;
+      wave_lds_sync();
+    }
+  };
+
+  long long t = T - 1;
+  if (!v.x_in) {
+    for (int e = tid; e < n; e += 64) m[e] = v.m.p[at(v.m, t, e)];
+    for (int e = tid; e < nn; e += 64) {
+      const float x = v.P.p[at(v.P, t, e)];
+      P[(e / n) * ld + e % n] = x;
+      Sg[(e / n) * ld + e % n] = x;
+    }
+    wave_lds_sync();
+    psd_factor();
+    samples(t, true);
+    --t;
+  }
+  for (; t >= 0; --t) {
+    for (int e = tid; e < n; e += 64) m[e] = v.m.p[at(v.m, t, e)];
+    for (int e = tid; e < nn; e += 64) P[(e / n) * ld + e % n] = v.P.p[at(v.P, t, e)];
+    if (c.kind != RTS_LIN_RECOMPUTE) {
+      for (int e = tid; e < n; e += 64) mp[e] = v.pm.p[at(v.pm, t, e)];
+      for (int e = tid; e < nn; e += 64) Pp[(e / n) * ld + e % n] = v.pP.p[at(v.pP, t, e)];
+    }
+    wave_lds_sync();
+    const float u0 = ((UNSC || USER || c.kind == RTS_EXT) && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+    rts_gen_linearize<UNSC, USER>(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid, ul);
+    rts_gen_chol(n, Pp, W, tid);
+    rts_gen_solve_lower(n, W, X, tid);  // X <- L^-1 X
+    wave_lds_sync();
+    for (int e = tid; e < nn; e += 64) {  // Sg = P - X^T X, lower triangle
+      const int i = e / n, j = e - i * n;
+      if (j > i) continue;
+      float s = P[i * ld + j];
+      for (int k = 0; k < n; ++k) s = fmaf(-X[k * ld + i], X[k * ld + j], s);
+      Sg[i * ld + j] = s;
+    }
+    wave_lds_sync();
+    rts_gen_solve_upper(n, W, X, tid);  // X <- L^-T X
+    wave_lds_sync();
+    psd_factor();
+    samples(t, false);
+  }
+}
+
 #endif
 
+#ifndef BF_JIT
 // ---- host side (defined in rts_smoother.hip) --------------------------------------------------------------------------
 int gen_fill(const bf_model* p, long long T, GenModel& g, std::vector<float>& blk);  // generic_scan.hip
 // A, G Q_s G^T for every step s of Q (zeros without Q), G q0 (lgssm_pack.hpp: the bits the filters upload)
@@ -226,6 +505,16 @@ inline RtsUnsc<N> rts_unsc_arg(const RtsUnscHost& h) {
   c.w = h.wu;
   return c;
 }
+// Source route: the kernel argument of the register kernels built at run time (RtsUser<DQ> of rts_smoother.hpp is its first
+// 64 + dq floats) and the largest n they serve: every instance up to it builds without scratch for the Lorenz-96 twin the
+// headers of rts_smoother.hip / ffbs_sampler.hip tabulate; above it the route goes to the LDS kernel
+enum { RTS_USER_REG_MAX = 8 };
+struct RtsUserHost {
+  float theta[64];
+  float q0[64];
+};
+int rts_user_fill(const bf_model* p, RtsUserHost& h);
+int rts_user_gen_model(const bf_model* p, GenModel& g, hipStream_t stream);   // q0 | theta uploaded, for the run-time-dimension kernels
 // uploads blk (content-keyed cache) and turns the offsets of c (linear kinds, RTS_UNSC) or g (RTS_EXT) into device pointers
 int rts_gen_upload(RtsGen& c, GenModel& g, const std::vector<float>& blk, hipStream_t stream);
 
@@ -259,5 +548,6 @@ inline EkfModel<N, 1> rts_ekf_arg(const bf_model* p, const GenModel& g) {
     case 7: return GO_(std::integral_constant<int, 7>{});        \
     default: return GO_(std::integral_constant<int, 8>{});       \
   }
+#endif  // BF_JIT
 
 }  // namespace bf

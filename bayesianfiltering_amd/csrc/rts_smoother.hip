@@ -14,6 +14,16 @@
 // VGPRs (arch + acc) / waves per SIMD: n = 1: 35 / 8, n = 2: 62 / 8, n = 3: 105 / 4, n = 4: 170 / 2, n = 5: 235 / 2,
 // n = 6: 346 / 1, n = 7: 447 / 1, n = 8: 496 / 1.  Run-time-dimension kernel: rts_generic_kernel<true> 130 VGPRs, 3 waves per
 // SIMD; rts_generic_kernel<false> (every other kind) 112 VGPRs, 4 waves, as before the route existed.
+//
+// Source route (RTS_EXT_USER: F_t from n dual-number evaluations of the caller's dynamics; kernels compiled at run time,
+// jit_source.hip JIT_RTS_REGS / JIT_RTS_GENERIC).  Measured on a Lorenz-96 twin written as source (a loop over BF_N, dq = n),
+// hipcc -Rpass-analysis=kernel-resource-usage, gfx950, -ffp-contract=off: every instance n = 1 ... 8 builds without scratch,
+// so the register limit of the route is 8 (RTS_USER_REG_MAX) for that function; a caller's function with more live values
+// may spill where this one does not.  VGPRs (arch + acc) / waves per SIMD, strided path: n = 1: 25 / 8, n = 2: 58 / 8,
+// n = 3: 82 / 5, n = 4: 135 / 3, n = 5: 207 / 2, n = 6: 280 / 1, n = 7: 438 / 1, n = 8: 420 / 1; staged path: n = 1: 94 / 5,
+// n = 2: 166 / 3, n = 3: 341 / 1, n = 4: 330 / 1.  Run-time-dimension kernel (lane d evaluates the function with the seed
+// in state direction d; the per-lane arrays are BF_N long): n = 3: 87 VGPRs / 5 waves, n = 10: 101 / 4, n = 64: 281 / 1, no
+// scratch.
 #include "rts_generic.hpp"
 #include "lgssm_pack.hpp"
 
@@ -26,97 +36,9 @@ namespace bf {
 // the helpers of rts_generic.hpp: W <- F_t, X = F P, [recompute: P-, m-], W <- chol(P-), X <- L^-T L^-1 X,
 // C = X^T P^s (straight to HBM), m^s <- m + X^T (m^s - m-), P^s <- P^s - P-, P- <- X^T (P^s), P <- P + P- X, swap P / P^s.
 // RTS_UNSC: two more matrices (the root's eigenvectors and the root) and the root's vectors (rts_generic.hpp: RtsUnscLds)
-static inline size_t rts_gen_lds_floats(int n, int kind) {
-  const size_t base = 5 * (size_t)n * rts_gen_ld(n) + 4 * (size_t)n;
-  return kind == RTS_UNSC ? base + 2 * (size_t)n * rts_gen_ld(n) + (size_t)rts_unsc_vec_floats(n) : base;
-}
-
 template <bool UNSC>
 __global__ void __launch_bounds__(64) rts_generic_kernel(RtsGen c, GenModel g, RtsViews v, long long T) {
-  const int tid = threadIdx.x;
-  const long long b = blockIdx.x;
-  const int n = c.n, ld = rts_gen_ld(n), nn = n * n;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* P = lds;
-  float* Ps = P + n * ld;
-  float* Pp = Ps + n * ld;
-  float* X = Pp + n * ld;
-  float* W = X + n * ld;
-  float* m = W + n * ld;
-  float* ms = m + n;
-  float* mp = ms + n;
-  float* tv = mp + n;
-  const RtsUnscLds ul = rts_unsc_carve(tv + n, tv + n + n * ld, tv + n + 2 * n * ld, n);  // carved for RTS_UNSC only
-  const bool want_c = v.Cs.p != nullptr;
-  auto at = [&](const SView& s, long long t, int e) { return b * s.sB + t * s.sT + e * s.sE; };
-
-  long long t = T - 1;
-  if (v.m_in) {
-    for (int e = tid; e < n; e += 64) ms[e] = v.m_in[b * n + e];
-    for (int e = tid; e < nn; e += 64) Ps[(e / n) * ld + e % n] = v.P_in[b * nn + e];
-  } else {
-    for (int e = tid; e < n; e += 64) { const float x = v.m.p[at(v.m, t, e)]; ms[e] = x; v.ms.p[at(v.ms, t, e)] = x; }
-    for (int e = tid; e < nn; e += 64) { const float x = v.P.p[at(v.P, t, e)]; Ps[(e / n) * ld + e % n] = x; v.Ps.p[at(v.Ps, t, e)] = x; }
-    --t;
-  }
-  wave_lds_sync();
-  for (; t >= 0; --t) {
-    for (int e = tid; e < n; e += 64) m[e] = v.m.p[at(v.m, t, e)];
-    for (int e = tid; e < nn; e += 64) P[(e / n) * ld + e % n] = v.P.p[at(v.P, t, e)];
-    if (c.kind != RTS_LIN_RECOMPUTE) {
-      for (int e = tid; e < n; e += 64) mp[e] = v.pm.p[at(v.pm, t, e)];
-      for (int e = tid; e < nn; e += 64) Pp[(e / n) * ld + e % n] = v.pP.p[at(v.pP, t, e)];
-    }
-    wave_lds_sync();
-    const float u0 = ((UNSC || c.kind == RTS_EXT) && v.u) ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
-    rts_gen_linearize<UNSC>(c, g, u0, t, m, P, mp, Pp, X, W, tv, tid, ul);
-    rts_gen_chol(n, Pp, W, tid);
-    rts_gen_solve_lower(n, W, X, tid);  // X <- L^-T L^-1 X
-    rts_gen_solve_upper(n, W, X, tid);
-    wave_lds_sync();
-    if (want_c) {
-      for (int e = tid; e < nn; e += 64) {  // C = G P^s = X^T P^s
-        const int i = e / n, j = e - i * n;
-        float s = X[i] * Ps[j];
-        for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], Ps[k * ld + j], s);
-        v.Cs.p[at(v.Cs, t, e)] = s;
-      }
-    }
-    for (int i = tid; i < n; i += 64) tv[i] = ms[i] - mp[i];
-    wave_lds_sync();
-    for (int i = tid; i < n; i += 64) {
-      float s = X[i] * tv[0];
-      for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], tv[k], s);
-      ms[i] = m[i] + s;
-    }
-    for (int e = tid; e < nn; e += 64) {
-      const int i = e / n, j = e - i * n;
-      Ps[i * ld + j] = Ps[i * ld + j] - Pp[i * ld + j];
-    }
-    wave_lds_sync();
-    for (int e = tid; e < nn; e += 64) {  // G D -> P-
-      const int i = e / n, j = e - i * n;
-      float s = X[i] * Ps[j];
-      for (int k = 1; k < n; ++k) s = fmaf(X[k * ld + i], Ps[k * ld + j], s);
-      Pp[i * ld + j] = s;
-    }
-    wave_lds_sync();
-    for (int e = tid; e < nn; e += 64) {  // P + (G D) G^T -> P, which becomes P^s
-      const int i = e / n, j = e - i * n;
-      float s = Pp[i * ld] * X[j];
-      for (int k = 1; k < n; ++k) s = fmaf(Pp[i * ld + k], X[k * ld + j], s);
-      P[i * ld + j] = P[i * ld + j] + s;
-    }
-    wave_lds_sync();
-    float* sw = P;
-    P = Ps;
-    Ps = sw;
-    for (int e = tid; e < n; e += 64) v.ms.p[at(v.ms, t, e)] = ms[e];
-    for (int e = tid; e < nn; e += 64) v.Ps.p[at(v.Ps, t, e)] = Ps[(e / n) * ld + e % n];
-    wave_lds_sync();
-  }
-  if (v.m_out) for (int e = tid; e < n; e += 64) v.m_out[b * n + e] = ms[e];
-  if (v.P_out) for (int e = tid; e < nn; e += 64) v.P_out[b * nn + e] = Ps[(e / n) * ld + e % n];
+  rts_generic_body<UNSC, false>(c, g, v, T);
 }
 
 // ---- host helpers --------------------------------------------------------------------------------------------------
@@ -219,29 +141,39 @@ static inline bool rts_ref_stream(const SView& s, long long E, long long rows) {
 static Option g_rts_load_mode{-1, OPT_RTS_LOAD_MODE};
 Option& rts_load_mode_option() { return g_rts_load_mode; }
 
+// The data path of a register launch: staged for whole waves of contiguous reference rows (stage_ok: RtsStage<N>::OK), strided
+// otherwise.  Without a carry the cross-covariances have T-1 entries: their rows may be T-1 steps long as well as T (the kernel
+// takes the row pitch from the view and never touches entry T-1; rts_ref_stream's ((T-1) E) % 4 test keeps every row on 16 bytes)
+static int rts_pick_path(int n, bool stage_ok, bool load_pred, const RtsViews& v, long long B, long long T, int load_mode, bool* staged) {
+  const bool cs_ok = rts_ref_stream(v.Cs, n * n, T) || (v.m_in == nullptr && T > 1 && rts_ref_stream(v.Cs, n * n, T - 1));
+  bool staged_ok = stage_ok && rts_ref_stream(v.m, n, T) && rts_ref_stream(v.P, n * n, T) && rts_ref_stream(v.ms, n, T) &&
+                   rts_ref_stream(v.Ps, n * n, T) && cs_ok;
+  if (load_pred) staged_ok = staged_ok && rts_ref_stream(v.pm, n, T) && rts_ref_stream(v.pP, n * n, T);
+  if (load_mode == RTS_STAGED && !staged_ok)
+    return set_error(BF_EINVAL, "rts_load_mode = 2 needs n <= 4 and the contiguous reference layout with 16-byte aligned rows");
+  *staged = staged_ok && load_mode != RTS_STRIDED && B >= 64;
+  return BF_OK;
+}
+
+// the views of the trajectories from b_begin on
+static RtsViews rts_shifted(const RtsViews& v, long long b_begin, int n) {
+  RtsViews w = v;
+  for (SView* s : {&w.m, &w.P, &w.pm, &w.pP, &w.ms, &w.Ps, &w.Cs}) if (s->p) s->p += b_begin * s->sB;
+  if (w.m_in) w.m_in += b_begin * n;
+  if (w.P_in) w.P_in += b_begin * n * n;
+  if (w.m_out) w.m_out += b_begin * n;
+  if (w.P_out) w.P_out += b_begin * n * n;
+  if (w.u) w.u += b_begin * w.u_sB;
+  return w;
+}
+
 template <int N, int KIND, class Arg>
 static int launch_rts_n(const Arg& c, const float* d_gqg, const RtsViews& v, long long B, long long T, int load_mode,
                         hipStream_t stream) {
   using S = RtsStage<N>;
-  // without a carry the cross-covariances have T-1 entries: their rows may be T-1 steps long as well as T (the kernel
-  // takes the row pitch from the view and never touches entry T-1; rts_ref_stream's ((T-1) E) % 4 test keeps every row on 16 bytes)
-  const bool cs_ok = rts_ref_stream(v.Cs, N * N, T) || (v.m_in == nullptr && T > 1 && rts_ref_stream(v.Cs, N * N, T - 1));
-  bool staged_ok = S::OK && rts_ref_stream(v.m, N, T) && rts_ref_stream(v.P, N * N, T) && rts_ref_stream(v.ms, N, T) &&
-                   rts_ref_stream(v.Ps, N * N, T) && cs_ok;
-  if (KIND != RTS_LIN_RECOMPUTE) staged_ok = staged_ok && rts_ref_stream(v.pm, N, T) && rts_ref_stream(v.pP, N * N, T);
-  if (load_mode == RTS_STAGED && !staged_ok)
-    return set_error(BF_EINVAL, "rts_load_mode = 2 needs n <= 4 and the contiguous reference layout with 16-byte aligned rows");
-  const bool staged = staged_ok && load_mode != RTS_STRIDED && B >= 64;
-  auto shifted = [&](long long b_begin) {
-    RtsViews w = v;
-    for (SView* s : {&w.m, &w.P, &w.pm, &w.pP, &w.ms, &w.Ps, &w.Cs}) if (s->p) s->p += b_begin * s->sB;
-    if (w.m_in) w.m_in += b_begin * N;
-    if (w.P_in) w.P_in += b_begin * N * N;
-    if (w.m_out) w.m_out += b_begin * N;
-    if (w.P_out) w.P_out += b_begin * N * N;
-    if (w.u) w.u += b_begin * w.u_sB;
-    return w;
-  };
+  bool staged = false;
+  const int rc = rts_pick_path(N, S::OK, KIND != RTS_LIN_RECOMPUTE, v, B, T, load_mode, &staged);
+  if (rc != BF_OK) return rc;
   long long b_main = 0;
   if constexpr (S::OK && KIND != RTS_UNSC) {  // (the unscented route is compute-bound: strided loads only)
     if (staged) {
@@ -254,7 +186,7 @@ static int launch_rts_n(const Arg& c, const float* d_gqg, const RtsViews& v, lon
   if (b_main < B) {
     const long long nb = B - b_main;
     hipLaunchKernelGGL((rts_reg_kernel<N, RTS_STRIDED, KIND, Arg>), dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, stream, c,
-                       d_gqg, shifted(b_main), nb, T);
+                       d_gqg, rts_shifted(v, b_main, N), nb, T);
   }
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;
@@ -314,8 +246,12 @@ int launch_rts_linear(const bf_lgssm* p, const RtsViews& v, long long B, long lo
   return launch_rts_generic(c, g, blk, v, B, T, stream);
 }
 
+int launch_rts_user(const bf_model* p, const RtsViews& v, long long B, long long T, bool force_generic, int load_mode,
+                    hipStream_t stream);
+
 int launch_rts_ext(const bf_model* p, const RtsViews& v, long long B, long long T, bool force_generic, int load_mode,
                    hipStream_t stream) {
+  if (p->user && p->dyn_id == BF_FN_USER) return launch_rts_user(p, v, B, T, force_generic, load_mode, stream);
   GenModel g;
   std::vector<float> blk;
   int rc = gen_fill(p, T, g, blk);  // validates the registry ids and theta layouts
@@ -334,6 +270,94 @@ int launch_rts_ext(const bf_model* p, const RtsViews& v, long long B, long long 
   c.n = n;
   c.kind = RTS_EXT;
   return launch_rts_generic(c, g, blk, v, B, T, stream);
+}
+
+// ---- source route (RTS_EXT_USER): the register kernels compiled at run time around the caller's dynamics ------------------
+// (RTS_USER_REG_MAX, rts_generic.hpp: the largest n of the route on the register kernels -- every instance up to it, both
+// data paths of the smoother and the four samples-per-lane counts of the sampler, builds without scratch for the Lorenz-96
+// twin written as source; header comment)
+int rts_user_fill(const bf_model* p, RtsUserHost& h) {
+  std::memset(&h, 0, sizeof(h));
+  if (p->n_dyn_theta > 64)
+    return set_error(BF_EUNSUPPORTED, "smoother / sampler: a dynamics function from source takes at most 64 parameters (got %d)", p->n_dyn_theta);
+  for (int i = 0; i < p->n_dyn_theta; ++i) h.theta[i] = p->dyn_theta[i];
+  for (int i = 0; i < p->dq; ++i) h.q0[i] = p->q0 ? p->q0[i] : 0.f;
+  return BF_OK;
+}
+
+// the run-time-dimension kernels' constants of the source route: q0 | theta on the device, g.q0 / g.dyn_theta pointing into it
+int rts_user_gen_model(const bf_model* p, GenModel& g, hipStream_t stream) {
+  std::memset(&g, 0, sizeof(g));
+  g.dyn_id = DYN_USER; g.emi_id = p->emi_id; g.n = p->n; g.dq = p->dq; g.m = p->m; g.dr = p->dr;
+  const int nth = p->n_dyn_theta > 0 ? p->n_dyn_theta : 0;
+  std::vector<float> blk((size_t)p->dq + nth + 1, 0.f);
+  for (int i = 0; i < p->dq; ++i) blk[i] = p->q0 ? p->q0[i] : 0.f;
+  for (int i = 0; i < nth; ++i) blk[(size_t)p->dq + i] = p->dyn_theta[i];
+  const void* dv = nullptr;
+  const int rc = device_constants(blk.data(), sizeof(float) * blk.size(), stream, &dv);
+  if (rc != BF_OK) return rc;
+  g.q0 = static_cast<const float*>(dv);
+  g.dyn_theta = g.q0 + p->dq;
+  return BF_OK;
+}
+
+static int launch_rts_user_generic(const bf_model* p, const RtsViews& v, long long B, long long T, hipStream_t stream) {
+  const int n = p->n;
+  const size_t lds = sizeof(float) * rts_gen_lds_floats(n, RTS_EXT_USER);
+  if (lds > 160 * 1024) return set_error(BF_EUNSUPPORTED, "smoother: n = %d needs %zu bytes of LDS (160 KiB per workgroup)", n, lds);
+  if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "smoother: B too large for the run-time-dimension kernel");
+  RtsGen c;
+  std::memset(&c, 0, sizeof(c));
+  c.n = n;
+  c.kind = RTS_EXT_USER;
+  GenModel g;
+  int rc = rts_user_gen_model(p, g, stream);
+  if (rc != BF_OK) return rc;
+  hipFunction_t fn = nullptr;
+  if ((rc = user_kernel(p->user, JIT_RTS_GENERIC, 0, 0, JIT_SPEC_USER, &fn)) != BF_OK) return rc;
+  RtsViews w = v;
+  long long T_ = T;
+  void* args[] = {&c, &g, &w, &T_};
+  return launch_user_kernel(p->user, 64, (unsigned)B, lds, stream, args, fn);
+}
+
+int launch_rts_user(const bf_model* p, const RtsViews& v, long long B, long long T, bool force_generic, int load_mode,
+                    hipStream_t stream) {
+  const int n = p->n;
+  if (force_generic || n > RTS_USER_REG_MAX) {
+    if (load_mode == RTS_STAGED) return set_error(BF_EINVAL, "rts_load_mode = 2 needs n <= 4 on the register kernel");
+    return launch_rts_user_generic(p, v, B, T, stream);
+  }
+  RtsUserHost h;
+  int rc = rts_user_fill(p, h);
+  if (rc != BF_OK) return rc;
+  bool staged = false;
+  size_t stage_bytes = 0;
+  auto dims = [&](auto NC) -> int {
+    using S = RtsStage<decltype(NC)::value>;
+    stage_bytes = sizeof(float) * S::FLOATS;
+    return rts_pick_path(decltype(NC)::value, S::OK, true, v, B, T, load_mode, &staged);
+  };
+  auto pick = [&]() -> int { BF_RTS_DIMS(n, dims) };
+  if ((rc = pick()) != BF_OK) return rc;
+  long long b_main = 0, T_ = T;
+  if (staged) {  // whole waves; a ragged remainder goes through the strided kernel, as in launch_rts_n
+    hipFunction_t fn = nullptr;
+    if ((rc = user_kernel(p->user, JIT_RTS_REGS, RTS_STAGED, 0, JIT_SPEC_USER, &fn)) != BF_OK) return rc;
+    b_main = (B / 64) * 64;
+    RtsViews w = v;
+    void* args[] = {&h, &w, &b_main, &T_};
+    BF_HIP_CHECK(hipModuleLaunchKernel(fn, (unsigned)(b_main / 64), 1, 1, 64, 1, 1, (unsigned)stage_bytes, stream, args, nullptr));
+  }
+  if (b_main < B) {
+    hipFunction_t fn = nullptr;
+    if ((rc = user_kernel(p->user, JIT_RTS_REGS, RTS_STRIDED, 0, JIT_SPEC_USER, &fn)) != BF_OK) return rc;
+    long long nb = B - b_main;
+    RtsViews w = rts_shifted(v, b_main, n);
+    void* args[] = {&h, &w, &nb, &T_};
+    BF_HIP_CHECK(hipModuleLaunchKernel(fn, (unsigned)((nb + 63) / 64), 1, 1, 64, 1, 1, 0, stream, args, nullptr));
+  }
+  return BF_OK;
 }
 
 // Largest n of the unscented route on the register kernel: every instance up to it builds without scratch (header comment)

@@ -37,8 +37,17 @@
 //                chunk's loads are issued into registers before the current chunk is computed (double buffering: the
 //                registers are the second buffer) and land in LDS after the flush.
 // Run-time-dimension kernel (rts_smoother.hip): one wave per trajectory, state in LDS, for every other n.
+//
+// Source route (RTS_EXT_USER; bf_eks_smoother_f32 / bf_effbs_sample_f32 with dynamics given as source): F_t is the Jacobian
+// of the caller's dynamics(x, q, u, theta, out) with respect to the state at (m_t, q0, u_t) by forward-mode dual numbers,
+// the Jacobian the filter's predict used at step t.  This file and ffbs_sampler.hpp are embedded in the library
+// (jit_embed.py) and compiled by hiprtc around the caller's source (jit_source.hip: JIT_RTS_REGS / JIT_FFBS_REGS), so they
+// stay self-contained under BF_JIT: device code only, after bf_views.hpp, kf_math.hpp, scan_common.hpp, bf_rng.hpp,
+// models.hpp and ugsf_scan.hpp.
 #pragma once
+#ifndef BF_JIT
 #include "bf_common.hpp"
+#endif
 #include "kf_math.hpp"
 #include "models.hpp"
 #include "scan_common.hpp"
@@ -47,7 +56,7 @@
 namespace bf {
 
 enum { RTS_STRIDED = 0, RTS_STAGED = 2 };
-enum { RTS_LIN = 0, RTS_LIN_RECOMPUTE = 1, RTS_EXT = 2, RTS_UNSC = 3 };
+enum { RTS_LIN = 0, RTS_LIN_RECOMPUTE = 1, RTS_EXT = 2, RTS_UNSC = 3, RTS_EXT_USER = 4 };
 
 // Linear dynamics: A, G Q G^T (constant part), G q0.
 template <int N>
@@ -66,6 +75,15 @@ struct RtsUnsc {
   float A[N * N];
   float Gq0[N];
   float c, w;
+};
+
+// Source route (RTS_EXT_USER): what the caller's dynamics(x, q, u, theta, out) reads besides the state and the input -- its
+// parameters (at most 64, the register filter's limit) and the noise bias q0.  Nothing of the registry.
+template <int DQ_>
+struct RtsUser {
+  static constexpr int DQ = DQ_;
+  float theta[64];
+  float q0[DQ_];
 };
 
 struct RtsViews {
@@ -179,6 +197,25 @@ __device__ __forceinline__ void rts_unsc_cross(const RtsUnsc<N>& c, float u0, co
   BF_UNROLL for (int i = 0; i < N * N; ++i) X[i] *= c.w;
 }
 
+#ifdef BF_USER_DYN
+// F_t of the source route: the Jacobian of the caller's dynamics with respect to the state at (m_t, q0, u_t), by forward-mode
+// dual numbers (jit_source.hip) -- one evaluation per state direction, n in all: F_q and Q never enter the backward pass.
+// The seed loop is fully unrolled, so every index into the per-lane arrays is a compile-time constant (no scratch).
+template <int N, class Arg>
+__device__ __forceinline__ void rts_user_jacobian(const Arg& c, float u0, const float* m, float* F) {
+  constexpr int DQ = Arg::DQ;
+  bfu::Dual xd[N], qd[DQ], od[N];
+  BF_UNROLL for (int i = 0; i < N; ++i) xd[i] = bfu::Dual(m[i]);
+  BF_UNROLL for (int i = 0; i < DQ; ++i) qd[i] = bfu::Dual(c.q0[i]);
+  BF_UNROLL for (int s = 0; s < N; ++s) {
+    xd[s].d = 1.f;
+    bfu::dynamics<bfu::Dual>(xd, qd, bfu::Dual(u0), c.theta, od);
+    xd[s].d = 0.f;
+    BF_UNROLL for (int i = 0; i < N; ++i) F[i * N + s] = od[i].d;
+  }
+}
+#endif
+
 // F_t P_t (RTS_UNSC: X_t from the sigma points) and, for the recompute path, m-_{t+1} = A m + G q0,
 // P-_{t+1} = (A P) A^T + G Q_t G^T (kf_math.hpp's predict_cov association).
 template <int N, int KIND, class Arg>
@@ -188,7 +225,11 @@ __device__ __forceinline__ void rts_linearize(const Arg& c, const float* gqg_t, 
     rts_unsc_cross<N>(c, u0, m, P, X);
   } else {
     float F[N * N];
-    if constexpr (KIND == RTS_EXT) {
+    if constexpr (KIND == RTS_EXT_USER) {
+#ifdef BF_USER_DYN
+      rts_user_jacobian<N>(c, u0, m, F);
+#endif
+    } else if constexpr (KIND == RTS_EXT) {
       float fx[N];
       dyn_linearize<N, 1>(c, m, u0, F, fx);
     } else {
@@ -242,9 +283,11 @@ __device__ __forceinline__ void tile_flush(const float* tile, float* base, long 
   }
 }
 
+// (the body is a device function: the ahead-of-time instances below and the entry points compiled at run time around the
+// caller's dynamics, jit_source.hip, are both thin kernels around it)
 template <int N, int MODE, int KIND, class Arg>
-__global__ void __launch_bounds__(64) rts_reg_kernel(Arg c, const float* __restrict__ gqg_t, RtsViews v, long long B,
-                                                     long long T) {
+__device__ __forceinline__ void rts_reg_body(const Arg& c, const float* __restrict__ gqg_t, const RtsViews& v, long long B,
+                                             long long T) {
   constexpr int NN = N * N;
   const int lane = threadIdx.x;
   const long long b0 = (long long)blockIdx.x * 64;
@@ -379,6 +422,12 @@ __global__ void __launch_bounds__(64) rts_reg_kernel(Arg c, const float* __restr
   }
   if (v.m_out) BF_UNROLL for (int i = 0; i < N; ++i) v.m_out[b * N + i] = ms[i];
   if (v.P_out) BF_UNROLL for (int i = 0; i < NN; ++i) v.P_out[b * NN + i] = Ps[i];
+}
+
+template <int N, int MODE, int KIND, class Arg>
+__global__ void __launch_bounds__(64) rts_reg_kernel(Arg c, const float* __restrict__ gqg_t, RtsViews v, long long B,
+                                                     long long T) {
+  rts_reg_body<N, MODE, KIND, Arg>(c, gqg_t, v, B, T);
 }
 
 }  // namespace bf

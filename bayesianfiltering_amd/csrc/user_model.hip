@@ -53,10 +53,28 @@ int user_kernel(const bf_user_model* handle, int kind, int ppt, int nw, int spec
   bf_user_model* um = const_cast<bf_user_model*>(handle);
   int rc = check_user_device(um);
   if (rc != BF_OK) return rc;
-  const int key = ((kind * 10 + spec) * 100 + ppt) * 100 + nw;
+  auto key_of = [&](int variant) { return ((kind * 10 + spec) * 100 + variant) * 100 + nw; };
+  const int key = key_of(ppt);
   std::lock_guard<std::mutex> lock(g_mu);
   auto it = um->kernels.find(key);
   if (it != um->kernels.end()) {
+    *fn = it->second;
+    return BF_OK;
+  }
+  if (kind == JIT_RTS_REGS || kind == JIT_FFBS_REGS) {
+    // the smoother's data paths / the sampler's samples-per-lane counts (ppt) share one module: a build fills the map for all
+    const bool rts = kind == JIT_RTS_REGS;
+    const int variants[4] = {rts ? 0 : 1, 2, 4, 8};
+    const int nv = rts ? 2 : 4;
+    hipFunction_t f[4] = {nullptr, nullptr, nullptr, nullptr};
+    const std::string src = jit_source(*um, kind, 0, nw, spec);
+    rc = rts ? jit_load(src, {{jit_entry_name(kind, 0), &f[0]}, {jit_entry_name(kind, 2), &f[1]}})
+             : jit_load(src, {{jit_entry_name(kind, 1), &f[0]}, {jit_entry_name(kind, 2), &f[1]}, {jit_entry_name(kind, 4), &f[2]},
+                              {jit_entry_name(kind, 8), &f[3]}});
+    if (rc != BF_OK) return rc;
+    for (int i = 0; i < nv; ++i) um->kernels[key_of(variants[i])] = f[i];
+    it = um->kernels.find(key);
+    if (it == um->kernels.end()) return set_error(BF_EINVAL, "no such variant of the kernel (kind %d, variant %d)", kind, ppt);
     *fn = it->second;
     return BF_OK;
   }

@@ -9,7 +9,8 @@
 #include "bf_common.hpp"
 
 // kernels compiled at run time around the caller's functions -- or around the registry's, for dimensions without a compiled instance
-enum bf_jit_kind { JIT_GSF_GENERIC, JIT_BPF, JIT_UGSF, JIT_AGSF_UKF, JIT_AGSF_EKF, JIT_GSF_REGS, JIT_SAMPLE, JIT_BPF_BIG, JIT_UGSF_GENERIC };
+enum bf_jit_kind { JIT_GSF_GENERIC, JIT_BPF, JIT_UGSF, JIT_AGSF_UKF, JIT_AGSF_EKF, JIT_GSF_REGS, JIT_SAMPLE, JIT_BPF_BIG, JIT_UGSF_GENERIC,
+                   JIT_RTS_REGS, JIT_FFBS_REGS, JIT_RTS_GENERIC, JIT_FFBS_GENERIC };   // the smoother's / the posterior sampler's kernels around dynamics from source
 // the model structure a sampling kernel is compiled for: the handle's own functions, or (registry models) bpf_scan.hpp's specs
 enum bf_jit_spec { JIT_SPEC_USER = 0, JIT_SPEC_RUNTIME = 1, JIT_SPEC_L96_PICK = 2 };
 
@@ -20,7 +21,7 @@ struct bf_user_model {
   bool hw_arith = false;                  // internal handle of bf_set_option "bpf_arith" = 1: registry functions, hardware transcendentals
   std::string dyn_src, emi_src, lp_src;  // kept: all kernels but the run-time-dimension scan are built on first use
   hipFunction_t k64 = nullptr, k256 = nullptr;   // the run-time-dimension Gaussian-sum scan, built at creation when f or h is given
-  std::map<int, hipFunction_t> kernels;   // built on first use, by (kind, spec, particles per thread, waves): user_kernel
+  std::map<int, hipFunction_t> kernels;   // built on first use, by (kind, spec, particles per thread -- the smoother's data path / the sampler's samples per lane --, waves): user_kernel
   int user_flags() const { return (has_dyn ? 1 : 0) | (has_emi ? 2 : 0) | (has_lp ? 4 : 0); }   // fill_*_model_view's user_flags
 };
 
@@ -34,7 +35,7 @@ int jit_load(const std::string& src, std::initializer_list<std::pair<const char*
 
 // ---- jit_source.hip: the text hiprtc compiles for one kernel of a handle, and that kernel's entry point
 std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int spec);
-const char* jit_entry_name(int kind);
+const char* jit_entry_name(int kind, int variant = 0);   // variant: the data path (JIT_RTS_REGS) / samples per lane (JIT_FFBS_REGS)
 
 // ---- user_model.hip
 int check_user_model(const bf_user_model* um, const bf_model* p);   // the handle was created for this model's dimensions and functions

@@ -12,9 +12,9 @@ from typing import NamedTuple, Optional, Any
 import numpy as np
 
 from . import _lib
-from .inference import (_torch, _dev_f32, _host_f32, _alloc_stream, _stream_desc, _Model, kalman_filter,
+from .inference import (_torch, _dev_f32, _host_f32, _alloc_stream, _stream_desc, _Model, _param_dims, kalman_filter,
                         gaussian_sum_filter, unscented_gaussian_sum_filter)
-from .nonlinearities import DYN_LINEAR, require_device_function
+from .nonlinearities import DYN_LINEAR, DeviceFunction, require_device_function
 from .smoother import _LinearDynamics, _batched, _FILTER_KW, _ukf_params, _inputs_desc
 
 
@@ -47,16 +47,22 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
     ``key``: ``keys = random.split(key, B)`` (a (B, 2) array of keys is taken as it is) and trajectory b uses
     ``random.normal(keys[b], (S, T, n))``; chunked calls take a key per chunk.
     Linear dynamics run ``bf_ffbs_sample_f32`` (without the predicted streams in ``posterior`` they are recomputed);
-    other registry dynamics run ``bf_effbs_sample_f32`` and need them, ``extended=True`` sends a linear model there too.
+    other registry dynamics, ``nonlinearities.user_dynamics`` source and plain Python functions (recorded at the model's
+    dimensions) run ``bf_effbs_sample_f32`` and need them, ``extended=True`` sends a linear model there too.
     ``uparams`` (a :class:`ParamsUKF` or a 3-tuple): the posterior is ``unscented_gaussian_sum_filter``'s with one component
     and the gain uses the sigma-point cross-covariance of the filter's predict (``bf_uffbs_sample_f32``, the contract and
-    its float32 error model as in :func:`rts_smoother`); it needs the predicted streams and excludes ``extended=True``.
+    its float32 error model as in :func:`rts_smoother`; registry dynamics only); it needs the predicted streams and excludes
+    ``extended=True``.
     ``carry``: the :class:`SamplerCarry` returned (``return_carry=True``) by the sampling of the steps that FOLLOW these.
     ``out``: a tensor a previous call returned, reused.  ``device`` must name the device the posterior's streams live on.
     ``options``: e.g. ``{"ffbs_spl": 4}``, ``{"force_generic": 1}``.
     """
     torch = _torch()
-    f = require_device_function(params.dynamics_function, "dynamics", "params.dynamics_function")
+    f = params.dynamics_function
+    if not isinstance(f, DeviceFunction):  # a plain Python function is recorded at the model's dimensions, as the filters do
+        n0, dq0, _ = _param_dims(params)
+        f = require_device_function(f, "dynamics", "params.dynamics_function", n0, dq0)
+    f = require_device_function(f, "dynamics", "params.dynamics_function")
     means, covs = posterior.means, posterior.covariances
     if means is None or covs is None:
         raise ValueError("the sampler needs the filtered means and covariances")

@@ -11,9 +11,9 @@ from typing import NamedTuple, Optional, Any
 import numpy as np
 
 from . import _lib
-from .inference import (_torch, _dev_f32, _host_f32, _fp, _alloc_stream, _stream_desc, _time_varying, _Model,
+from .inference import (_torch, _dev_f32, _host_f32, _fp, _alloc_stream, _stream_desc, _time_varying, _Model, _param_dims,
                         _check_out_tensor, kalman_filter, gaussian_sum_filter, unscented_gaussian_sum_filter, ParamsUKF)
-from .nonlinearities import DYN_LINEAR, require_device_function
+from .nonlinearities import DYN_LINEAR, DeviceFunction, require_device_function
 
 
 class PosteriorGaussianSmoothed(NamedTuple):
@@ -90,12 +90,14 @@ def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariance
 
     Linear dynamics (``linear_dynamics``) run ``bf_rts_smoother_f32``; without ``predicted_means`` /
     ``predicted_covariances`` in ``posterior`` the predictions are recomputed from the filtered streams.  Other registry
-    dynamics run ``bf_eks_smoother_f32`` (F_t = the Jacobian at the filtered mean and ``inputs``, as the filter's predict
-    used it) and need the predicted streams; ``extended=True`` sends a linear model there too.
+    dynamics, ``nonlinearities.user_dynamics`` source and plain Python functions (recorded at the model's dimensions, as
+    the filters record them) run ``bf_eks_smoother_f32`` (F_t = the Jacobian at the filtered mean and ``inputs``, as the
+    filter's predict used it; by forward-mode dual numbers for functions from source, in kernels built on first use) and
+    need the predicted streams; ``extended=True`` sends a linear model there too.
     ``uparams`` (a :class:`ParamsUKF` or a 3-tuple): the posterior is ``unscented_gaussian_sum_filter``'s with one component
     and the backward gain uses the sigma-point cross-covariance of the filter's predict (``bf_uks_smoother_f32``; the
     contract is in csrc/rts_smoother.hpp); it needs the predicted streams and excludes ``extended=True``.  For linear
-    dynamics it is the linear smoother's function of the streams.  The cross-covariance is a float32 difference of
+    dynamics it is the linear smoother's function of the streams; it serves registry dynamics only.  The cross-covariance is a float32 difference of
     sigma-point images: its relative error grows like 2^-24 |f(m)| / (alpha sqrt(n + dq + kappa) |P|^1/2), 1e-4 ... 2e-4
     at alpha = 1e-3.
     ``carry``: the :class:`SmootherCarry` returned (``return_carry=True``) by the smoothing of the steps that FOLLOW
@@ -107,7 +109,11 @@ def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariance
     before a kernel is launched.  Returns :class:`PosteriorGaussianSmoothed` (and the carry when ``return_carry``).
     """
     torch = _torch()
-    f = require_device_function(params.dynamics_function, "dynamics", "params.dynamics_function")
+    f = params.dynamics_function
+    if not isinstance(f, DeviceFunction):  # a plain Python function is recorded at the model's dimensions, as the filters do
+        n0, dq0, _ = _param_dims(params)
+        f = require_device_function(f, "dynamics", "params.dynamics_function", n0, dq0)
+    f = require_device_function(f, "dynamics", "params.dynamics_function")
     means, covs = posterior.means, posterior.covariances
     if means is None or covs is None:
         raise ValueError("the smoother needs the filtered means and covariances")

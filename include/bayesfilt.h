@@ -130,15 +130,18 @@ int bf_device_count(void);
  *                   same three-term bf16 products); it has no option.
  *   "force_generic": 1 = bf_kalman_filter_f32 / bf_gsf_ekf_f32 run the run-time-dimension kernel (any n, m, K; state in
  *                   LDS) even where a compile-time-dimension instance exists (test hook; default 0).  The smoothers
- *                   (bf_rts_smoother_f32, bf_eks_smoother_f32) honour it the same way.
+ *                   (bf_rts_smoother_f32, bf_eks_smoother_f32) honour it the same way, bf_eks_smoother_f32 / bf_effbs_sample_f32
+ *                   also for dynamics given as source (the run-time-dimension kernel built around them).
  *   "agsf_force_generic": 1 = bf_agsf_ekf_f32 / bf_agsf_ukf_f32 run the run-time-dimension kernel (the node in turn in LDS, up
  *                   to 256 leaves per trajectory, registry functions) even where every dimension is <= 8 (default 0): the two
  *                   kernels on one model, or more than 64 leaves at 5 <= n <= 8.
  *   "rts_load_mode": the smoothers' data path: -1 = choose from the layout (default), 0 = strided per-lane loads and
- *                   stores, 2 = LDS-staged time chunks (contiguous reference layout, n <= 4 only).
+ *                   stores, 2 = LDS-staged time chunks (contiguous reference layout, n <= 4 only); dynamics given as
+ *                   source follow the same rule.
  *   "ffbs_spl":     samples per lane of the posterior samplers' register kernel (n <= 8): 0 = the smallest compiled count that holds all S
  *                   samples of a trajectory in one lane, 8 for S > 8 (default),
- *                   otherwise one of the compiled counts 1, 2, 4, 8 (the arithmetic of a sample does not depend on it).
+ *                   otherwise one of the compiled counts 1, 2, 4, 8 (the arithmetic of a sample does not depend on it);
+ *                   the kernels built around dynamics given as source have the same four counts.
  *   "gsf_structured": 1 (default) lets bf_gsf_ekf_f32 use the structure-aware kernel instances
  *                   (banded Lorenz-96 Jacobian, selection emission) when the model qualifies;
  *                   0 forces the dense generic instances.
@@ -430,9 +433,15 @@ int bf_smoother_abi_check(size_t sizeof_smooth_desc, size_t sizeof_smooth_carry)
 int bf_rts_smoother_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T,
                         const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream);
 
-/* Extended RTS smoother for registry dynamics (K = 1; the streams of bf_gsf_ekf_f32 with one component).
- * pred_means / pred_covs are required.  u: the filter's inputs (NULL or u->ptr == NULL = zeros).
- * BF_EUNSUPPORTED for functions given as source (BF_FN_USER) and for model->flags != 0. */
+/* Extended RTS smoother (K = 1; the streams of bf_gsf_ekf_f32 with one component) for registry dynamics and for dynamics
+ * given as source.  pred_means / pred_covs are required.  u: the filter's inputs (NULL or u->ptr == NULL = zeros).
+ * Dynamics from source (model->user with dyn_id = BF_FN_USER): F_t is the Jacobian of the caller's dynamics with respect to
+ * the state at (m_t, q0, u_t) by forward-mode dual numbers, the one the filter's predict used; the kernels are compiled by
+ * hiprtc on first use through the handle -- n <= 8: registers, one lane per trajectory, both data paths ("rts_load_mode"),
+ * at most 64 parameters; larger n and "force_generic": one workgroup per trajectory, state in LDS.  BF_EINVAL for a handle
+ * made for other dimensions or another device.  A handle that holds only the emission (or a log-density) runs the registry
+ * instances: a backward pass never reads the emission.  BF_EUNSUPPORTED for BF_FN_USER without a handle and for
+ * model->flags != 0.  (The unscented smoother below and bf_pf_backward_sample_f32 do not serve dynamics from source.) */
 int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
                         const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream);
 
@@ -497,8 +506,11 @@ int bf_sampler_abi_check(size_t sizeof_sample_desc, size_t sizeof_sample_carry);
 int bf_ffbs_sample_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T, int32_t S,
                        const bf_sample_carry* carry, const bf_sample_desc* out, void* stream);
 
-/* Posterior samples for registry dynamics (extended Kalman streams, pred_* required).  BF_EUNSUPPORTED for functions
- * given as source (BF_FN_USER) and for model->flags != 0. */
+/* Posterior samples over extended Kalman streams (pred_* required) for registry dynamics and for dynamics given as source
+ * (model->user with dyn_id = BF_FN_USER: F_t by dual numbers as in bf_eks_smoother_f32, kernels compiled on first use; n <= 8:
+ * registers at every "ffbs_spl" count, larger n and "force_generic": state in LDS; BF_EINVAL for a handle made for other
+ * dimensions or another device; a handle holding only the emission runs the registry instances).  BF_EUNSUPPORTED for
+ * BF_FN_USER without a handle and for model->flags != 0.  (bf_uffbs_sample_f32 does not serve dynamics from source.) */
 int bf_effbs_sample_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
                         int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream);
 
