@@ -1,5 +1,6 @@
 // C-ABI entry points (include/bayesfilt.h).  Validation and dispatch only; the kernels live in
-// the kf_*/gsf_*/bpf_* translation units.
+// the kf_*/gsf_*/bpf_* translation units.  (The smoothers' and the samplers' entry points sit with
+// their launchers: rts_smoother.hip, ffbs_sampler.hip, pf_sampler.hip.)
 #include <cstring>
 #include "bf_common.hpp"
 #include "user_model.hpp"
@@ -54,16 +55,6 @@ int launch_sample_ssm(const bf_bpf_model* bp, const uint32_t* d_keys, const bf_c
 int launch_resample(const float* d_w, const uint32_t* d_keys, long long B, int NP, int resampler, int* d_idx,
                     hipStream_t stream);
 
-struct RtsViews;
-int launch_rts_linear(const bf_lgssm* p, const RtsViews& v, long long B, long long T, bool recompute, bool force_generic,
-                      int load_mode, hipStream_t stream);
-int launch_rts_ext(const bf_model* p, const RtsViews& v, long long B, long long T, bool force_generic, int load_mode,
-                   hipStream_t stream);
-int launch_rts_unsc(const bf_model* p, const bf_ukf_params* up, const RtsViews& v, long long B, long long T, bool force_generic,
-                    int load_mode, hipStream_t stream);
-int rts_views(const bf_out_desc* f, const bf_smooth_carry* carry, const bf_smooth_desc* out, const bf_cstream* u, long long B,
-              long long T, int n, bool need_pred, int (*launch)(const RtsViews&, void*), void* ctx);
-
 CallOverrides& call_overrides() {
   static thread_local CallOverrides c = {};
   return c;
@@ -101,7 +92,7 @@ __global__ void canon_eval_kernel(int op, const float* __restrict__ in, long lon
 Option& rts_load_mode_option();  // rts_smoother.hip: -1 = from the layout, 0 = strided, 2 = LDS-staged
 static Option g_kf_small_mode{1, OPT_KF_SMALL_MODE};   // bf_set_option "kf_small_mode": 1 = one-wave matrix-core kernel for 9 <= n <= 32 (default), 0 = off
 static Option g_force_generic{0, OPT_FORCE_GENERIC};  // 1 = run the run-time-dimension kernel even where a compiled instance exists
-Option& force_generic_option() { return g_force_generic; }  // read by the samplers' entry points (ffbs_sampler.hip)
+Option& force_generic_option() { return g_force_generic; }  // read by the backward family's entry points (backward_host.hpp)
 Option& ffbs_spl_option();  // ffbs_sampler.hip: 0 = from S and n, else samples per lane of the register kernel
 
 // A shape / option the compiled instances do not cover falls through to the run-time-dimension kernel
@@ -128,25 +119,11 @@ int bf_abi_check(int32_t header_version, size_t sizeof_out_desc, size_t sizeof_l
                  size_t sizeof_bpf_model, size_t sizeof_bpf_out) {
   if (header_version / 100 != BF_VERSION / 100)
     return bf::set_error(BF_EINVAL, "binding was written against header version %d, the library is %d", (int)header_version, BF_VERSION);
-#define BF_ABI_SIZE(NAME_, T_)                                                                                  \
-  if (NAME_ != 0 && NAME_ != sizeof(T_)) \
-    return bf::set_error(BF_EINVAL, "binding's sizeof(" #T_ ") = %zu, the library's is %zu: the struct layouts differ", NAME_, sizeof(T_));
   BF_ABI_SIZE(sizeof_out_desc, bf_out_desc)
   BF_ABI_SIZE(sizeof_lgssm, bf_lgssm)
   BF_ABI_SIZE(sizeof_model, bf_model)
   BF_ABI_SIZE(sizeof_bpf_model, bf_bpf_model)
   BF_ABI_SIZE(sizeof_bpf_out, bf_bpf_out)
-#undef BF_ABI_SIZE
-  return BF_OK;
-}
-
-int bf_smoother_abi_check(size_t sizeof_smooth_desc, size_t sizeof_smooth_carry) {
-#define BF_ABI_SIZE(NAME_, T_)                                                                                  \
-  if (NAME_ != 0 && NAME_ != sizeof(T_)) \
-    return bf::set_error(BF_EINVAL, "binding's sizeof(" #T_ ") = %zu, the library's is %zu: the struct layouts differ", NAME_, sizeof(T_));
-  BF_ABI_SIZE(sizeof_smooth_desc, bf_smooth_desc)
-  BF_ABI_SIZE(sizeof_smooth_carry, bf_smooth_carry)
-#undef BF_ABI_SIZE
   return BF_OK;
 }
 
@@ -398,72 +375,6 @@ int bf_collapse_f32(const bf_stream* weights, const bf_stream* means, const bf_s
   if (B <= 0 || T <= 0 || K <= 0 || n <= 0) return bf::set_error(BF_EINVAL, "non-positive size");
   if (!mean_out && !cov_out) return bf::set_error(BF_EINVAL, "nothing to compute");
   return bf::launch_collapse(weights, means, covs, B, T, K, n, mean_out, cov_out, static_cast<hipStream_t>(stream));
-}
-
-int bf_rts_smoother_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T,
-                        const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream) {
-  bf::CallOptionScope call_option_scope;
-  if (!model || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
-  if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
-  if (model->n <= 0 || model->dq <= 0) return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->A) return bf::set_error(BF_EINVAL, "A is required");
-  if (!model->G && model->dq != model->n) return bf::set_error(BF_EINVAL, "G == NULL requires dq == n");
-  const bool has_pm = filtered->pred_means.ptr != nullptr, has_pP = filtered->pred_covs.ptr != nullptr;
-  if (has_pm != has_pP) return bf::set_error(BF_EINVAL, "pred_means and pred_covs are given together or not at all");
-  const bool recompute = !has_pm;
-  if (recompute) {
-    if (!model->Q) return bf::set_error(BF_EINVAL, "recomputing the predictions needs Q");
-    if (model->Q_steps < 1 || (model->Q_steps > 1 && model->Q_steps != T))
-      return bf::set_error(BF_EINVAL, "Q_steps must be 1 or T = %lld", (long long)T);
-  }
-  struct Ctx { const bf_lgssm* p; long long B, T; bool recompute; hipStream_t s; } ctx{model, B, T, recompute, static_cast<hipStream_t>(stream)};
-  return bf::rts_views(filtered, carry, out, nullptr, B, T, model->n, false, [](const bf::RtsViews& v, void* c) {
-    const Ctx& x = *static_cast<const Ctx*>(c);
-    return bf::launch_rts_linear(x.p, v, x.B, x.T, x.recompute, bf::g_force_generic.load() != 0, bf::rts_load_mode_option().load(), x.s);
-  }, &ctx);
-}
-
-int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
-                        const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream) {
-  bf::CallOptionScope call_option_scope;
-  if (!model || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
-  if (!model->user && (model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER))
-    return bf::set_error(BF_EUNSUPPORTED, "the extended smoother serves functions given as source through bf_model.user (bf_user_model_create); it is NULL");
-  if (model->flags != 0)
-    return bf::set_error(BF_EUNSUPPORTED, "the extended smoother needs the JAX path's update -> predict streams (flags = 0)");
-  if (model->user) {  // dynamics from source: the kernels built around them; an emission from source is never read
-    int rc = bf::check_user_model(model->user, model);
-    if (rc == BF_OK && model->dyn_id == BF_FN_USER) rc = bf::check_user_device(model->user);
-    if (rc != BF_OK) return rc;
-  }
-  if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
-    return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
-  struct Ctx { const bf_model* p; long long B, T; hipStream_t s; } ctx{model, B, T, static_cast<hipStream_t>(stream)};
-  return bf::rts_views(filtered, carry, out, u, B, T, model->n, true, [](const bf::RtsViews& v, void* c) {
-    const Ctx& x = *static_cast<const Ctx*>(c);
-    return bf::launch_rts_ext(x.p, v, x.B, x.T, bf::g_force_generic.load() != 0, bf::rts_load_mode_option().load(), x.s);
-  }, &ctx);
-}
-
-int bf_uks_smoother_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* u, const bf_out_desc* filtered,
-                        int64_t B, int64_t T, const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream) {
-  bf::CallOptionScope call_option_scope;
-  if (!model || !uparams || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
-  if (model->user || model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER)
-    return bf::set_error(BF_EUNSUPPORTED, "the unscented smoother serves registry dynamics; functions given as source are not supported");
-  if (model->flags != 0)
-    return bf::set_error(BF_EUNSUPPORTED, "the unscented smoother needs the JAX path's update -> predict streams (flags = 0)");
-  if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
-    return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
-  struct Ctx { const bf_model* p; const bf_ukf_params* up; long long B, T; hipStream_t s; } ctx{model, uparams, B, T, static_cast<hipStream_t>(stream)};
-  return bf::rts_views(filtered, carry, out, u, B, T, model->n, true, [](const bf::RtsViews& v, void* c) {
-    const Ctx& x = *static_cast<const Ctx*>(c);
-    return bf::launch_rts_unsc(x.p, x.up, v, x.B, x.T, bf::g_force_generic.load() != 0, bf::rts_load_mode_option().load(), x.s);
-  }, &ctx);
 }
 
 int bf_bpf_f32(const bf_bpf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t N,

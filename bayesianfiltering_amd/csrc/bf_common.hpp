@@ -22,6 +22,11 @@ int set_error(int code, const char* fmt, ...);
                              __FILE__, __LINE__);                                            \
   } while (0)
 
+// in a bf_*_abi_check: a binding's struct size (0 = not stated) against the library's
+#define BF_ABI_SIZE(NAME_, T_)           \
+  if (NAME_ != 0 && NAME_ != sizeof(T_)) \
+    return ::bf::set_error(BF_EINVAL, "binding's sizeof(" #T_ ") = %zu, the library's is %zu: the struct layouts differ", NAME_, sizeof(T_));
+
 // A tuning option: a process-wide default (bf_set_option) that ONE call can override (bf_set_call_option arms an override on
 // the calling thread; the next filter entry point on that thread reads it and disarms every override when it returns), so
 // that one caller's choices never leak into another caller's launches.  Reads behave like the std::atomic<int> it replaces.

@@ -1,5 +1,8 @@
-// Host side of the posterior sampler (ffbs_sampler.hpp): the two C entry points, the register instances for n <= 8 and
-// the run-time-dimension kernel for every other n (one wave per trajectory, matrices and a block of samples in LDS).
+// Host side of the posterior sampler (ffbs_sampler.hpp): its three C entry points, the run-time-dimension kernel (one wave
+// per trajectory, matrices and a block of samples in LDS) and the sampler as a product of the backward family's dispatch --
+// the launches of the register instances for n <= 8 at a samples-per-lane count, and of the run-time-dimension kernel for
+// every other n.  The model validation, the route resolution and the register-versus-run-time-dimension decision are shared
+// with the smoother: backward_host.hpp.
 //
 // Register instances (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): every instance, n = 1 ... 8, SPL = 1, 2, 4, 8 samples
 // per lane, all three dynamics kinds, builds without scratch.  VGPRs (arch + acc) / waves per SIMD, range over the kinds:
@@ -18,8 +21,8 @@
 // 6b (n = 4, B = 65 536, S = 8 and 64): SPL = 8 was the fastest there except in noise mode at S = 64.
 //
 // Unscented route (RTS_UNSC: X_t through rts_linearize, the root and the sigma-point images before the factorization): every
-// instance n = 1 ... 8 at every SPL builds without scratch, so the register limit is 8 for all four counts
-// (ffbs_unsc_reg_max).  VGPRs (arch + acc) / waves per SIMD:
+// instance n = 1 ... 8 at every SPL builds without scratch, so the family's register limit of 8 holds at all four
+// counts (BACKWARD_REG_MAX).  VGPRs (arch + acc) / waves per SIMD:
 //   n    SPL = 1    SPL = 2    SPL = 4    SPL = 8
 //   1    72 / 7     101 / 4    145 / 3    102 / 4
 //   2    80 / 6     102 / 4    98 / 4     130 / 3
@@ -33,8 +36,8 @@
 // kind) 116 VGPRs, 4 waves, as before the route existed.
 //
 // Source route (RTS_EXT_USER, kernels compiled at run time: jit_source.hip JIT_FFBS_REGS / JIT_FFBS_GENERIC), measured on a
-// Lorenz-96 twin written as source (dq = n, -ffp-contract=off): every instance builds without scratch, so the register limit
-// is 8 at all four counts (RTS_USER_REG_MAX).  VGPRs (arch + acc) / waves per SIMD:
+// Lorenz-96 twin written as source (dq = n, -ffp-contract=off): every instance builds without scratch, so the family's register
+// limit of 8 holds at all four counts (BACKWARD_REG_MAX).  VGPRs (arch + acc) / waves per SIMD:
 //   n    SPL = 1    SPL = 2    SPL = 4    SPL = 8
 //   1    65 / 7     93 / 5     137 / 3    99 / 4
 //   2    62 / 8     90 / 5     85 / 5     117 / 4
@@ -45,8 +48,7 @@
 //   7    246 / 2    272 / 1    306 / 1    372 / 1
 //   8    336 / 1    292 / 1    328 / 1    398 / 1
 // Run-time-dimension kernel: n = 3: 83 VGPRs / 5 waves, n = 10: 97 / 4, n = 64: 315 / 1, no scratch.
-#include "ffbs_sampler.hpp"
-#include "rts_generic.hpp"
+#include "backward_host.hpp"
 
 namespace bf {
 
@@ -67,39 +69,12 @@ __global__ void __launch_bounds__(64) ffbs_generic_kernel(FfbsGen fc, GenModel g
 static Option g_ffbs_spl{0, OPT_FFBS_SPL};
 Option& ffbs_spl_option() { return g_ffbs_spl; }
 
-// Largest n of the unscented route on the register kernel for a samples-per-lane count: every instance up to it builds
-// without scratch (header comment).  All four counts reach n = 8.
-constexpr int ffbs_unsc_reg_max(int /* spl */) { return 8; }
-
 // the smallest compiled count that holds all S samples of a trajectory in one lane, 8 for S > 8 (header comment)
 static int ffbs_pick_spl(int S, int forced) {
   if (forced) return forced;
   int spl = 1;
   while (spl < 8 && spl < S) spl *= 2;
   return spl;
-}
-
-template <int N, int KIND, class Arg>
-static int launch_ffbs_n(const Arg& c, const float* d_gqg, const FfbsViews& v, long long B, long long T, int S, int forced_spl,
-                         hipStream_t stream) {
-  const int spl = ffbs_pick_spl(S, forced_spl);
-  const long long lanes = B * ((S + spl - 1) / spl);
-  if ((lanes + 63) / 64 > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B x S too large for one launch");
-  const dim3 grid((unsigned)((lanes + 63) / 64));
-  // an unscented instance exists only up to its SPL's limit (ffbs_unsc_reg_max; the host sends the rest to the other kernel)
-  auto go = [&](auto SC) {
-    constexpr int SPL = decltype(SC)::value;
-    if constexpr (KIND != RTS_UNSC || N <= ffbs_unsc_reg_max(SPL))
-      hipLaunchKernelGGL((ffbs_reg_kernel<N, SPL, KIND, Arg>), grid, dim3(64), 0, stream, c, d_gqg, v, B, T, S);
-  };
-  switch (spl) {
-    case 1: go(std::integral_constant<int, 1>{}); break;
-    case 2: go(std::integral_constant<int, 2>{}); break;
-    case 4: go(std::integral_constant<int, 4>{}); break;
-    default: go(std::integral_constant<int, 8>{}); break;
-  }
-  BF_HIP_CHECK(hipGetLastError());
-  return BF_OK;
 }
 
 // c.SB and the LDS bytes of the run-time-dimension kernel; BF_EUNSUPPORTED with the byte count when 160 KiB do not hold the model
@@ -124,143 +99,85 @@ static int ffbs_gen_plan(FfbsGen& c, size_t* lds_bytes) {
   return BF_OK;
 }
 
-static int launch_ffbs_generic(const FfbsGen& c0, const GenModel& g, const std::vector<float>& blk, const FfbsViews& v,
-                               long long B, long long T, hipStream_t stream) {
-  const int kind = c0.r.kind;
-  FfbsGen c = c0;
-  size_t lds = 0;
-  const int prc = ffbs_gen_plan(c, &lds);
-  if (prc != BF_OK) return prc;
-  GenModel gg = g;
-  const int rc = rts_gen_upload(c.r, gg, blk, stream);
-  if (rc != BF_OK) return rc;
-  if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B too large for the run-time-dimension kernel");
-  auto kern = kind == RTS_UNSC ? ffbs_generic_kernel<true> : ffbs_generic_kernel<false>;
-  if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), lds, stream, c, gg, v, T);
-  BF_HIP_CHECK(hipGetLastError());
-  return BF_OK;
-}
+// The sampler as a product of backward_dispatch (backward_host.hpp): the four launches of one call
+struct FfbsProduct {
+  const FfbsViews& v;
+  long long B, T;
+  int S, forced_spl;
+  hipStream_t stream;
 
-static int launch_ffbs_linear(const bf_lgssm* p, const FfbsViews& v, long long B, long long T, int S, bool recompute,
-                              bool force_generic, int spl, hipStream_t stream) {
-  const int n = p->n;
-  std::vector<float> A, GQG, Gq0;
-  rts_lin_fill(p, A, GQG, Gq0);
-  const bool tv = recompute && p->Q_steps > 1;
-  if (!force_generic && n <= 8) {
-    const float* d_gqg = nullptr;
-    if (tv) {
-      const void* dv = nullptr;
-      const int rc = device_constants(GQG.data(), sizeof(float) * GQG.size(), stream, &dv);
-      if (rc != BF_OK) return rc;
-      d_gqg = static_cast<const float*>(dv);
-    }
-    auto go = [&](auto NC) -> int {
-      constexpr int N = decltype(NC)::value;
-      const RtsLin<N> c = rts_lin_arg<N>(A, GQG, Gq0);
-      if (recompute) return launch_ffbs_n<N, RTS_LIN_RECOMPUTE>(c, d_gqg, v, B, T, S, spl, stream);
-      return launch_ffbs_n<N, RTS_LIN>(c, nullptr, v, B, T, S, spl, stream);
-    };
-    BF_RTS_DIMS(n, go)
+  // samples per lane of the register kernels and their grid
+  int lanes_grid(int* spl, unsigned* grid) const {
+    *spl = ffbs_pick_spl(S, forced_spl);
+    const long long lanes = B * ((S + *spl - 1) / *spl);
+    if ((lanes + 63) / 64 > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B x S too large for one launch");
+    *grid = (unsigned)((lanes + 63) / 64);
+    return BF_OK;
   }
-  std::vector<float> blk;
-  FfbsGen c;
-  std::memset(&c, 0, sizeof(c));
-  rts_gen_lin_block(p, recompute, A, GQG, Gq0, c.r, blk);
-  c.S = S;
-  GenModel g;
-  std::memset(&g, 0, sizeof(g));
-  return launch_ffbs_generic(c, g, blk, v, B, T, stream);
-}
 
-// Source route (RTS_EXT_USER): the register kernel compiled at run time around the caller's dynamics, one entry point per
-// samples-per-lane count (jit_source.hip: JIT_FFBS_REGS)
-static int launch_ffbs_user(const bf_model* p, const FfbsViews& v, long long B, long long T, int S, bool force_generic, int forced_spl,
-                            hipStream_t stream) {
-  const int n = p->n;
-  if (force_generic || n > RTS_USER_REG_MAX) {  // the run-time-dimension kernel (JIT_FFBS_GENERIC), launch_ffbs_generic's LDS plan
-    FfbsGen c;
-    std::memset(&c, 0, sizeof(c));
-    c.r.n = n;
-    c.r.kind = RTS_EXT_USER;
-    c.S = S;
+  template <int N, int KIND, class Arg>
+  int regs(const Arg& c, const float* d_gqg) const {
+    int spl;
+    unsigned grid;
+    const int rc = lanes_grid(&spl, &grid);
+    if (rc != BF_OK) return rc;
+    auto go = [&](auto SC) {
+      constexpr int SPL = decltype(SC)::value;
+      hipLaunchKernelGGL((ffbs_reg_kernel<N, SPL, KIND, Arg>), dim3(grid), dim3(64), 0, stream, c, d_gqg, v, B, T, S);
+    };
+    switch (spl) {
+      case 1: go(std::integral_constant<int, 1>{}); break;
+      case 2: go(std::integral_constant<int, 2>{}); break;
+      case 4: go(std::integral_constant<int, 4>{}); break;
+      default: go(std::integral_constant<int, 8>{}); break;
+    }
+    BF_HIP_CHECK(hipGetLastError());
+    return BF_OK;
+  }
+
+  // the register kernel compiled at run time around the caller's dynamics, one entry point per samples-per-lane count
+  // (jit_source.hip: JIT_FFBS_REGS)
+  int user_regs(const bf_user_model* um, int /* n */, RtsUserHost& h) const {
+    int spl;
+    unsigned grid;
+    int rc = lanes_grid(&spl, &grid);
+    if (rc != BF_OK) return rc;
+    hipFunction_t fn = nullptr;
+    if ((rc = user_kernel(um, JIT_FFBS_REGS, spl, 0, JIT_SPEC_USER, &fn)) != BF_OK) return rc;
+    FfbsViews w = v;
+    long long B_ = B, T_ = T;
+    int S_ = S;
+    void* args[] = {&h, &w, &B_, &T_, &S_};
+    BF_HIP_CHECK(hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, stream, args, nullptr));
+    return BF_OK;
+  }
+
+  int generic(const RtsGen& r, const GenModel& g, const std::vector<float>& blk) const {
+    FfbsGen c{r, S, 0};
     size_t lds = 0;
     int rc = ffbs_gen_plan(c, &lds);
     if (rc != BF_OK) return rc;
+    GenModel gg = g;
+    if ((rc = rts_gen_upload(c.r, gg, blk, stream)) != BF_OK) return rc;
     if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B too large for the run-time-dimension kernel");
-    GenModel g;
-    if ((rc = rts_user_gen_model(p, g, stream)) != BF_OK) return rc;
-    hipFunction_t fn = nullptr;
-    if ((rc = user_kernel(p->user, JIT_FFBS_GENERIC, 0, 0, JIT_SPEC_USER, &fn)) != BF_OK) return rc;
+    auto kern = r.kind == RTS_UNSC ? ffbs_generic_kernel<true> : ffbs_generic_kernel<false>;
+    if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), lds, stream, c, gg, v, T);
+    BF_HIP_CHECK(hipGetLastError());
+    return BF_OK;
+  }
+
+  int user_generic(const bf_model* p, const RtsGen& r) const {  // (jit_source.hip: JIT_FFBS_GENERIC)
+    FfbsGen c{r, S, 0};
+    size_t lds = 0;
+    const int rc = ffbs_gen_plan(c, &lds);
+    if (rc != BF_OK) return rc;
     FfbsViews w = v;
-    long long T_ = T;
-    void* args[] = {&c, &g, &w, &T_};
-    return launch_user_kernel(p->user, 64, (unsigned)B, lds, stream, args, fn);
+    return backward_launch_user_generic(p, JIT_FFBS_GENERIC, "sampler", &c, &w, B, T, lds, stream);
   }
-  RtsUserHost h;
-  int rc = rts_user_fill(p, h);
-  if (rc != BF_OK) return rc;
-  const int spl = ffbs_pick_spl(S, forced_spl);
-  const long long lanes = B * ((S + spl - 1) / spl);
-  if ((lanes + 63) / 64 > 0x7fffffffLL) return set_error(BF_EINVAL, "sampler: B x S too large for one launch");
-  hipFunction_t fn = nullptr;
-  if ((rc = user_kernel(p->user, JIT_FFBS_REGS, spl, 0, JIT_SPEC_USER, &fn)) != BF_OK) return rc;
-  FfbsViews w = v;
-  long long B_ = B, T_ = T;
-  int S_ = S;
-  void* args[] = {&h, &w, &B_, &T_, &S_};
-  BF_HIP_CHECK(hipModuleLaunchKernel(fn, (unsigned)((lanes + 63) / 64), 1, 1, 64, 1, 1, 0, stream, args, nullptr));
-  return BF_OK;
-}
+};
 
-static int launch_ffbs_ext(const bf_model* p, const FfbsViews& v, long long B, long long T, int S, bool force_generic, int spl,
-                           hipStream_t stream) {
-  if (p->user && p->dyn_id == BF_FN_USER) return launch_ffbs_user(p, v, B, T, S, force_generic, spl, stream);
-  GenModel g;
-  std::vector<float> blk;
-  int rc = gen_fill(p, T, g, blk);  // validates the registry ids and theta layouts
-  if (rc != BF_OK) return rc;
-  const int n = p->n;
-  if (!force_generic && n <= 8) {
-    auto go = [&](auto NC) -> int {
-      constexpr int N = decltype(NC)::value;
-      return launch_ffbs_n<N, RTS_EXT>(rts_ekf_arg<N>(p, g), nullptr, v, B, T, S, spl, stream);
-    };
-    BF_RTS_DIMS(n, go)
-  }
-  FfbsGen c;
-  std::memset(&c, 0, sizeof(c));
-  c.r.n = n;
-  c.r.kind = RTS_EXT;
-  c.S = S;
-  return launch_ffbs_generic(c, g, blk, v, B, T, stream);
-}
-
-static int launch_ffbs_unsc(const bf_model* p, const bf_ukf_params* up, const FfbsViews& v, long long B, long long T, int S,
-                            bool force_generic, int spl, hipStream_t stream) {
-  RtsUnscHost h;
-  int rc = rts_unsc_fill(p, up, h);
-  if (rc != BF_OK) return rc;
-  const int n = p->n;
-  if (!force_generic && n <= ffbs_unsc_reg_max(ffbs_pick_spl(S, spl))) {
-    auto go = [&](auto NC) -> int {
-      constexpr int N = decltype(NC)::value;
-      return launch_ffbs_n<N, RTS_UNSC>(rts_unsc_arg<N>(h), nullptr, v, B, T, S, spl, stream);
-    };
-    BF_RTS_DIMS(n, go)
-  }
-  FfbsGen c;
-  std::memset(&c, 0, sizeof(c));
-  std::vector<float> blk;
-  if ((rc = rts_gen_unsc_block(h, n, c.r, blk)) != BF_OK) return rc;
-  c.S = S;
-  GenModel g;
-  std::memset(&g, 0, sizeof(g));
-  return launch_ffbs_generic(c, g, blk, v, B, T, stream);
-}
-
-// bf_out_desc / bf_sample_carry / bf_sample_desc -> FfbsViews, with the checks both entry points share
+// bf_out_desc / bf_sample_carry / bf_sample_desc -> FfbsViews, with the checks the three entry points share
 static int ffbs_views(const bf_out_desc* f, const bf_sample_carry* carry, const bf_sample_desc* out, const bf_cstream* u,
                       long long B, long long T, int S, int n, bool need_pred, FfbsViews& v) {
   if (B <= 0 || T <= 0) return set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", B, T);
@@ -301,19 +218,18 @@ static int ffbs_spl_checked(int* spl) {
   return BF_OK;
 }
 
-Option& force_generic_option();  // bf_api.hip
+static int ffbs_run(const BackwardRoute& r, const FfbsViews& v, long long B, long long T, int S, int spl, void* stream) {
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  return backward_dispatch(r, force_generic_option().load() != 0, FfbsProduct{v, B, T, S, spl, s}, s);
+}
 
 }  // namespace bf
 
 extern "C" {
 
 int bf_sampler_abi_check(size_t sizeof_sample_desc, size_t sizeof_sample_carry) {
-#define BF_ABI_SIZE(NAME_, T_)                                                                                  \
-  if (NAME_ != 0 && NAME_ != sizeof(T_)) \
-    return bf::set_error(BF_EINVAL, "binding's sizeof(" #T_ ") = %zu, the library's is %zu: the struct layouts differ", NAME_, sizeof(T_));
   BF_ABI_SIZE(sizeof_sample_desc, bf_sample_desc)
   BF_ABI_SIZE(sizeof_sample_carry, bf_sample_carry)
-#undef BF_ABI_SIZE
   return BF_OK;
 }
 
@@ -321,67 +237,51 @@ int bf_ffbs_sample_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64
                        const bf_sample_carry* carry, const bf_sample_desc* out, void* stream) {
   bf::CallOptionScope call_option_scope;
   if (!model || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
-  if (model->n <= 0 || model->dq <= 0) return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->A) return bf::set_error(BF_EINVAL, "A is required");
-  if (!model->G && model->dq != model->n) return bf::set_error(BF_EINVAL, "G == NULL requires dq == n");
-  bf::FfbsViews v;
-  int rc = bf::ffbs_views(filtered, carry, out, nullptr, B, T, S, model->n, false, v);
+  int rc = bf::backward_check_lgssm(model);
   if (rc != BF_OK) return rc;
+  bf::FfbsViews v;
+  if ((rc = bf::ffbs_views(filtered, carry, out, nullptr, B, T, S, model->n, false, v)) != BF_OK) return rc;
   const bool recompute = v.pm.p == nullptr;
-  if (recompute) {
-    if (!model->Q) return bf::set_error(BF_EINVAL, "recomputing the predictions needs Q");
-    if (model->Q_steps < 1 || (model->Q_steps > 1 && model->Q_steps != T))
-      return bf::set_error(BF_EINVAL, "Q_steps must be 1 or T = %lld", (long long)T);
-  }
+  if (recompute && (rc = bf::backward_check_recompute(model, T)) != BF_OK) return rc;
   int spl;
   if ((rc = bf::ffbs_spl_checked(&spl)) != BF_OK) return rc;
   bf_lgssm lg = *model;
   if (!recompute || lg.Q_steps < 1) lg.Q_steps = 1;  // the table is read on the recompute path only
-  return bf::launch_ffbs_linear(&lg, v, B, T, S, recompute, bf::force_generic_option().load() != 0, spl,
-                                static_cast<hipStream_t>(stream));
+  bf::BackwardRoute r;
+  if ((rc = bf::backward_route(&lg, recompute, r)) != BF_OK) return rc;
+  return bf::ffbs_run(r, v, B, T, S, spl, stream);
 }
 
 int bf_effbs_sample_f32(const bf_model* model, const bf_cstream* u, const bf_out_desc* filtered, int64_t B, int64_t T,
                         int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream) {
   bf::CallOptionScope call_option_scope;
   if (!model || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
-  if (!model->user && (model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER))
-    return bf::set_error(BF_EUNSUPPORTED, "the extended sampler serves functions given as source through bf_model.user (bf_user_model_create); it is NULL");
-  if (model->flags != 0)
-    return bf::set_error(BF_EUNSUPPORTED, "the extended sampler needs the JAX path's update -> predict streams (flags = 0)");
-  if (model->user) {  // dynamics from source: the kernel built around them; an emission from source is never read
-    int rc = bf::check_user_model(model->user, model);
-    if (rc == BF_OK && model->dyn_id == BF_FN_USER) rc = bf::check_user_device(model->user);
-    if (rc != BF_OK) return rc;
-  }
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
-    return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
-  bf::FfbsViews v;
-  int rc = bf::ffbs_views(filtered, carry, out, u, B, T, S, model->n, true, v);
+  int rc = bf::backward_check_source(model, "extended sampler", false);
+  if (rc == BF_OK) rc = bf::backward_check_dims(model);
   if (rc != BF_OK) return rc;
+  bf::FfbsViews v;
+  if ((rc = bf::ffbs_views(filtered, carry, out, u, B, T, S, model->n, true, v)) != BF_OK) return rc;
   int spl;
   if ((rc = bf::ffbs_spl_checked(&spl)) != BF_OK) return rc;
-  return bf::launch_ffbs_ext(model, v, B, T, S, bf::force_generic_option().load() != 0, spl, static_cast<hipStream_t>(stream));
+  bf::BackwardRoute r;
+  if ((rc = bf::backward_route(model, T, r)) != BF_OK) return rc;
+  return bf::ffbs_run(r, v, B, T, S, spl, stream);
 }
 
 int bf_uffbs_sample_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* u, const bf_out_desc* filtered,
                         int64_t B, int64_t T, int32_t S, const bf_sample_carry* carry, const bf_sample_desc* out, void* stream) {
   bf::CallOptionScope call_option_scope;
   if (!model || !uparams || !filtered || !out) return bf::set_error(BF_EINVAL, "NULL argument");
-  if (model->user || model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER)
-    return bf::set_error(BF_EUNSUPPORTED, "the unscented sampler serves registry dynamics; functions given as source are not supported");
-  if (model->flags != 0)
-    return bf::set_error(BF_EUNSUPPORTED, "the unscented sampler needs the JAX path's update -> predict streams (flags = 0)");
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
-    return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
-  bf::FfbsViews v;
-  int rc = bf::ffbs_views(filtered, carry, out, u, B, T, S, model->n, true, v);
+  int rc = bf::backward_check_source(model, "unscented sampler", true);
+  if (rc == BF_OK) rc = bf::backward_check_dims(model);
   if (rc != BF_OK) return rc;
+  bf::FfbsViews v;
+  if ((rc = bf::ffbs_views(filtered, carry, out, u, B, T, S, model->n, true, v)) != BF_OK) return rc;
   int spl;
   if ((rc = bf::ffbs_spl_checked(&spl)) != BF_OK) return rc;
-  return bf::launch_ffbs_unsc(model, uparams, v, B, T, S, bf::force_generic_option().load() != 0, spl, static_cast<hipStream_t>(stream));
+  bf::BackwardRoute r;
+  if ((rc = bf::backward_route(model, uparams, r)) != BF_OK) return rc;
+  return bf::ffbs_run(r, v, B, T, S, spl, stream);
 }
 
 }  // extern "C"

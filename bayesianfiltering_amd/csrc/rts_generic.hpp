@@ -5,13 +5,9 @@
 // The kernel bodies live here as device functions: the ahead-of-time kernels (rts_smoother.hip, ffbs_sampler.hip) and the
 // entry points hiprtc compiles around a caller's dynamics (jit_source.hip: JIT_RTS_GENERIC / JIT_FFBS_GENERIC, the
 // RTS_EXT_USER route for n above the register limit and "force_generic" = 1) are thin kernels around them.  The file is
-// embedded for that purpose (jit_embed.py), so the host side stays behind #ifndef BF_JIT.
+// embedded for that purpose (jit_embed.py): device code and the structs and LDS sizes both sides read, nothing of the host
+// (the family's host side is backward_host.hpp).
 #pragma once
-#ifndef BF_JIT
-#include <cstring>
-#include <vector>
-#include "user_model.hpp"
-#endif
 #include "rts_smoother.hpp"
 #include "ffbs_sampler.hpp"
 #include "generic_device.hpp"
@@ -473,81 +469,5 @@ __device__ __forceinline__ void ffbs_generic_body(const FfbsGen& fc, const GenMo
 }
 
 #endif
-
-#ifndef BF_JIT
-// ---- host side (defined in rts_smoother.hip) --------------------------------------------------------------------------
-int gen_fill(const bf_model* p, long long T, GenModel& g, std::vector<float>& blk);  // generic_scan.hip
-// A, G Q_s G^T for every step s of Q (zeros without Q), G q0 (lgssm_pack.hpp: the bits the filters upload)
-void rts_lin_fill(const bf_lgssm* p, std::vector<float>& A, std::vector<float>& GQG, std::vector<float>& Gq0);
-// the linear kinds' constant block A | Gq0 | GQG[qs], with c's pointers as offsets into it
-void rts_gen_lin_block(const bf_lgssm* p, bool recompute, const std::vector<float>& A, const std::vector<float>& GQG,
-                       const std::vector<float>& Gq0, RtsGen& c, std::vector<float>& blk);
-// The unscented route's model on the host: the filter's own model fill (ugsf_scan.hpp: fill_ukf_model_view validates the
-// registry ids and forms the constants), reduced to what X_t reads.  BF_EINVAL for ParamsUKF values with L + lambda <= 0.
-struct RtsUnscHost {
-  int dyn_id;
-  float dth[8];
-  std::vector<float> A, Gq0;
-  float cu, wu;
-};
-int rts_unsc_fill(const bf_model* p, const bf_ukf_params* up, RtsUnscHost& h);
-// the run-time-dimension kernels' constant block A | Gq0 and c for RTS_UNSC; BF_EUNSUPPORTED for dynamics they do not hold
-int rts_gen_unsc_block(const RtsUnscHost& h, int n, RtsGen& c, std::vector<float>& blk);
-template <int N>
-inline RtsUnsc<N> rts_unsc_arg(const RtsUnscHost& h) {
-  RtsUnsc<N> c;
-  std::memset(&c, 0, sizeof(c));
-  c.dyn_id = h.dyn_id;
-  for (int i = 0; i < 8; ++i) c.dth[i] = h.dth[i];
-  std::memcpy(c.A, h.A.data(), sizeof(c.A));
-  std::memcpy(c.Gq0, h.Gq0.data(), sizeof(c.Gq0));
-  c.c = h.cu;
-  c.w = h.wu;
-  return c;
-}
-// Source route: the kernel argument of the register kernels built at run time (RtsUser<DQ> of rts_smoother.hpp is its first
-// 64 + dq floats) and the largest n they serve: every instance up to it builds without scratch for the Lorenz-96 twin the
-// headers of rts_smoother.hip / ffbs_sampler.hip tabulate; above it the route goes to the LDS kernel
-enum { RTS_USER_REG_MAX = 8 };
-struct RtsUserHost {
-  float theta[64];
-  float q0[64];
-};
-int rts_user_fill(const bf_model* p, RtsUserHost& h);
-int rts_user_gen_model(const bf_model* p, GenModel& g, hipStream_t stream);   // q0 | theta uploaded, for the run-time-dimension kernels
-// uploads blk (content-keyed cache) and turns the offsets of c (linear kinds, RTS_UNSC) or g (RTS_EXT) into device pointers
-int rts_gen_upload(RtsGen& c, GenModel& g, const std::vector<float>& blk, hipStream_t stream);
-
-template <int N>
-inline RtsLin<N> rts_lin_arg(const std::vector<float>& A, const std::vector<float>& GQG, const std::vector<float>& Gq0) {
-  RtsLin<N> c;
-  std::memcpy(c.A, A.data(), sizeof(c.A));
-  std::memcpy(c.GQG, GQG.data(), sizeof(c.GQG));
-  std::memcpy(c.Gq0, Gq0.data(), sizeof(c.Gq0));
-  return c;
-}
-template <int N>
-inline EkfModel<N, 1> rts_ekf_arg(const bf_model* p, const GenModel& g) {
-  EkfModel<N, 1> e;
-  std::memset(&e, 0, sizeof(e));
-  e.dyn_id = p->dyn_id;
-  for (int i = 0; i < 8; ++i) e.dth[i] = g.dth[i];
-  if (p->dyn_id == DYN_LINEAR) for (int i = 0; i < N * N; ++i) e.A[i] = p->dyn_theta[i];
-  return e;
-}
-
-// return GO_(std::integral_constant<int, n>{}) for n = 1 ... 8
-#define BF_RTS_DIMS(N_, GO_)                                     \
-  switch (N_) {                                                  \
-    case 1: return GO_(std::integral_constant<int, 1>{});        \
-    case 2: return GO_(std::integral_constant<int, 2>{});        \
-    case 3: return GO_(std::integral_constant<int, 3>{});        \
-    case 4: return GO_(std::integral_constant<int, 4>{});        \
-    case 5: return GO_(std::integral_constant<int, 5>{});        \
-    case 6: return GO_(std::integral_constant<int, 6>{});        \
-    case 7: return GO_(std::integral_constant<int, 7>{});        \
-    default: return GO_(std::integral_constant<int, 8>{});       \
-  }
-#endif  // BF_JIT
 
 }  // namespace bf

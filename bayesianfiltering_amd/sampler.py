@@ -12,10 +12,9 @@ from typing import NamedTuple, Optional, Any
 import numpy as np
 
 from . import _lib
-from .inference import (_torch, _dev_f32, _host_f32, _alloc_stream, _stream_desc, _Model, _param_dims, kalman_filter,
-                        gaussian_sum_filter, unscented_gaussian_sum_filter)
-from .nonlinearities import DYN_LINEAR, DeviceFunction, require_device_function
-from .smoother import _LinearDynamics, _batched, _FILTER_KW, _ukf_params, _inputs_desc
+from ._backward import _front, _call, _wrapper_kw
+from .inference import (_torch, _dev_f32, _alloc_stream, _stream_desc, kalman_filter, gaussian_sum_filter,
+                        unscented_gaussian_sum_filter)
 
 
 class SamplerCarry(NamedTuple):
@@ -58,58 +57,25 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
     ``options``: e.g. ``{"ffbs_spl": 4}``, ``{"force_generic": 1}``.
     """
     torch = _torch()
-    f = params.dynamics_function
-    if not isinstance(f, DeviceFunction):  # a plain Python function is recorded at the model's dimensions, as the filters do
-        n0, dq0, _ = _param_dims(params)
-        f = require_device_function(f, "dynamics", "params.dynamics_function", n0, dq0)
-    f = require_device_function(f, "dynamics", "params.dynamics_function")
-    means, covs = posterior.means, posterior.covariances
-    if means is None or covs is None:
-        raise ValueError("the sampler needs the filtered means and covariances")
-    squeeze = means.dim() == 3
-    m_b, P_b = _batched(means, 1), _batched(covs, 2)
-    pm_b, pP_b = _batched(posterior.predicted_means, 1), _batched(posterior.predicted_covariances, 2)
-    if (pm_b is None) != (pP_b is None):
-        raise ValueError("predicted_means and predicted_covariances are given together or not at all")
-    B, K, T, n = (int(v) for v in m_b.shape)
     S = int(num_samples)
-    if K != 1:
-        raise ValueError(f"the sampler serves one component (Kalman / extended Kalman); the posterior has K = {K}")
-    if T == 0 or B == 0:
-        raise ValueError("empty posterior")
-    if S <= 0:
-        raise ValueError(f"num_samples must be positive; got {num_samples}")
-    if tuple(P_b.shape) != (B, 1, T, n, n):
-        raise ValueError(f"covariances have shape {tuple(covs.shape)}, expected {(B, 1, T, n, n)}")
-    if f.out_dim != n:
-        raise ValueError(f"the dynamics function has state dimension {f.out_dim}, the posterior {n}")
-    if (key is None) == (noise is None):
-        raise ValueError("exactly one of key and noise must be given")
-    if noise is not None:
-        if not isinstance(noise, torch.Tensor):
-            raise ValueError("noise must be a float32 device tensor")
-        want = (S, T, n) if squeeze else (B, S, T, n)
-        if tuple(noise.shape) != want:
-            raise ValueError(f"noise has shape {tuple(noise.shape)}, expected {want}")
-    up = _ukf_params(uparams, extended) if uparams is not None else None
-    use_ext = (f.fn_id != DYN_LINEAR) if extended is None else bool(extended)
-    if up is not None and pm_b is None:
-        raise ValueError("the unscented sampler needs the predicted means and covariances (filter with FULL5 fields)")
-    if use_ext and pm_b is None:
-        raise ValueError("the extended sampler needs the predicted means and covariances (filter with FULL5 fields)")
-    for t_ in (m_b, P_b, pm_b, pP_b, noise):
-        if t_ is not None and (t_.dtype != torch.float32 or not t_.is_cuda):
-            raise ValueError("posterior streams and noise must be float32 device tensors")
-    lib = _lib.require_gpu()
-    dev = m_b.device
+
+    def checks(B, T, n, squeeze):
+        if S <= 0:
+            raise ValueError(f"num_samples must be positive; got {num_samples}")
+        if (key is None) == (noise is None):
+            raise ValueError("exactly one of key and noise must be given")
+        if noise is not None:
+            if not isinstance(noise, torch.Tensor):
+                raise ValueError("noise must be a float32 device tensor")
+            want = (S, T, n) if squeeze else (B, S, T, n)
+            if tuple(noise.shape) != want:
+                raise ValueError(f"noise has shape {tuple(noise.shape)}, expected {want}")
+
+    bw = _front("sampler", params, posterior, extended, uparams, checks, (noise,), "posterior streams and noise")
+    B, T, n, squeeze, dev = bw.B, bw.T, bw.n, bw.squeeze, bw.dev
     want_dev = torch.device(device)
     if want_dev.type != dev.type or (want_dev.index is not None and want_dev.index != dev.index):
         raise ValueError(f"device={device!r}, but the posterior lives on {dev}: the sampler runs where its streams are")
-    cur = torch.cuda.current_stream(dev)
-
-    fd = _lib.bf_out_desc()
-    fd.means, fd.covs = _stream_desc(m_b, 1), _stream_desc(P_b, 2)
-    fd.pred_means, fd.pred_covs = _stream_desc(pm_b, 1), _stream_desc(pP_b, 2)
 
     keep = []
     if out is not None:
@@ -147,28 +113,8 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
         c_out = SamplerCarry(torch.empty((B, S, n), dtype=torch.float32, device=dev))
         cr.x_out = c_out.states.data_ptr()
 
-    stream = cur.cuda_stream
-    if up is not None:
-        mdl = _Model(params)
-        ud = _inputs_desc(inputs, B, T, dev, keep)
-        _lib.arm_call_options(lib, options)
-        _lib.check(lib.bf_uffbs_sample_f32(C.byref(mdl.c), C.byref(up), C.byref(ud), C.byref(fd), B, T, S, C.byref(cr),
-                                           C.byref(sd), C.c_void_p(stream)))
-    elif use_ext:
-        mdl = _Model(params)
-        ud = _inputs_desc(inputs, B, T, dev, keep)
-        _lib.arm_call_options(lib, options)
-        _lib.check(lib.bf_effbs_sample_f32(C.byref(mdl.c), C.byref(ud), C.byref(fd), B, T, S, C.byref(cr), C.byref(sd),
-                                           C.c_void_p(stream)))
-    else:
-        if getattr(f, "M", None) is None:
-            raise ValueError("params.dynamics_function must be linear_dynamics for the linear sampler")
-        mdl = _LinearDynamics(params, f)
-        _lib.arm_call_options(lib, options)
-        _lib.check(lib.bf_ffbs_sample_f32(C.byref(mdl.c), C.byref(fd), B, T, S, C.byref(cr), C.byref(sd),
-                                          C.c_void_p(stream)))
-    for t_ in keep:  # buffers made for this call stay allocated until the asynchronous launch has read them
-        t_.record_stream(cur)
+    _call("sampler", ("bf_ffbs_sample_f32", "bf_effbs_sample_f32", "bf_uffbs_sample_f32"), bw, params, inputs, options,
+          (S, C.byref(cr), C.byref(sd)), keep, torch.cuda.current_stream(dev))
 
     res = xs[0] if squeeze else xs
     return (res, c_out) if return_carry else res
@@ -178,21 +124,15 @@ def kalman_posterior_sample(params, emissions, num_samples, key, **kw):
     """``kalman_filter`` emitting the filtered fields only, then :func:`posterior_sample` on the recompute path.
     Keywords of :func:`kalman_filter` (``initial_means``, ``initial_covariances``, ``layout``, ``device``) go to the
     filter, the others to :func:`posterior_sample`."""
-    fkw = {k: kw[k] for k in _FILTER_KW if k in kw}
-    skw = {k: v for k, v in kw.items() if k not in ("initial_means", "initial_covariances")}
-    post = kalman_filter(params, emissions, fields=("means", "covariances"), **fkw)
-    return posterior_sample(params, post, num_samples, key=key, **skw)
+    fkw, skw = _wrapper_kw(params, kw, False)
+    return posterior_sample(params, kalman_filter(params, emissions, **fkw), num_samples, key=key, **skw)
 
 
 def extended_kalman_posterior_sample(params, emissions, num_samples, key, inputs=None, **kw):
     """The extended Kalman filter (``gaussian_sum_filter`` with one component, started from ``params.initial_mean``
     unless ``initial_means`` is given), then :func:`posterior_sample` through ``bf_effbs_sample_f32``."""
-    fkw = {k: kw[k] for k in _FILTER_KW if k in kw}
-    skw = {k: v for k, v in kw.items() if k not in ("initial_means", "initial_covariances")}
-    if "initial_means" not in fkw:
-        fkw["initial_means"] = _host_f32(params.initial_mean).reshape(1, -1)
-    post = gaussian_sum_filter(params, emissions, 1, inputs=inputs,
-                               fields=("means", "covariances", "predicted_means", "predicted_covariances"), **fkw)
+    fkw, skw = _wrapper_kw(params, kw, True)
+    post = gaussian_sum_filter(params, emissions, 1, inputs=inputs, **fkw)
     return posterior_sample(params, post, num_samples, key=key, inputs=inputs, extended=True, **skw)
 
 
@@ -200,10 +140,6 @@ def unscented_kalman_posterior_sample(params, uparams, emissions, num_samples, k
     """The unscented Kalman filter (``unscented_gaussian_sum_filter`` with one component, started from
     ``params.initial_mean`` unless ``initial_means`` is given), then :func:`posterior_sample` through
     ``bf_uffbs_sample_f32``."""
-    fkw = {k: kw[k] for k in _FILTER_KW if k in kw}
-    skw = {k: v for k, v in kw.items() if k not in ("initial_means", "initial_covariances")}
-    if "initial_means" not in fkw:
-        fkw["initial_means"] = _host_f32(params.initial_mean).reshape(1, -1)
-    post = unscented_gaussian_sum_filter(params, uparams, emissions, 1, inputs=inputs,
-                                         fields=("means", "covariances", "predicted_means", "predicted_covariances"), **fkw)
+    fkw, skw = _wrapper_kw(params, kw, True)
+    post = unscented_gaussian_sum_filter(params, uparams, emissions, 1, inputs=inputs, **fkw)
     return posterior_sample(params, post, num_samples, key=key, inputs=inputs, uparams=uparams, **skw)

@@ -16,8 +16,8 @@ tests/test_output_contract_gpu.py, whose guard-band builders (tests/test_stream_
     buffer through the carry reproduce the one-shot run bit for bit;
 (e) an ``out`` that is not float32, not on the device, or not exactly the shape the call returns is refused before any launch.
 
-Routes (the dispatch was read in csrc/rts_smoother.hip: launch_rts_linear / launch_rts_ext / launch_rts_n, csrc/ffbs_sampler.hip:
-launch_ffbs_linear / launch_ffbs_ext / launch_ffbs_n / launch_ffbs_generic, csrc/pf_sampler.hip: launch_pfs_n / launch_pfs_inst):
+Routes (the dispatch was read in csrc/backward_host.hpp: backward_dispatch, csrc/rts_smoother.hip: RtsProduct::regs / generic,
+csrc/ffbs_sampler.hip: FfbsProduct::regs / generic, csrc/pf_sampler.hip: launch_pfs_n / launch_pfs_inst):
   rts-staged      n <= 4, B >= 64, every stream in the contiguous reference layout with 16-byte aligned rows ->
                   rts_reg_kernel<N, RTS_STAGED> on the whole waves, <N, RTS_STRIDED> on the B % 64 tail.  ``rts_load_mode = 2``
                   forces it and is refused (-1) where it cannot serve, so a forced run that returns DID take it.

@@ -75,7 +75,7 @@ def test_data_paths_and_chunks_bit_for_bit():
     import torch
     import bayesianfiltering_amd as bfa
     # rows on 16 bytes: T n = 48, T n^2 = 144 and, for the T-1 cross-covariances of a call without a carry, (T-1) n^2 = 135 is
-    # not -- launch_rts_n's rule then takes the T-step pitch the allocation has (the view is a slice of a (B, 1, T, n, n) buffer)
+    # not -- rts_pick_path's rule then takes the T-step pitch the allocation has (the view is a slice of a (B, 1, T, n, n) buffer)
     B, T, s = 130, 16, 8
     c = sc.case("lorenz63", B, T)
     staged = bfa.rts_smoother(c.p, c.post, cross_covariances=True, options={"rts_load_mode": 2})
