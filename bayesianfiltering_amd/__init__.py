@@ -11,6 +11,10 @@ from .inference import (PosteriorGaussianSumFiltered, gaussian_sum_filter, unsce
                         bootstrap_particle_filter, ParticleCarry, resample_indices)
 from .smoother import (PosteriorGaussianSmoothed, SmootherCarry, rts_smoother, kalman_smoother,
                        extended_kalman_smoother, unscented_kalman_smoother)
+from .gaussian_sum_smoother import (PosteriorGaussianSumSmoothed, GaussianSumSmootherCarry, gaussian_sum_smoother,
+                                    extended_gaussian_sum_smoother, unscented_gaussian_sum_smoother)
+from .gaussian_sum_sampler import (GaussianSumSamplerCarry, gaussian_sum_posterior_sample,
+                                   extended_gaussian_sum_posterior_sample, unscented_gaussian_sum_posterior_sample)
 from .sampler import (SamplerCarry, posterior_sample, kalman_posterior_sample, extended_kalman_posterior_sample,
                       unscented_kalman_posterior_sample)
 from .particle_sampler import (ParticleSamplerCarry, particle_posterior_sample, bootstrap_particle_posterior_sample)
@@ -22,5 +26,8 @@ __all__ = ["ParamsNLSSM", "ParamsBPF", "NonlinearSSM", "GaussianComponent", "Gau
            "sample_initial_component_means", "bootstrap_particle_filter", "ParticleCarry", "resample_indices",
            "nonlinearities", "utils", "BayesFiltError",
            "PosteriorGaussianSmoothed", "SmootherCarry", "rts_smoother", "kalman_smoother", "extended_kalman_smoother", "unscented_kalman_smoother",
+           "PosteriorGaussianSumSmoothed", "GaussianSumSmootherCarry", "gaussian_sum_smoother", "extended_gaussian_sum_smoother",
+           "unscented_gaussian_sum_smoother", "GaussianSumSamplerCarry", "gaussian_sum_posterior_sample",
+           "extended_gaussian_sum_posterior_sample", "unscented_gaussian_sum_posterior_sample",
            "SamplerCarry", "posterior_sample", "kalman_posterior_sample", "extended_kalman_posterior_sample", "unscented_kalman_posterior_sample",
            "ParticleSamplerCarry", "particle_posterior_sample", "bootstrap_particle_posterior_sample"]

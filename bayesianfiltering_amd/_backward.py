@@ -61,9 +61,10 @@ def _inputs_desc(inputs, B, T, dev, keep):
 
 
 class _Backward(NamedTuple):
-    """What :func:`_front` hands a backward pass: the dynamics function, the batched streams (B, 1, T, ...), the sizes,
+    """What :func:`_front` hands a backward pass: the dynamics function, the batched streams (B, K, T, ...), the sizes,
     whether the caller's posterior was unbatched, the streams' device, their descriptor and the route (``up``: the
-    unscented route's bf_ukf_params or None; else ``use_ext``: extended or linear)."""
+    unscented route's bf_ukf_params or None; else ``use_ext``: extended or linear).  ``K`` is 1 except for the
+    Gaussian-sum passes (``_front(..., multi=True)``)."""
     f: Any
     lib: Any
     m_b: Any
@@ -76,13 +77,15 @@ class _Backward(NamedTuple):
     fd: Any
     up: Optional[Any]
     use_ext: bool
+    K: int = 1
 
 
-def _front(noun, params, posterior, extended, uparams, product_checks=None, also=(), what="posterior streams"):
+def _front(noun, params, posterior, extended, uparams, product_checks=None, also=(), what="posterior streams", multi=False):
     """The front half of a backward pass of ``noun`` ("smoother" / "sampler") up to the device: resolves the dynamics
     function, batches the posterior, checks it and chooses the route.  ``product_checks(B, T, n, squeeze)``: the product's
     own argument checks, made once the sizes are known and before the route is chosen; ``also``: further tensors that
-    must be float32 device tensors like the streams (``what`` names them all)."""
+    must be float32 device tensors like the streams (``what`` names them all).  ``multi``: the pass serves K >= 1
+    components (the Gaussian-sum smoother); every other pass refuses K > 1."""
     torch = _torch()
     f = params.dynamics_function
     if not isinstance(f, DeviceFunction):  # a plain Python function is recorded at the model's dimensions, as the filters do
@@ -98,12 +101,12 @@ def _front(noun, params, posterior, extended, uparams, product_checks=None, also
     if (pm_b is None) != (pP_b is None):
         raise ValueError("predicted_means and predicted_covariances are given together or not at all")
     B, K, T, n = (int(v) for v in m_b.shape)
-    if K != 1:
+    if K != 1 and not multi:
         raise ValueError(f"the {noun} serves one component (Kalman / extended Kalman); the posterior has K = {K}")
     if T == 0 or B == 0:
         raise ValueError("empty posterior")
-    if tuple(P_b.shape) != (B, 1, T, n, n):
-        raise ValueError(f"covariances have shape {tuple(covs.shape)}, expected {(B, 1, T, n, n)}")
+    if tuple(P_b.shape) != (B, K, T, n, n):
+        raise ValueError(f"covariances have shape {tuple(covs.shape)}, expected {(B, K, T, n, n)}")
     if f.out_dim != n:
         raise ValueError(f"the dynamics function has state dimension {f.out_dim}, the posterior {n}")
     if product_checks is not None:
@@ -121,7 +124,7 @@ def _front(noun, params, posterior, extended, uparams, product_checks=None, also
     fd = _lib.bf_out_desc()
     fd.means, fd.covs = _stream_desc(m_b, 1), _stream_desc(P_b, 2)
     fd.pred_means, fd.pred_covs = _stream_desc(pm_b, 1), _stream_desc(pP_b, 2)
-    return _Backward(f, lib, m_b, P_b, B, T, n, squeeze, m_b.device, fd, up, use_ext)
+    return _Backward(f, lib, m_b, P_b, B, T, n, squeeze, m_b.device, fd, up, use_ext, K)
 
 
 def _call(noun, names, bw, params, inputs, options, tail, keep, cur):

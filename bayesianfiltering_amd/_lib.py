@@ -50,6 +50,16 @@ class bf_smooth_carry(C.Structure):
     _fields_ = [("m_in", C.c_void_p), ("P_in", C.c_void_p), ("m_out", C.c_void_p), ("P_out", C.c_void_p)]
 
 
+class bf_gs_smooth_desc(C.Structure):
+    _fields_ = [("means", bf_stream), ("covs", bf_stream), ("cross_covs", bf_stream), ("coll_mean", bf_stream),
+                ("coll_cov", bf_stream), ("weights", C.c_void_p)]
+
+
+class bf_gs_sample_desc(C.Structure):
+    _fields_ = [("samples", bf_stream), ("noise", bf_cstream), ("keys", C.c_void_p), ("weights", C.c_void_p),
+                ("comp_noise", C.c_void_p), ("comp_keys", C.c_void_p), ("comp_in", C.c_void_p), ("comp_out", C.c_void_p)]
+
+
 class bf_sample_desc(C.Structure):
     _fields_ = [("samples", bf_stream), ("noise", bf_cstream), ("keys", C.c_void_p)]
 
@@ -158,6 +168,13 @@ SYMBOLS = {
     "bf_uks_smoother_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_ukf_params), C.POINTER(bf_cstream),
                                       C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.POINTER(bf_smooth_carry),
                                       C.POINTER(bf_smooth_desc), C.c_void_p]),
+    "bf_gs_abi_check": (C.c_int, [C.c_size_t, C.c_size_t]),
+    "bf_gs_smoother_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_ukf_params), C.POINTER(bf_cstream),
+                                     C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.c_int64, C.POINTER(bf_smooth_carry),
+                                     C.POINTER(bf_gs_smooth_desc), C.c_void_p]),
+    "bf_gs_sample_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_ukf_params), C.POINTER(bf_cstream),
+                                   C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(bf_sample_carry),
+                                   C.POINTER(bf_gs_sample_desc), C.c_void_p]),
     "bf_sampler_abi_check": (C.c_int, [C.c_size_t, C.c_size_t]),
     "bf_ffbs_sample_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.c_int32,
                                      C.POINTER(bf_sample_carry), C.POINTER(bf_sample_desc), C.c_void_p]),
@@ -202,6 +219,8 @@ def load():
                         C.sizeof(bf_bpf_out)) != BF_OK:
         raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
     if lib.bf_smoother_abi_check(C.sizeof(bf_smooth_desc), C.sizeof(bf_smooth_carry)) != BF_OK:
+        raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
+    if lib.bf_gs_abi_check(C.sizeof(bf_gs_smooth_desc), C.sizeof(bf_gs_sample_desc)) != BF_OK:
         raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())
     if lib.bf_sampler_abi_check(C.sizeof(bf_sample_desc), C.sizeof(bf_sample_carry)) != BF_OK:
         raise ImportError("ABI mismatch between _lib.py and the built library: " + lib.bf_last_error().decode())

@@ -161,8 +161,8 @@ int rts_gen_upload(RtsGen& c, GenModel& gg, const std::vector<float>& blk, hipSt
 }
 
 int backward_launch_user_generic(const bf_model* p, int jit_kind, const char* noun, void* c, void* views, long long B, long long T,
-                                 size_t lds, hipStream_t stream) {
-  if (B > 0x7fffffffLL) return set_error(BF_EINVAL, "%s: B too large for the run-time-dimension kernel", noun);
+                                 size_t lds, hipStream_t stream, int K, void* last) {
+  if (B * (K > 0 ? K : 1) > 0x7fffffffLL) return set_error(BF_EINVAL, "%s: B too large for the run-time-dimension kernel", noun);
   // the kernels' constants of the source route: q0 | theta on the device, g.q0 / g.dyn_theta pointing into it
   GenModel g;
   std::memset(&g, 0, sizeof(g));
@@ -178,8 +178,8 @@ int backward_launch_user_generic(const bf_model* p, int jit_kind, const char* no
   g.dyn_theta = g.q0 + p->dq;
   hipFunction_t fn = nullptr;
   if ((rc = user_kernel(p->user, jit_kind, 0, 0, JIT_SPEC_USER, &fn)) != BF_OK) return rc;
-  void* args[] = {c, &g, views, &T};
-  return launch_user_kernel(p->user, 64, (unsigned)B, lds, stream, args, fn);
+  void* args[] = {c, &g, views, &T, last ? last : &K};  // (the fifth: read by the Gaussian-sum kernels only, whose signatures end with it)
+  return launch_user_kernel(p->user, 64, (unsigned)(B * (K > 0 ? K : 1)), lds, stream, args, fn);
 }
 
 }  // namespace bf

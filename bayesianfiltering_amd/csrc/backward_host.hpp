@@ -86,9 +86,16 @@ int rts_user_fill(const bf_model* p, RtsUserHost& h);
 int rts_gen_upload(RtsGen& c, GenModel& g, const std::vector<float>& blk, hipStream_t stream);
 // The source route's run-time-dimension launch once the product has planned its LDS: the B range check (`noun`: "smoother" /
 // "sampler"), q0 | theta uploaded behind a GenModel, the handle's kernel of `jit_kind`, one workgroup per trajectory.
-// `c` and `views` are the product's first and third kernel arguments.
+// `c` and `views` are the product's first and third kernel arguments.  K > 0 (the Gaussian-sum kinds): one workgroup per chain,
+// B K in all, and K -- or `last`, when given -- as the kernel's last argument.
 int backward_launch_user_generic(const bf_model* p, int jit_kind, const char* noun, void* c, void* views, long long B, long long T,
-                                 size_t lds, hipStream_t stream);
+                                 size_t lds, hipStream_t stream, int K = 0, void* last = nullptr);
+// the smoother of one-component streams on the route `r` (rts_smoother.hip): the register kernels with their data path, or the
+// run-time-dimension kernel.  The Gaussian-sum smoother calls it with B K trajectories where the layout flattens.
+int rts_run(const BackwardRoute& r, const RtsViews& v, long long B, long long T, void* stream);
+Option& rts_load_mode_option();  // rts_smoother.hip
+int launch_collapse(const bf_stream* w, const bf_stream* m, const bf_stream* P, long long B, long long T, int K, int n,
+                    float* mean_out, float* cov_out, hipStream_t stream);  // collapse.hip
 
 template <int N>
 inline RtsLin<N> rts_lin_arg(const BackwardRoute& r) {

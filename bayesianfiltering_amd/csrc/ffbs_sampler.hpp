@@ -21,6 +21,14 @@
 // (s, t, i) = bits_to_normal(threefry_bits(k0, k1, (s T + t) n + i, S T n)) (bf_rng.hpp): jax.random.normal(keys[b],
 // (S, T, n)), the values bf_random_normal_f32(keys[b], S T n) writes on the host.
 //
+// Gaussian-sum sampler (bf_gs_sample_f32; K >= 1 components; the mixture over the initial component's index of
+// rts_smoother.hpp).  Per sample (b, s) a component z: c_j = the inclusive cumulative sum of w[b][0..j] in index order by
+// sequential fp32 adds; z = the smallest j with c_j > v c_{K-1}, clamped to K-1, v = comp_noise[b][s] in [0, 1) -- or
+// bf_random_uniform_f32(comp_keys[b], S)[s]; c_{K-1} not finite or not > 0: the draw is invalid, z = -1, and that sample is NaN at
+// every step and in the carry, other samples untouched.  comp_in[B][S] replaces the draw, comp_out[B][S] returns it.  Sample s is
+// then the recursion above on chain (b, z) -- streams at b sB + z sK, inputs and keys at b -- with noise row (b, s): its bits do
+// not depend on S, on the other samples' components or on the launch shape.  Noise: a stream, or keys[b] exactly as above.
+//
 // Register kernel (this file, n <= 8): a lane is one (trajectory, block of SPL samples); adjacent lanes are adjacent sample
 // blocks of one trajectory, so the stream loads of a wave are same-address broadcasts and nothing crosses lanes.  Every
 // lane repeats the factorization its trajectory shares (ALU time, no HBM traffic) and then serves its SPL samples from it.
@@ -108,16 +116,64 @@ __device__ __forceinline__ void ffbs_factor(float* X, const float* P, const floa
   psdchol<N>(Ls, d);
 }
 
+// ---- Gaussian-sum sampler: the component of a sample (the contract in include/bayesfilt.h, bf_gs_sample_f32) ---------------
+// c_j = the inclusive cumulative sum of w[b][0..j] by sequential fp32 adds; z = the smallest j with c_j > v c_{K-1}, clamped
+// to K-1; -1 (an invalid draw) when c_{K-1} is not finite or not positive.  v = comp_noise[b][s], or
+// bits_to_unit(threefry_bits(comp_keys[b], s, S)): bf_random_uniform_f32(comp_keys[b], S).  z_in replaces the draw (values
+// outside [0, K) count as invalid); z_out receives it.
+struct GsDraw {
+  const float* w;         // [B][K]
+  const float* v;         // [B][S] or NULL
+  const uint32_t* vkeys;  // [B][2], read when v == NULL
+  const int* z_in;        // [B][S] or NULL
+  int* z_out;             // [B][S] or NULL
+  int K;
+};
+__device__ __forceinline__ int gs_draw_component(const GsDraw& d, long long b, int s, int S) {
+#pragma clang fp contract(off)
+  const int K = d.K;
+  if (d.z_in) {
+    const int z = d.z_in[b * S + s];
+    return (z >= 0 && z < K) ? z : -1;
+  }
+  const float* w = d.w + b * K;
+  float tot = w[0];
+  for (int j = 1; j < K; ++j) tot = tot + w[j];
+  if (!(tot > 0.f) || !(tot <= 3.4028234663852886e38f)) return -1;
+  const float v = d.v ? d.v[b * S + s] : bits_to_unit(threefry_bits(d.vkeys[2 * b], d.vkeys[2 * b + 1], (uint32_t)s, (uint32_t)S));
+  const float thr = v * tot;
+  float c = w[0];
+  int j = 0;
+  while (!(c > thr) && j < K - 1) {
+    ++j;
+    c = c + w[j];
+  }
+  return j;
+}
+
 // (a device function, as rts_reg_body: shared by the ahead-of-time instances and the entry points compiled at run time)
-template <int N, int SPL, int KIND, class Arg>
+// GS (the Gaussian-sum sampler, SPL = 1): a lane is one (trajectory, sample); its component z only changes which chain's
+// streams the lane reads (b sB + z sK); an invalid draw writes NaN at every step and into the carry.
+template <int N, int SPL, int KIND, class Arg, bool GS = false>
 __device__ __forceinline__ void ffbs_reg_body(const Arg& c, const float* __restrict__ gqg_t, const FfbsViews& v, long long B,
-                                              long long T, int S) {
+                                              long long T, int S, const GsDraw* gd = nullptr) {
   constexpr int NN = N * N;
   const int NB = (S + SPL - 1) / SPL;  // sample blocks (lanes) per trajectory
   const long long g = (long long)blockIdx.x * 64 + threadIdx.x;
   const long long b = g / NB;
   if (b >= B) return;  // no cross-lane work
   const int s0 = (int)(g - b * NB) * SPL;
+  int zk = 0;
+  if constexpr (GS) {
+    zk = gs_draw_component(*gd, b, s0, S);
+    if (gd->z_out) gd->z_out[b * S + s0] = zk;
+    if (zk < 0) {
+      const float nan = __builtin_nanf("");
+      for (long long t = 0; t < T; ++t) BF_UNROLL for (int i = 0; i < N; ++i) v.x.p[b * v.x.sB + s0 * v.x.sK + t * v.x.sT + i * v.x.sE] = nan;
+      if (v.x_out) BF_UNROLL for (int i = 0; i < N; ++i) v.x_out[(b * S + s0) * N + i] = nan;
+      return;
+    }
+  }
   const bool keyed = v.xi.p == nullptr;
   uint32_t k0 = 0, k1 = 0;
   if (keyed) {
@@ -125,7 +181,10 @@ __device__ __forceinline__ void ffbs_reg_body(const Arg& c, const float* __restr
     k1 = v.keys[2 * b + 1];
   }
   const uint32_t count = (uint32_t)S * (uint32_t)T * (uint32_t)N;
-  auto ld = [&](const SView& s, long long t, int e) { return s.p[b * s.sB + t * s.sT + e * s.sE]; };
+  auto ld = [&](const SView& s, long long t, int e) {
+    if constexpr (GS) return s.p[b * s.sB + zk * s.sK + t * s.sT + e * s.sE];
+    else return s.p[b * s.sB + t * s.sT + e * s.sE];
+  };
   auto noise = [&](int s, long long t, float* z) __attribute__((always_inline)) {
     if (keyed) {
       const uint32_t base = ((uint32_t)s * (uint32_t)T + (uint32_t)t) * (uint32_t)N;
@@ -197,6 +256,11 @@ template <int N, int SPL, int KIND, class Arg>
 __global__ void __launch_bounds__(64) ffbs_reg_kernel(Arg c, const float* __restrict__ gqg_t, FfbsViews v, long long B,
                                                       long long T, int S) {
   ffbs_reg_body<N, SPL, KIND, Arg>(c, gqg_t, v, B, T, S);
+}
+
+template <int N, int KIND, class Arg>
+__global__ void __launch_bounds__(64) ffbs_gs_reg_kernel(Arg c, FfbsViews v, GsDraw gd, long long B, long long T, int S) {
+  ffbs_reg_body<N, 1, KIND, Arg, true>(c, nullptr, v, B, T, S, &gd);
 }
 
 }  // namespace bf

@@ -162,6 +162,10 @@ const char* jit_entry_name(int kind, int variant) {
     case JIT_FFBS_GENERIC: return "bf_user_ffbs_generic";
     case JIT_RTS_REGS: return variant == 2 ? "bf_user_rts_staged" : "bf_user_rts_strided";   // RTS_STAGED / RTS_STRIDED
     case JIT_FFBS_REGS: return variant == 1 ? "bf_user_ffbs_spl1" : variant == 2 ? "bf_user_ffbs_spl2" : variant == 4 ? "bf_user_ffbs_spl4" : "bf_user_ffbs_spl8";
+    case JIT_GS_RTS_GENERIC: return "bf_user_gs_rts_generic";
+    case JIT_GS_FFBS_GENERIC: return "bf_user_gs_ffbs_generic";
+    case JIT_GS_FFBS_REGS: return "bf_user_gs_ffbs";
+    case JIT_GS_RTS_REGS: return variant == 1 ? "bf_user_gs_rts_comp" : variant == 2 ? "bf_user_gs_rts_coll" : "bf_user_gs_rts_both";   // GS_COMP / GS_COLL / both
     case JIT_BPF: return "bf_user_bpf";
     case JIT_UGSF: return "bf_user_ugsf";
     case JIT_AGSF_UKF: case JIT_AGSF_EKF: return "bf_user_agsf";
@@ -176,7 +180,7 @@ const char* jit_entry_name(int kind, int variant) {
 std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int spec_id) {
   if (kind == JIT_GSF_GENERIC) return generic_scan_source(um, 0);
   if (kind == JIT_UGSF_GENERIC) return generic_scan_source(um, 64 * nw);   // nw = 1: one wave per trajectory, 4: four
-  if (kind == JIT_RTS_GENERIC || kind == JIT_FFBS_GENERIC) {
+  if (kind == JIT_RTS_GENERIC || kind == JIT_FFBS_GENERIC || kind == JIT_GS_RTS_GENERIC || kind == JIT_GS_FFBS_GENERIC) {
     // The run-time-dimension kernels of the smoother / the posterior sampler around the caller's dynamics: libm's float functions
     // under the dual numbers, as in JIT_GSF_GENERIC, whose streams they read; the kernel bodies are rts_generic.hpp's, with every
     // header they include in front (BF_JIT_FULL_HEADERS: generic_device.hpp then brings no helpers of its own).
@@ -197,7 +201,13 @@ std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int s
     s += kGenericDeviceSource;
     s += kUgsfGenericSource;
     s += kRtsGenericSource;
-    if (kind == JIT_RTS_GENERIC)
+    if (kind == JIT_GS_FFBS_GENERIC)
+      s += "extern \"C\" __global__ void __launch_bounds__(64) bf_user_gs_ffbs_generic(bf::FfbsGen c, bf::GenModel g, bf::FfbsViews v, long long T, bf::GsDraw gd) {\n"
+           "  bf::ffbs_generic_body<false, true, true>(c, g, v, T, &gd);\n}\n";
+    else if (kind == JIT_GS_RTS_GENERIC)
+      s += "extern \"C\" __global__ void __launch_bounds__(64) bf_user_gs_rts_generic(bf::RtsGen c, bf::GenModel g, bf::RtsViews v, long long T, int K) {\n"
+           "  bf::rts_generic_body<false, true, true>(c, g, v, T, K);\n}\n";
+    else if (kind == JIT_RTS_GENERIC)
       s += "extern \"C\" __global__ void __launch_bounds__(64) bf_user_rts_generic(bf::RtsGen c, bf::GenModel g, bf::RtsViews v, long long T) {\n"
            "  bf::rts_generic_body<false, true>(c, g, v, T);\n}\n";
     else
@@ -205,7 +215,7 @@ std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int s
            "  bf::ffbs_generic_body<false, true>(c, g, v, T);\n}\n";
     return s;
   }
-  if (kind == JIT_RTS_REGS || kind == JIT_FFBS_REGS) {
+  if (kind == JIT_RTS_REGS || kind == JIT_FFBS_REGS || kind == JIT_GS_RTS_REGS || kind == JIT_GS_FFBS_REGS) {
     // The register kernels of the smoother / the posterior sampler around the caller's dynamics (RTS_EXT_USER), assembled as
     // JIT_GSF_REGS is: the caller's function sees the float functions of the register filter that produced the streams.  The
     // emission is not read by a backward pass and is left out.  One module holds every data path / samples-per-lane count.
@@ -221,6 +231,13 @@ std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int s
     s += kSamplingSourceB;
     s += kUgsfSource;
     s += kRtsSource;
+    if (kind == JIT_GS_RTS_REGS) {  // the Gaussian-sum smoother: one entry point per output set
+      for (int out : {1, 2, 3})
+        s += std::string("extern \"C\" __global__ void __launch_bounds__(64) ") + jit_entry_name(kind, out) +
+             "(bf::RtsUser<BF_DQ> c, bf::RtsGsViews gv, long long B, long long T) {\n  bf::rts_gs_reg_body<BF_N, bf::RTS_EXT_USER, " +
+             std::to_string(out) + ">(c, gv, B, T);\n}\n";
+      return s;
+    }
     if (kind == JIT_RTS_REGS) {
       for (int mode : {0, 2})
         s += std::string("extern \"C\" __global__ void __launch_bounds__(64) ") + jit_entry_name(kind, mode) +
@@ -229,6 +246,11 @@ std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int s
       return s;
     }
     s += kFfbsSource;
+    if (kind == JIT_GS_FFBS_REGS) {  // the Gaussian-sum sampler: one lane per (trajectory, sample)
+      s += "extern \"C\" __global__ void __launch_bounds__(64) bf_user_gs_ffbs(bf::RtsUser<BF_DQ> c, bf::FfbsViews v, bf::GsDraw gd, long long B, long long T, int S) {\n"
+           "  bf::ffbs_reg_body<BF_N, 1, bf::RTS_EXT_USER, bf::RtsUser<BF_DQ>, true>(c, nullptr, v, B, T, S, &gd);\n}\n";
+      return s;
+    }
     for (int spl : {1, 2, 4, 8})
       s += std::string("extern \"C\" __global__ void __launch_bounds__(64) ") + jit_entry_name(kind, spl) +
            "(bf::RtsUser<BF_DQ> c, bf::FfbsViews v, long long B, long long T, int S) {\n  bf::ffbs_reg_body<BF_N, " + std::to_string(spl) +

@@ -244,11 +244,18 @@ __device__ __forceinline__ void rts_gen_solve_upper(int n, const float* W, float
   }
 }
 
-// The smoother's run-time-dimension kernel (rts_smoother.hip states its LDS carve-up): one 64-lane workgroup per trajectory
-template <bool UNSC, bool USER>
-__device__ __forceinline__ void rts_generic_body(const RtsGen& c, const GenModel& g, const RtsViews& v, long long T) {
+// The smoother's run-time-dimension kernel (rts_smoother.hip states its LDS carve-up): one 64-lane workgroup per trajectory.
+// GS (the Gaussian-sum smoother): one workgroup per chain ch = b K + k, streams at b sB + k sK, inputs at b, carries at ch.
+template <bool UNSC, bool USER, bool GS = false>
+__device__ __forceinline__ void rts_generic_body(const RtsGen& c, const GenModel& g, const RtsViews& v, long long T, int K = 1) {
   const int tid = threadIdx.x;
-  const long long b = blockIdx.x;
+  const long long ch = blockIdx.x;
+  long long b = ch;
+  int kc = 0;
+  if constexpr (GS) {
+    b = ch / K;
+    kc = (int)(ch - b * K);
+  }
   const int n = c.n, ld = rts_gen_ld(n), nn = n * n;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* P = lds;
@@ -262,12 +269,15 @@ __device__ __forceinline__ void rts_generic_body(const RtsGen& c, const GenModel
   float* tv = mp + n;
   const RtsUnscLds ul = rts_unsc_carve(tv + n, tv + n + n * ld, tv + n + 2 * n * ld, n);  // carved for RTS_UNSC only
   const bool want_c = v.Cs.p != nullptr;
-  auto at = [&](const SView& s, long long t, int e) { return b * s.sB + t * s.sT + e * s.sE; };
+  auto at = [&](const SView& s, long long t, int e) {
+    if constexpr (GS) return b * s.sB + kc * s.sK + t * s.sT + e * s.sE;
+    else return b * s.sB + t * s.sT + e * s.sE;
+  };
 
   long long t = T - 1;
   if (v.m_in) {
-    for (int e = tid; e < n; e += 64) ms[e] = v.m_in[b * n + e];
-    for (int e = tid; e < nn; e += 64) Ps[(e / n) * ld + e % n] = v.P_in[b * nn + e];
+    for (int e = tid; e < n; e += 64) ms[e] = v.m_in[ch * n + e];
+    for (int e = tid; e < nn; e += 64) Ps[(e / n) * ld + e % n] = v.P_in[ch * nn + e];
   } else {
     for (int e = tid; e < n; e += 64) { const float x = v.m.p[at(v.m, t, e)]; ms[e] = x; v.ms.p[at(v.ms, t, e)] = x; }
     for (int e = tid; e < nn; e += 64) { const float x = v.P.p[at(v.P, t, e)]; Ps[(e / n) * ld + e % n] = x; v.Ps.p[at(v.Ps, t, e)] = x; }
@@ -329,17 +339,26 @@ __device__ __forceinline__ void rts_generic_body(const RtsGen& c, const GenModel
     for (int e = tid; e < nn; e += 64) v.Ps.p[at(v.Ps, t, e)] = Ps[(e / n) * ld + e % n];
     wave_lds_sync();
   }
-  if (v.m_out) for (int e = tid; e < n; e += 64) v.m_out[b * n + e] = ms[e];
-  if (v.P_out) for (int e = tid; e < nn; e += 64) v.P_out[b * nn + e] = Ps[(e / n) * ld + e % n];
+  if (v.m_out) for (int e = tid; e < n; e += 64) v.m_out[ch * n + e] = ms[e];
+  if (v.P_out) for (int e = tid; e < nn; e += 64) v.P_out[ch * nn + e] = Ps[(e / n) * ld + e % n];
 }
 
 
-// The sampler's run-time-dimension kernel (ffbs_sampler.hip states its LDS carve-up): one 64-lane workgroup per trajectory
-template <bool UNSC, bool USER>
-__device__ __forceinline__ void ffbs_generic_body(const FfbsGen& fc, const GenModel& g, const FfbsViews& v, long long T) {
+// The sampler's run-time-dimension kernel (ffbs_sampler.hip states its LDS carve-up): one 64-lane workgroup per trajectory.
+// GS (the Gaussian-sum sampler): one workgroup per (trajectory, component) that serves the samples whose component is its
+// own -- their indices, in order, in `sel` behind the sample buffers -- and exits at once when there is none; the workgroup
+// of component 0 also writes the drawn components and the NaN of the invalid draws.
+template <bool UNSC, bool USER, bool GS = false>
+__device__ __forceinline__ void ffbs_generic_body(const FfbsGen& fc, const GenModel& g, const FfbsViews& v, long long T,
+                                                  const GsDraw* gd = nullptr) {
   const RtsGen& c = fc.r;
   const int tid = threadIdx.x;
-  const long long b = blockIdx.x;
+  long long b = blockIdx.x;
+  int kc = 0;
+  if constexpr (GS) {
+    b = blockIdx.x / gd->K;
+    kc = (int)(blockIdx.x - b * gd->K);
+  }
   const int n = c.n, ld = rts_gen_ld(n), nn = n * n, S = fc.S, SB = fc.SB;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* P = lds;
@@ -354,7 +373,30 @@ __device__ __forceinline__ void ffbs_generic_body(const FfbsGen& fc, const GenMo
   float* xs = tv + n + (UNSC ? n * ld + rts_unsc_vec_floats(n) : 0);  // x_{t+1} of the block, then x_{t+1} - m-
   float* xi = xs + SB * n;   // the block's noise
   float* xo = xi + SB * n;   // x_t of the block
-  const bool one_block = SB >= S;
+  int NS = S;   // samples this workgroup serves
+  int* sel = reinterpret_cast<int*>(xo + SB * n);
+  if constexpr (GS) {
+    int cnt = 0;
+    for (int s0 = 0; s0 < S; s0 += 64) {  // uniform trip count: every lane reaches the ballot
+      const int s = s0 + tid;
+      const int z = s < S ? gs_draw_component(*gd, b, s, S) : -2;
+      if (kc == 0 && s < S) {
+        if (gd->z_out) gd->z_out[b * S + s] = z;
+        if (z < 0) {
+          const float nan = __builtin_nanf("");
+          for (long long t = 0; t < T; ++t) for (int i = 0; i < n; ++i) v.x.p[b * v.x.sB + s * v.x.sK + t * v.x.sT + i * v.x.sE] = nan;
+          if (v.x_out) for (int i = 0; i < n; ++i) v.x_out[((long long)b * S + s) * n + i] = nan;
+        }
+      }
+      const unsigned long long mask = __ballot(z == kc);
+      if (z == kc) sel[cnt + __popcll(mask & ((1ull << tid) - 1ull))] = s;
+      cnt += __popcll(mask);
+    }
+    NS = cnt;
+    if (NS == 0) return;  // uniform
+    wave_lds_sync();
+  }
+  const bool one_block = SB >= NS;
   const bool keyed = v.xi.p == nullptr;
   uint32_t k0 = 0, k1 = 0;
   if (keyed) {
@@ -362,15 +404,22 @@ __device__ __forceinline__ void ffbs_generic_body(const FfbsGen& fc, const GenMo
     k1 = v.keys[2 * b + 1];
   }
   const uint32_t count = (uint32_t)S * (uint32_t)T * (uint32_t)n;
-  auto at = [&](const SView& s, long long t, int e) { return b * s.sB + t * s.sT + e * s.sE; };
+  auto at = [&](const SView& s, long long t, int e) {
+    if constexpr (GS) return b * s.sB + kc * s.sK + t * s.sT + e * s.sE;
+    else return b * s.sB + t * s.sT + e * s.sE;
+  };
+  auto smp_of = [&](int j) {
+    if constexpr (GS) return sel[j];
+    else return j;
+  };
   auto xat = [&](const SView& s, int smp, long long t, int e) { return b * s.sB + smp * s.sK + t * s.sT + e * s.sE; };
 
   // the samples of step t in blocks: first = the chunk's last step without a carry (x = m + Sg xi)
   auto samples = [&](long long t, bool first) {
-    for (int sb0 = 0; sb0 < S; sb0 += SB) {
-      const int ne = ((S - sb0) < SB ? (S - sb0) : SB) * n;
+    for (int sb0 = 0; sb0 < NS; sb0 += SB) {
+      const int ne = ((NS - sb0) < SB ? (NS - sb0) : SB) * n;
       for (int e = tid; e < ne; e += 64) {
-        const int sl = e / n, i = e - sl * n, smp = sb0 + sl;
+        const int sl = e / n, i = e - sl * n, smp = smp_of(sb0 + sl);
         xi[e] = keyed ? bits_to_normal(threefry_bits(k0, k1, ((uint32_t)smp * (uint32_t)T + (uint32_t)t) * (uint32_t)n + i, count))
                       : v.xi.p[xat(v.xi, smp, t, i)];
         if (!first) {
@@ -397,8 +446,14 @@ __device__ __forceinline__ void ffbs_generic_body(const FfbsGen& fc, const GenMo
         }
         const float xv = m[i] + s;
         xo[e] = xv;
-        v.x.p[xat(v.x, sb0 + sl, t, i)] = xv;
-        if (t == 0 && v.x_out) v.x_out[((long long)b * S + sb0 + sl) * n + i] = xv;
+        if constexpr (GS) {
+          const int smp = sel[sb0 + sl];
+          v.x.p[xat(v.x, smp, t, i)] = xv;
+          if (t == 0 && v.x_out) v.x_out[((long long)b * S + smp) * n + i] = xv;
+        } else {
+          v.x.p[xat(v.x, sb0 + sl, t, i)] = xv;
+          if (t == 0 && v.x_out) v.x_out[((long long)b * S + sb0 + sl) * n + i] = xv;
+        }
       }
       wave_lds_sync();
       if (one_block) {

@@ -218,7 +218,7 @@ static int rts_views(const bf_out_desc* f, const bf_smooth_carry* carry, const b
   return BF_OK;
 }
 
-static int rts_run(const BackwardRoute& r, const RtsViews& v, long long B, long long T, void* stream) {
+int rts_run(const BackwardRoute& r, const RtsViews& v, long long B, long long T, void* stream) {
   const hipStream_t s = static_cast<hipStream_t>(stream);
   return backward_dispatch(r, force_generic_option().load() != 0, RtsProduct{v, B, T, g_rts_load_mode.load(), s}, s);
 }

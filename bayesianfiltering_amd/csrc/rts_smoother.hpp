@@ -24,6 +24,19 @@
 // difference of images 2 c |R_t| apart: its fp32 relative error is about 2^-24 |f(m_t)| / (c |P_t|^1/2), the cancellation
 // the filter's own moment sums have; alpha << 1 makes it large (1e-4 ... 2e-4 against float64 at alpha = 1e-3).
 //
+// Gaussian-sum smoother (bf_gs_smoother_f32; K >= 1 components).  In bf_gsf_ekf_f32 and bf_ugsf_ukf_f32 the components never
+// interact: each is an extended (unscented) Kalman chain started from its own initial mean, coupled only through the weight
+// recursion w_{t,k} ~ w_{t-1,k} p(y_t | y_{<t}, k).  The model is a mixture over the index k of the initial component,
+//   p(x_{0:T-1} | y_{0:T-1}) = sum_k w_{T-1,k} p(x_{0:T-1} | y_{0:T-1}, k),
+// so the smoothed weights are the filter's weights at the LAST step of the whole series (constant in t, given as weights[B][K] so
+// that backward chunks share them) and smoothed component k is the recursion above (extended from the registry or from source,
+// or unscented) on chain (b, k): streams at b sB + k sK, inputs u at b, the carry bf_smooth_carry contiguous [B][K][n] /
+// [B][K][n][n] at b K + k.  Optional collapsed streams, the moment match of utils.collapse with time-constant weights:
+//   mu_t = sum_k w_k m^s_{k,t},   Sigma_t = sum_k w_k (P^s_{k,t} + (m^s_{k,t} - mu_t)(m^s_{k,t} - mu_t)^T),
+// the sum over k an adjacent-pair tree over the power of two >= K whose order depends on K alone (never on B or on where a
+// trajectory sits in a wave); NaN weights or a NaN chain give NaN collapsed values for that trajectory only.  The kernels are at
+// the end of this file (rts_gs_reg_body) and in rts_generic.hpp (rts_generic_body<.., GS>); the host side is gs_smoother.hip.
+//
 // Register kernel (this file, n <= 8): one lane per trajectory, 64-thread workgroups.  The carry (m^s, P^s) and the
 // step's P, P-, X, Cholesky factor live in VGPRs; every loop has compile-time bounds.  Two data paths, same arithmetic
 // (so the same bits):
@@ -428,6 +441,131 @@ template <int N, int MODE, int KIND, class Arg>
 __global__ void __launch_bounds__(64) rts_reg_kernel(Arg c, const float* __restrict__ gqg_t, RtsViews v, long long B,
                                                      long long T) {
   rts_reg_body<N, MODE, KIND, Arg>(c, gqg_t, v, B, T);
+}
+
+// ---- Gaussian-sum smoother: K chains per trajectory (the contract at the top of this file) -------------------------------
+// Chain (b, k) reads and writes the streams at b sB + k sK, the inputs at b and the carries at b K + k; its arithmetic is
+// rts_linearize / rts_step, the one-component kernel's, so its streams carry the same bits.
+enum { GS_COMP = 1, GS_COLL = 2 };  // what a launch writes: the per-component streams, the collapsed moments, or both
+
+struct RtsGsViews {
+  RtsViews v;       // sK honoured; m_in / P_in / m_out / P_out contiguous [B][K][n] / [B][K][n][n]
+  SView cm, cP;     // collapsed mean / covariance, element (b, t, e) at p[b sB + t sT + e sE]; p may be NULL
+  const float* w;   // [B][K], read when a collapsed output is written
+  int K;
+  int KP;           // GS_COLL: lanes per trajectory, the power of two >= K (<= 64); the lanes k >= K idle with weight 0
+  int b_inner;      // components only: adjacent lanes are adjacent trajectories (sB < sK), else adjacent components
+};
+
+// sum over the KP adjacent lanes of a trajectory as an adjacent-pair tree (lane ^ 1, ^ 2, ...): a + b is commutative, so
+// every lane of the group holds the same bits, and the order depends on KP alone
+__device__ __forceinline__ float gs_tree_sum(float x, int KP) {
+  for (int off = 1; off < KP; off <<= 1) x += __shfl_xor(x, off, 64);
+  return x;
+}
+
+// Register kernel, strided data path.  OUT == GS_COMP: one lane per chain, densely packed (a single trajectory with many
+// components fills its waves).  OUT & GS_COLL: a trajectory's chains sit in KP adjacent lanes; after every step the n + n^2
+// weighted moments are summed across them and the lane of component 0 stores mu_t, Sigma_t.  Without GS_COMP the
+// per-component stores are not compiled in.
+template <int N, int KIND, int OUT, class Arg>
+__device__ __forceinline__ void rts_gs_reg_body(const Arg& c, const RtsGsViews& gv, long long B, long long T) {
+  constexpr int NN = N * N;
+  constexpr bool COMP = (OUT & GS_COMP) != 0, COLL = (OUT & GS_COLL) != 0;
+  const RtsViews& v = gv.v;
+  const int lane = threadIdx.x;
+  const int K = gv.K;
+  long long b;
+  int k;
+  bool act = true;
+  if constexpr (COLL) {
+    const int KP = gv.KP;
+    b = (long long)blockIdx.x * (64 / KP) + lane / KP;
+    k = lane & (KP - 1);
+    act = b < B && k < K;  // idle lanes stay for the cross-lane sums
+  } else {
+    const long long g = (long long)blockIdx.x * 64 + lane;
+    if (g >= B * K) return;  // no cross-lane work on this path
+    if (gv.b_inner) { k = (int)(g / B); b = g - (long long)k * B; }
+    else { b = g / K; k = (int)(g - b * K); }
+  }
+  const long long ch = b * K + k;
+  const bool want_c = COMP && v.Cs.p != nullptr;
+  const bool carry_in = v.m_in != nullptr;
+  float ms[N], Ps[NN];
+  float w = 0.f;
+  if constexpr (COLL) {
+    BF_UNROLL for (int i = 0; i < N; ++i) ms[i] = 0.f;
+    BF_UNROLL for (int i = 0; i < NN; ++i) Ps[i] = 0.f;
+    if (act) w = gv.w[ch];
+  }
+  auto ld = [&](const SView& s, long long t, int e) { return s.p[b * s.sB + k * s.sK + t * s.sT + e * s.sE]; };
+  auto st = [&](const SView& s, long long t, int e, float x) { s.p[b * s.sB + k * s.sK + t * s.sT + e * s.sE] = x; };
+  // mu_t = sum_k w_k m^s_k, Sigma_t = sum_k w_k (P^s_k + (m^s_k - mu_t)(m^s_k - mu_t)^T); every lane of the wave takes part
+  auto collapse = [&](long long t) __attribute__((always_inline)) {
+    const int KP = gv.KP;
+    const bool lead = act && k == 0;
+    float d[N];
+    BF_UNROLL for (int i = 0; i < N; ++i) {
+      const float mu = gs_tree_sum(act ? w * ms[i] : 0.f, KP);
+      d[i] = ms[i] - mu;
+      if (lead && gv.cm.p) gv.cm.p[b * gv.cm.sB + t * gv.cm.sT + i * gv.cm.sE] = mu;
+    }
+    if (gv.cP.p) {
+      BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = 0; j < N; ++j) {
+        const float s = gs_tree_sum(act ? w * fmaf(d[i], d[j], Ps[i * N + j]) : 0.f, KP);
+        if (lead) gv.cP.p[b * gv.cP.sB + t * gv.cP.sT + (i * N + j) * gv.cP.sE] = s;
+      }
+    }
+  };
+
+  long long t = T - 1;
+  if (act) {
+    if (carry_in) {
+      BF_UNROLL for (int i = 0; i < N; ++i) ms[i] = v.m_in[ch * N + i];
+      BF_UNROLL for (int i = 0; i < NN; ++i) Ps[i] = v.P_in[ch * NN + i];
+    } else {
+      BF_UNROLL for (int i = 0; i < N; ++i) { ms[i] = ld(v.m, t, i); if constexpr (COMP) st(v.ms, t, i, ms[i]); }
+      BF_UNROLL for (int i = 0; i < NN; ++i) { Ps[i] = ld(v.P, t, i); if constexpr (COMP) st(v.Ps, t, i, Ps[i]); }
+    }
+  }
+  if (!carry_in) {
+    if constexpr (COLL) collapse(t);
+    --t;
+  }
+  for (; t >= 0; --t) {
+    if (act) {
+      float m[N], P[NN], mp[N], Pp[NN], X[NN], C[NN];
+      BF_UNROLL for (int i = 0; i < N; ++i) m[i] = ld(v.m, t, i);
+      BF_UNROLL for (int i = 0; i < NN; ++i) P[i] = ld(v.P, t, i);
+      if constexpr (KIND != RTS_UNSC) {
+        BF_UNROLL for (int i = 0; i < N; ++i) mp[i] = ld(v.pm, t, i);
+        BF_UNROLL for (int i = 0; i < NN; ++i) Pp[i] = ld(v.pP, t, i);
+      }
+      const float u0 = v.u ? v.u[b * v.u_sB + t * v.u_sT] : 0.f;
+      rts_linearize<N, KIND>(c, nullptr, t, u0, m, P, X, mp, Pp);
+      if constexpr (KIND == RTS_UNSC) {  // after the root, as in rts_reg_body
+        BF_UNROLL for (int i = 0; i < N; ++i) mp[i] = ld(v.pm, t, i);
+        BF_UNROLL for (int i = 0; i < NN; ++i) Pp[i] = ld(v.pP, t, i);
+      }
+      rts_step<N>(X, P, m, mp, Pp, ms, Ps, C, want_c);
+      if constexpr (COMP) {
+        BF_UNROLL for (int i = 0; i < N; ++i) st(v.ms, t, i, ms[i]);
+        BF_UNROLL for (int i = 0; i < NN; ++i) st(v.Ps, t, i, Ps[i]);
+        if (want_c) BF_UNROLL for (int i = 0; i < NN; ++i) st(v.Cs, t, i, C[i]);
+      }
+    }
+    if constexpr (COLL) collapse(t);
+  }
+  if (act) {
+    if (v.m_out) BF_UNROLL for (int i = 0; i < N; ++i) v.m_out[ch * N + i] = ms[i];
+    if (v.P_out) BF_UNROLL for (int i = 0; i < NN; ++i) v.P_out[ch * NN + i] = Ps[i];
+  }
+}
+
+template <int N, int KIND, int OUT, class Arg>
+__global__ void __launch_bounds__(64) rts_gs_reg_kernel(Arg c, RtsGsViews gv, long long B, long long T) {
+  rts_gs_reg_body<N, KIND, OUT, Arg>(c, gv, B, T);
 }
 
 }  // namespace bf

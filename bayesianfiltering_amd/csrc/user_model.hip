@@ -78,6 +78,16 @@ int user_kernel(const bf_user_model* handle, int kind, int ppt, int nw, int spec
     *fn = it->second;
     return BF_OK;
   }
+  if (kind == JIT_GS_RTS_REGS) {  // the three output sets (ppt = GS_COMP, GS_COLL, both) share one module
+    hipFunction_t f[3] = {nullptr, nullptr, nullptr};
+    rc = jit_load(jit_source(*um, kind, 0, nw, spec), {{jit_entry_name(kind, 1), &f[0]}, {jit_entry_name(kind, 2), &f[1]}, {jit_entry_name(kind, 3), &f[2]}});
+    if (rc != BF_OK) return rc;
+    for (int i = 0; i < 3; ++i) um->kernels[key_of(i + 1)] = f[i];
+    it = um->kernels.find(key);
+    if (it == um->kernels.end()) return set_error(BF_EINVAL, "no such variant of the kernel (kind %d, variant %d)", kind, ppt);
+    *fn = it->second;
+    return BF_OK;
+  }
   rc = jit_load(jit_source(*um, kind, ppt, nw, spec), {{jit_entry_name(kind), fn}});
   if (rc == BF_OK) um->kernels[key] = *fn;
   return rc;

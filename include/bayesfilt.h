@@ -162,7 +162,7 @@ int bf_device_count(void);
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
  * called on that thread (bf_kalman_filter_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
  * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_eks_smoother_f32,
- * bf_ffbs_sample_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
+ * bf_ffbs_sample_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_gs_smoother_f32, bf_gs_sample_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
 int bf_set_option(const char* name, int value);
 int bf_set_call_option(const char* name, int value);
@@ -464,6 +464,74 @@ int bf_eks_smoother_f32(const bf_model* model, const bf_cstream* u, const bf_out
 int bf_uks_smoother_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* u, const bf_out_desc* filtered,
                         int64_t B, int64_t T, const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream);
 
+/* ---- Gaussian-sum smoothing: the backward pass of bf_gsf_ekf_f32 / bf_ugsf_ukf_f32 with K >= 1 components ---------------
+ * In those filters the components never interact: each is an extended (unscented) Kalman chain started from its own
+ * initial mean, coupled only through the weight recursion w_{t,k} ~ w_{t-1,k} p(y_t | y_{<t}, k).  The model is a mixture over
+ * the index k of the initial component, so
+ *   p(x_{0:T-1} | y_{0:T-1}) = sum_k w_{T-1,k} p(x_{0:T-1} | y_{0:T-1}, k):
+ * the smoothed weights are the filter's weights at the LAST step of the whole series, constant in t, and smoothed component k
+ * is the RTS pass of chain k -- the recursion of bf_eks_smoother_f32 (uparams == NULL; registry dynamics or dynamics from
+ * source) or of bf_uks_smoother_f32 (uparams given) on chain (b, k), bit for bit.
+ * Inputs: the K-component streams means / covs / pred_means / pred_covs, all required, element (b, k, t, e) at
+ * ptr[b*sB + k*sK + t*sT + e*sE]; u is read at b; the carry is bf_smooth_carry with contiguous [B][K][n] / [B][K][n][n].
+ * Outputs, at least one: the per-component streams (means and covs together, cross_covs optional, sK honoured) and the
+ * collapsed moments (either or both; element (b, t, e) at ptr[b*sB + t*sT + e*sE], sK unused) with w = weights[b][.]:
+ *   mu_t = sum_k w_k m^s_{k,t},   Sigma_t = sum_k w_k (P^s_{k,t} + (m^s_{k,t} - mu_t)(m^s_{k,t} - mu_t)^T)
+ * (utils.collapse / bf_collapse_f32 with time-constant weights).  n <= 8 and K <= 64: formed inside the smoother, the chains of
+ * a trajectory in adjacent lanes, the sum over k an adjacent-pair tree over the power of two >= K whose order depends on K
+ * alone; with only collapsed outputs nothing per component is stored.  NaN weights or a NaN chain give NaN collapsed values
+ * for that trajectory only.  K > 64, n > 8 and "force_generic": with the per-component streams present bf_collapse_f32's
+ * kernel runs over them on the same stream (coll_mean / coll_cov must then be contiguous [B][T][E]); collapsed outputs alone
+ * are BF_EUNSUPPORTED there and the message names the limit.
+ * weights: DEVICE [B][K], required with a collapsed output.  Errors otherwise as the two smoothers above; BF_EINVAL for K < 1.
+ * Asynchronous on `stream`, no allocation; "force_generic" and "rts_load_mode" honoured (the staged data path serves
+ * per-component output on the contiguous reference layout, where the chains are B K one-component trajectories). */
+typedef struct bf_gs_smooth_desc {
+  bf_stream means;      /* E = n,   per component */
+  bf_stream covs;       /* E = n*n, per component; given together with means */
+  bf_stream cross_covs; /* E = n*n, optional, needs means / covs: entries as bf_smooth_desc's */
+  bf_stream coll_mean;  /* E = n,   collapsed, optional */
+  bf_stream coll_cov;   /* E = n*n, collapsed, optional */
+  const float* weights; /* DEVICE [B][K] */
+} bf_gs_smooth_desc;
+
+/* ABI guard of bf_gs_smooth_desc and bf_gs_sample_desc (below); a size of 0 = not mirrored. */
+int bf_gs_abi_check(size_t sizeof_gs_smooth_desc, size_t sizeof_gs_sample_desc);
+
+int bf_gs_smoother_f32(const bf_model* model, const bf_ukf_params* uparams /* NULL = extended route */, const bf_cstream* u,
+                       const bf_out_desc* filtered, int64_t B, int64_t T, int64_t K, const bf_smooth_carry* carry,
+                       const bf_gs_smooth_desc* out, void* stream);
+
+/* Joint draws from the smoothed mixture: sample (b, s) picks a component z ~ Cat(weights[b][.]) ONCE and is then the backward
+ * sampling recursion of bf_effbs_sample_f32 (uparams == NULL) / bf_uffbs_sample_f32 on chain (b, z) with noise row (b, s); its
+ * bits do not depend on S, on the other samples' components or on the launch shape.  (bf_sample_desc / bf_sample_carry and
+ * the recursion are declared below.)
+ *   c_j = the inclusive cumulative sum of weights[b][0..j] in index order, by sequential fp32 adds;
+ *   z   = the smallest j with c_j > v c_{K-1}, clamped to K-1, v = the sample's uniform in [0, 1);
+ *   c_{K-1} not finite or not > 0: the draw is invalid, z = -1, and that sample is NaN at every step and in the carry; other
+ *   samples are untouched.
+ * Noise: a stream, or keys[b] exactly as the samplers below (random.normal(keys[b], (S, T, n))).  Uniforms: comp_noise[B][S], or
+ * comp_keys[b] -> the S values bf_random_uniform_f32(comp_keys[b], S) writes.  comp_in[B][S] (a later chunk's components, or
+ * the caller's; values outside [0, K) count as invalid draws) replaces the draw; comp_out[B][S] receives the components.
+ * BF_EINVAL for K < 1, for weights missing where a draw is needed, and for both or neither of comp_noise and comp_keys
+ * without comp_in.  n <= 8: registers, one lane per (trajectory, sample); other n and "force_generic": one workgroup per
+ * (trajectory, component) serving the samples of its component ("ffbs_spl" is not read).  Asynchronous, no allocation. */
+struct bf_sample_carry;
+typedef struct bf_gs_sample_desc {
+  bf_stream samples;         /* E = n; the K axis is the sample s; required */
+  bf_cstream noise;          /* standard normals, same indexing; ptr == NULL: drawn from keys */
+  const uint32_t* keys;      /* DEVICE [B][2], required when noise.ptr == NULL */
+  const float* weights;      /* DEVICE [B][K], required unless comp_in is given */
+  const float* comp_noise;   /* DEVICE [B][S] uniforms in [0, 1) */
+  const uint32_t* comp_keys; /* DEVICE [B][2] */
+  const int32_t* comp_in;    /* DEVICE [B][S] */
+  int32_t* comp_out;         /* DEVICE [B][S] */
+} bf_gs_sample_desc;
+
+int bf_gs_sample_f32(const bf_model* model, const bf_ukf_params* uparams /* NULL = extended route */, const bf_cstream* u,
+                     const bf_out_desc* filtered, int64_t B, int64_t T, int64_t K, int32_t S, const struct bf_sample_carry* carry,
+                     const bf_gs_sample_desc* out, void* stream);
+
 /* ---- Posterior sampling: the backward half of forward-filter backward-sampling (dynamax's lgssm_posterior_sample) ----
  * Draws S joint trajectories x_{0:T-1} ~ p(x_{0:T-1} | y_{0:T-1}) per filtered trajectory from the streams the smoothers
  * read (same order, same F_t).  With xi_{s,t} in R^n standard normals:
@@ -478,7 +546,7 @@ int bf_uks_smoother_f32(const bf_model* model, const bf_ukf_params* uparams, con
  * singular G Q G^T, e.g. the constant-velocity model, is part of the definition and not an error).  xi = 0 gives the RTS
  * smoothed means.  One component (K = 1), flags == 0.
  * With bf_sampler_abi_check, the three samplers below, the unscented smoother above and the four entry points of the particle
- * smoother this header declares 36 entry points. */
+ * smoother, and the three of the Gaussian-sum smoother and sampler above, this header declares 39 entry points. */
 typedef struct bf_sample_desc {
   bf_stream samples;    /* E = n; the K axis is the sample s: ptr[b*sB + s*sK + t*sT + e*sE]; required */
   bf_cstream noise;     /* standard normals, same indexing; ptr == NULL: drawn from keys */
