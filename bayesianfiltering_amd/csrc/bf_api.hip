@@ -94,6 +94,10 @@ static Option g_kf_small_mode{1, OPT_KF_SMALL_MODE};   // bf_set_option "kf_smal
 static Option g_force_generic{0, OPT_FORCE_GENERIC};  // 1 = run the run-time-dimension kernel even where a compiled instance exists
 Option& force_generic_option() { return g_force_generic; }  // read by the backward family's entry points (backward_host.hpp)
 Option& ffbs_spl_option();  // ffbs_sampler.hip: 0 = from S and n, else samples per lane of the register kernel
+Option& pkf_block_option();  // kf_pscan.hip: 0 = from (B, T), else the block length of the parallel-in-time Kalman filter
+long long kf_pscan_workspace_bytes(int n, int m, long long B, long long T, int block);
+int launch_kf_pscan(const bf_lgssm* model, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
+                    const bf_out_desc* out, void* workspace, long long workspace_bytes, hipStream_t stream);
 
 // A shape / option the compiled instances do not cover falls through to the run-time-dimension kernel
 // (generic_scan.hip); if that cannot run it either, both reasons are reported.
@@ -183,6 +187,10 @@ static int set_option_impl(const char* name, int value, bool this_call_only) {
     if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return bf::set_error(BF_EINVAL, "ffbs_spl must be 0, 1, 2, 4 or 8");
     return assign(bf::ffbs_spl_option());
   }
+  if (name && std::strcmp(name, "pkf_block") == 0) {
+    if (value != 0 && (value < 4 || value > 4096)) return bf::set_error(BF_EINVAL, "pkf_block must be 0 or 4..4096");
+    return assign(bf::pkf_block_option());
+  }
   if (name && std::strcmp(name, "gsf_structured") == 0) {
     if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "gsf_structured must be 0 or 1");
     return assign(bf::g_gsf_structured);
@@ -256,6 +264,16 @@ int bf_kalman_filter_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, 
     return bf::with_generic_fallback(bf::launch_kf_mfma(model, y, B, T, carry, out, hs, 1, false, 0, nullptr), generic);
   return bf::with_generic_fallback(
       bf::launch_kf_group(model, y, B, T, carry, out, hs, bf::g_kf_emit_mode.load(), bf::g_kf_lanes.load()), generic);
+}
+
+int64_t bf_kalman_pscan_workspace_bytes(int32_t n, int32_t m, int64_t B, int64_t T, int32_t block) {
+  return bf::kf_pscan_workspace_bytes(n, m, B, T, block);
+}
+
+int bf_kalman_filter_pscan_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T, const bf_carry* carry,
+                               const bf_out_desc* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  return bf::launch_kf_pscan(model, y, B, T, carry, out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int bf_gsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t K,

@@ -1,0 +1,21 @@
+// Instantiations of the parallel-in-time Kalman kernels (kf_pscan.hpp) for a slice of the (n, m) table; split over several
+// translation units to build in parallel.
+#include "kf_pscan.hpp"
+
+namespace bf {
+
+int launch_kf_pscan_group_d(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
+        const bf_out_desc* out, float* workspace, int L, hipStream_t stream, bool* matched) {
+#define BF_CASE(N_, M_)                                                            \
+  if (p->n == N_ && p->m == M_) {                                                  \
+    *matched = true;                                                               \
+    return launch_pscan_nm<N_, M_>(p, y, B, T, carry, out, workspace, L, stream); \
+  }
+  BF_CASE(4, 3);
+  BF_CASE(4, 4);
+#undef BF_CASE
+  *matched = false;
+  return BF_OK;
+}
+
+}  // namespace bf

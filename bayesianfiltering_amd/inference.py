@@ -152,21 +152,24 @@ class FilterCarry(NamedTuple):
     covariances: Any
 
 
-def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
-                  fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
-                  return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None):
-    """Batched Kalman filter == ``gaussian_sum_filter(params, y, num_components=1)`` of the
-    reference for linear ``f(x,q,u) = A x + G q``, ``h(x,r,u) = H x + D r`` with the initial
-    component mean given explicitly (the reference samples it from N(m0, P0) with PRNGKey(0),
-    inference.py:367; pass ``initial_means=`` to choose it, default ``params.initial_mean``).
+class _KalmanCall:
+    """The arguments of a Kalman entry point of the C-ABI (bf_kalman_filter_f32, bf_kalman_filter_pscan_f32) built from the
+    keyword set of :func:`kalman_filter`: model, observations, carry and output descriptors, with the tensors they point to."""
 
-    emissions: (T, m) or (B, T, m).  Returns PosteriorGaussianSumFiltered with arrays shaped
-    (1, T, ...) or (B, 1, T, ...); ``layout='batch_inner'`` returns the same logical shapes as
-    strided views of a [K][T][E][B] buffer (the fastest store pattern).  ``out`` may hold a
-    previously returned posterior whose buffers are reused.
-    """
+    def result(self):
+        sq = self.squeeze
+        post = PosteriorGaussianSumFiltered(**{k: (v[0] if (sq and v is not None) else v) for k, v in self.bufs.items()})
+        extras = []
+        if self.ll is not None:
+            extras.append(self.ll[0] if sq else self.ll)
+        if self.c_out is not None:
+            extras.append(self.c_out)
+        return (post, *extras) if extras else post
+
+
+def _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
+                 return_carry, device):
     torch = _torch()
-    lib = _lib.require_gpu()
     mdl = _Lgssm(params)
     n, m = mdl.n, mdl.m
     y = _dev_f32(emissions, device)
@@ -233,18 +236,35 @@ def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=
                             torch.empty((B, 1, n, n), dtype=torch.float32, device=y.device))
         cr.w_out, cr.m_out, cr.P_out = (t.data_ptr() for t in c_out)
 
-    stream = torch.cuda.current_stream(y.device).cuda_stream
-    _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
-    _lib.check(lib.bf_kalman_filter_f32(C.byref(mdl.c), C.byref(yd), B, T, C.byref(cr), C.byref(od),
-                                        C.c_void_p(stream)))
+    k = _KalmanCall()
+    k.mdl, k.y, k.B, k.T, k.squeeze = mdl, y, B, T, squeeze
+    k.carry_in = (w_in, m_in, P_in)      # (kept alive: cr points into them)
+    k.bufs, k.ll, k.c_out = bufs, ll, c_out
+    k.od, k.yd, k.cr = od, yd, cr
+    k.stream = torch.cuda.current_stream(y.device).cuda_stream
+    return k
 
-    post = PosteriorGaussianSumFiltered(**{k: (v[0] if (squeeze and v is not None) else v) for k, v in bufs.items()})
-    extras = []
-    if return_loglik:
-        extras.append(ll[0] if squeeze else ll)
-    if return_carry:
-        extras.append(c_out)
-    return (post, *extras) if extras else post
+
+def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
+                  fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
+                  return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None):
+    """Batched Kalman filter == ``gaussian_sum_filter(params, y, num_components=1)`` of the
+    reference for linear ``f(x,q,u) = A x + G q``, ``h(x,r,u) = H x + D r`` with the initial
+    component mean given explicitly (the reference samples it from N(m0, P0) with PRNGKey(0),
+    inference.py:367; pass ``initial_means=`` to choose it, default ``params.initial_mean``).
+
+    emissions: (T, m) or (B, T, m).  Returns PosteriorGaussianSumFiltered with arrays shaped
+    (1, T, ...) or (B, 1, T, ...); ``layout='batch_inner'`` returns the same logical shapes as
+    strided views of a [K][T][E][B] buffer (the fastest store pattern).  ``out`` may hold a
+    previously returned posterior whose buffers are reused.
+    """
+    lib = _lib.require_gpu()
+    k = _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
+                     return_carry, device)
+    _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
+    _lib.check(lib.bf_kalman_filter_f32(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od),
+                                        C.c_void_p(k.stream)))
+    return k.result()
 
 
 def _param_dims(params):

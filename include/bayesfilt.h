@@ -142,6 +142,8 @@ int bf_device_count(void);
  *                   samples of a trajectory in one lane, 8 for S > 8 (default),
  *                   otherwise one of the compiled counts 1, 2, 4, 8 (the arithmetic of a sample does not depend on it);
  *                   the kernels built around dynamics given as source have the same four counts.
+ *   "pkf_block":    block length L of bf_kalman_filter_pscan_f32: 0 (default) = from (B, T), otherwise 4 ... 4096 (the arithmetic of
+ *                   a trajectory depends on T and L alone).
  *   "gsf_structured": 1 (default) lets bf_gsf_ekf_f32 use the structure-aware kernel instances
  *                   (banded Lorenz-96 Jacobian, selection emission) when the model qualifies;
  *                   0 forces the dense generic instances.
@@ -160,7 +162,7 @@ int bf_device_count(void);
  *                   and serves particle counts up to 4 096 with registry functions.
  * bf_set_option changes the PROCESS-WIDE default.  A library or a thread that must not disturb -- or be disturbed by -- other
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
- * called on that thread (bf_kalman_filter_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
+ * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
  * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_eks_smoother_f32,
  * bf_ffbs_sample_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_gs_smoother_f32, bf_gs_sample_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
@@ -173,6 +175,32 @@ int bf_set_call_option(const char* name, int value);
  * y: observations, element (b, t, e) at y->ptr[b*sB + t*sT + e*sE], E = m. */
 int bf_kalman_filter_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T,
                          const bf_carry* carry, const bf_out_desc* out, void* stream);
+
+/* Parallel-in-time Kalman filter for few long trajectories: the model, streams, carry and log-likelihood of
+ * bf_kalman_filter_f32, with time cut into blocks of L steps that run on separate lanes (the associative filtering elements
+ * of Sarkka & Garcia-Fernandez 2021; the scheme is stated at the head of csrc/kf_pscan.hpp).  Three launches on `stream`,
+ * no waiting between workgroups: fold (one lane per (trajectory, block) builds the block's aggregate), scan (one workgroup per
+ * trajectory turns the aggregates into every block's start state), emit (one lane per (trajectory, block) runs the ordinary
+ * update -> predict step of bf_kalman_filter_f32 from its block's start state and stores the streams, any strides).
+ * Inside a block the outputs are the ordinary filter's from that block's start state; the start states come from a jitter-free
+ * recursion, so the result agrees with bf_kalman_filter_f32 to fp32 tolerance (1e-5 relative), not bit for bit.  A trajectory's
+ * bits depend on (T, L) alone.  A NaN / Inf observation at step t gives NaN in every stream and in the carry from t on, in that
+ * trajectory only -- the covariances included, which bf_kalman_filter_f32 leaves finite: a step whose innovation is not finite has no posterior.
+ * L: option "pkf_block" (4..4096; 0 = default: the largest of ceil(B T / 65 536) -- one (trajectory, block) lane per lane of the
+ * device --, the smallest s with 50 s^2 >= T -- the balance between the per-trajectory scan and the per-lane work -- and 16,
+ * at most 4096).
+ * workspace: a caller-owned DEVICE buffer of at least bf_kalman_pscan_workspace_bytes(n, m, B, T, L) =
+ *   4 B ceil(T / L) (4 n^2 + 3 n) bytes, 4-byte aligned; its contents before and after the call mean nothing.
+ * bf_kalman_pscan_workspace_bytes: `block` = 0 reads "pkf_block" as the filter call would and else uses the default; a negative
+ * result is a BF_E* code (B or T <= 0, a block length outside 4..4096, dimensions that are not built, B ceil(T / L) >= 2^31).
+ * BF_EUNSUPPORTED: n > 6 or m > 4 (register kernels: the scan needs scratch from n = 7; the message names the limit), per-step covariances (Q_steps or
+ * R_steps > 1: "constant Q and R"), collapsed streams, a singular S = H G Q G^T H^T + D R D^T.  BF_EINVAL: NULL arguments,
+ * B or T <= 0, a workspace that is too small (the message names the bytes needed).  Every check precedes the first HIP call.
+ * With these two, this header declares 41 entry points. */
+int64_t bf_kalman_pscan_workspace_bytes(int32_t n, int32_t m, int64_t B, int64_t T, int32_t block); /* < 0: BF_E* */
+int bf_kalman_filter_pscan_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T,
+                               const bf_carry* carry, const bf_out_desc* out,
+                               void* workspace, int64_t workspace_bytes, void* stream);
 
 /* A state-space model built from the function registry (the device-side replacement of the
  * Python callables f(x,q,u), h(x,r,u) of gaussfiltax/models.py:46-49; ids and theta layouts:
@@ -546,7 +574,8 @@ int bf_gs_sample_f32(const bf_model* model, const bf_ukf_params* uparams /* NULL
  * singular G Q G^T, e.g. the constant-velocity model, is part of the definition and not an error).  xi = 0 gives the RTS
  * smoothed means.  One component (K = 1), flags == 0.
  * With bf_sampler_abi_check, the three samplers below, the unscented smoother above and the four entry points of the particle
- * smoother, and the three of the Gaussian-sum smoother and sampler above, this header declares 39 entry points. */
+ * smoother, and the three of the Gaussian-sum smoother and sampler above, this header declares 39 entry points (41 with the two of the
+ * parallel-in-time Kalman filter above). */
 typedef struct bf_sample_desc {
   bf_stream samples;    /* E = n; the K axis is the sample s: ptr[b*sB + s*sK + t*sT + e*sE]; required */
   bf_cstream noise;     /* standard normals, same indexing; ptr == NULL: drawn from keys */

@@ -1,0 +1,174 @@
+"""parallel_kalman_filter on the GPU: parity with the float64 recursion of kalman_filter (reference's jitter), the bits that
+must not depend on the launch shape, chunking through the carry, NaN containment, the smoother downstream, default blocks.
+
+Measured on an MI355X, worst over the parity cases below against the jittered float64 recursion (bound 1e-5): rel_err 1.4e-6
+(means), 1.5e-6 (covariances), 1.8e-6 (predicted means), 9.7e-7 (predicted covariances), 1.8e-6 (log-likelihood); elem_err(ev=2)
+5.1e-6 on both covariance streams; constant-velocity model 2.0e-7 ... 4.2e-7."""
+import numpy as np
+import pytest
+import torch
+
+import bayesianfiltering_amd as bfa
+from tests import common as cm
+from tests import parallel_kalman_cases as pk
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-5   # the project's standing fp32 tolerance
+MODELS = ["1x1", "2x2", "3x1", "4x2", "4x4", "bias", "5x2", "6x3"]   # every built n; 'bias': noise biases, dq = 2 < n = 4
+# (T, block): 301 blocks -- across a wave and a 256-thread tile, ragged last block of 3; 16 blocks inside one wave, ragged;
+# one block; one step
+SHAPES = [(1203, 4), (1000, 64), (37, 64), (1, 64)]
+B, TMAX = 3, 1203
+
+
+def run(name, T, block, **kw):
+    a, ys, init, ref = pk.case(name, kw.pop("B", B), TMAX)
+    return bfa.parallel_kalman_filter(cm.product_params(a), ys[:, :T], initial_means=init, block=block, **kw)
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def same_bits(x, y):
+    return torch.equal(x.contiguous().view(torch.int32), y.contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize("T,block", SHAPES)
+@pytest.mark.parametrize("name", MODELS)
+def test_parity_with_the_float64_recursion(name, T, block):
+    ref = pk.case(name, B, TMAX)[3]
+    post, ll = run(name, T, block, return_loglik=True)
+    assert host(post.weights).min() == 1.0 and host(post.weights).max() == 1.0
+    got = {k: host(getattr(post, k)) for k in pk.STREAMS}
+    got["loglik"] = host(ll)
+    for k, v in got.items():
+        r = ref[k][:, :, :T]
+        err = cm.rel_err(v, r)
+        elem = cm.elem_err(v, r, ev=2) if "covariances" in k else None
+        print(f"parity {name} T={T} block={block} {k}: rel {err:.2e}" + (f" elem {elem:.2e}" if elem is not None else ""))
+        assert err <= TOL, (k, err)
+        if elem is not None:
+            assert elem <= TOL, (k, elem)
+
+
+def test_marginally_stable_model():
+    ref = pk.case("cv", B, TMAX)[3]
+    post = run("cv", 1203, 4)
+    for k in pk.STREAMS:
+        err = cm.rel_err(host(getattr(post, k)), ref[k])
+        print(f"cv {k}: rel {err:.2e}")
+        assert err <= TOL, (k, err)
+
+
+def test_bits_do_not_depend_on_the_launch():
+    T, block = 301, 4
+    a, ys, init, _ = pk.case("4x2", 5, TMAX)
+    p = cm.product_params(a)
+    call = lambda **kw: bfa.parallel_kalman_filter(p, ys[:, :T], initial_means=init, block=block, **kw)
+    full, ll, carry = call(return_loglik=True, return_carry=True)
+    # the same call twice
+    again, ll2, carry2 = call(return_loglik=True, return_carry=True)
+    for x, y in zip(full + (ll,) + tuple(carry), again + (ll2,) + tuple(carry2)):
+        assert same_bits(x, y)
+    # trajectory b alone
+    for b in (0, 3):
+        one = bfa.parallel_kalman_filter(p, ys[b:b + 1, :T], initial_means=init[b:b + 1], block=block)
+        for k in bfa.FULL5:
+            assert same_bits(getattr(one, k)[0], getattr(full, k)[b]), (b, k)
+    # layouts
+    inner, ll_inner = call(layout="batch_inner", return_loglik=True)
+    for k in bfa.FULL5:
+        assert same_bits(getattr(inner, k), getattr(full, k)), k
+    assert same_bits(ll_inner, ll)
+    # subsets of the streams
+    for fields in (("means",), bfa.FILTERED):
+        part = call(fields=fields)
+        for k in bfa.FULL5:
+            assert (getattr(part, k) is None) == (k not in fields)
+            if k in fields:
+                assert same_bits(getattr(part, k), getattr(full, k)), (fields, k)
+    # out= reuse and a reused workspace against a fresh one
+    n, m = 4, 2
+    ws = torch.full((bfa.parallel_kalman_workspace_bytes(n, m, 5, T, block) + 64,), 0xFF, dtype=torch.uint8, device="cuda")
+    reused = call(out=again, workspace=ws)
+    assert reused.means.data_ptr() == again.means.data_ptr()
+    twice = call(workspace=ws)
+    for k in bfa.FULL5:
+        assert same_bits(getattr(reused, k), getattr(full, k)), k
+        assert same_bits(getattr(twice, k), getattr(full, k)), k
+    # the carry is the last prediction
+    assert same_bits(carry.means[:, 0], full.predicted_means[:, 0, -1])
+    assert same_bits(carry.covariances[:, 0], full.predicted_covariances[:, 0, -1])
+    assert host(carry.weights).tolist() == [[1.0]] * 5
+
+
+def test_chunks_through_the_carry():
+    """[0, 600) then [600, 1203) against one shot.  Not bit-equal: the one-shot start state of block 150 comes from the scan,
+    the chunked one from the first chunk's emit launch (the ordinary step's prediction)."""
+    a, ys, init, _ = pk.case("4x2", B, TMAX)
+    p = cm.product_params(a)
+    whole = bfa.parallel_kalman_filter(p, ys, initial_means=init, block=4)
+    first, carry = bfa.parallel_kalman_filter(p, ys[:, :600], initial_means=init, block=4, return_carry=True)
+    second = bfa.parallel_kalman_filter(p, ys[:, 600:], carry=carry, block=4)
+    for k in pk.STREAMS:
+        joined = np.concatenate([host(getattr(first, k)), host(getattr(second, k))], axis=2)
+        assert cm.rel_err(joined, host(getattr(whole, k))) <= TOL, k
+
+
+def _nan_runs():
+    a, ys, init, _ = pk.case("4x2", B, TMAX)
+    p = cm.product_params(a)
+    T = 64
+    clean, ll_clean = bfa.parallel_kalman_filter(p, ys[:, :T], initial_means=init, block=4, return_loglik=True)
+    bad = np.array(ys[:, :T])
+    bad[1, 7, 0] = np.nan
+    post, ll = bfa.parallel_kalman_filter(p, bad, initial_means=init, block=4, return_loglik=True)
+    return clean._asdict() | {"loglik": ll_clean}, post._asdict() | {"loglik": ll}
+
+
+def test_nan_observation_stays_in_its_trajectory():
+    """NaN at (b = 1, t = 7), block = 4: every stream of trajectory 1 -- weights, means, covariances, both predictions, the
+    log-likelihood -- is NaN for every t >= 7 and finite before (steps 4 ... 6 share the NaN's block); the other trajectories
+    keep their bits.  (The covariance recursion reads no observation: the update sets it to NaN when the innovation is not
+    finite, csrc/kf_pscan.hpp ps_update.)"""
+    clean, post = _nan_runs()
+    for k in post:
+        v = host(post[k])
+        assert np.isnan(v[1, :, 7:]).all(), k
+        assert np.isfinite(v[1, :, :7]).all(), k
+        assert same_bits(post[k][1, :, :7], clean[k][1, :, :7]), k
+        for b in (0, 2):
+            assert same_bits(post[k][b], clean[k][b]), (k, b)
+
+
+def test_nan_observation_reaches_the_carry_and_a_single_block():
+    """The same with one block (T <= block: the emit launch alone) and in the carry a later chunk would start from."""
+    a, ys, init, _ = pk.case("4x2", B, TMAX)
+    bad = np.array(ys[:, :16])
+    bad[1, 7, 1] = np.inf
+    post, carry = bfa.parallel_kalman_filter(cm.product_params(a), bad, initial_means=init, block=64, return_carry=True)
+    for k in bfa.FULL5:
+        v = host(getattr(post, k))
+        assert np.isnan(v[1, :, 7:]).all() and np.isfinite(v[1, :, :7]).all() and np.isfinite(v[[0, 2]]).all(), k
+    for x in carry:
+        assert np.isnan(host(x)[1]).all() and np.isfinite(host(x)[[0, 2]]).all()
+
+
+def test_smoother_downstream():
+    a, ys, init, _ = pk.case("4x2", B, TMAX)
+    p = cm.product_params(a)
+    par = bfa.rts_smoother(p, bfa.parallel_kalman_filter(p, ys[:, :301], initial_means=init, block=4))
+    seq = bfa.rts_smoother(p, bfa.kalman_filter(p, ys[:, :301], initial_means=init))
+    for k in ("smoothed_means", "smoothed_covariances"):
+        assert cm.rel_err(host(getattr(par, k)), host(getattr(seq, k))) <= TOL, k
+
+
+@pytest.mark.parametrize("Bd,Td", [(1, 5000), (64, 300), (4096, 16)])
+def test_default_block(Bd, Td):
+    a = pk.model("4x2")
+    ys = cm.simulate_batch(a, Bd, Td, seed=3)
+    post = bfa.parallel_kalman_filter(cm.product_params(a), ys)
+    for k in bfa.FULL5:
+        assert torch.isfinite(getattr(post, k)).all(), k
