@@ -7,7 +7,7 @@ from typing import NamedTuple, Optional, Any
 import numpy as np
 
 from . import _lib
-from .inference import _torch, _dev_f32, _host_f32, _fp, _stream_desc, _time_varying, _Model, _param_dims, ParamsUKF
+from .inference import _torch, _host_f32, _fp, _stream_desc, _time_varying, _Model, _param_dims, _inputs_desc, _ukf_params
 from .nonlinearities import DYN_LINEAR, DeviceFunction, require_device_function
 
 
@@ -33,31 +33,6 @@ def _batched(x, event_dims):
     if x is None:
         return None
     return x.unsqueeze(0) if x.dim() == 2 + event_dims else x
-
-
-def _ukf_params(uparams, extended):
-    """``uparams`` (a :class:`ParamsUKF` or a 3-tuple) as the C struct; it excludes ``extended=True``."""
-    if extended:
-        raise ValueError("uparams selects the unscented route; it cannot be combined with extended=True")
-    if not isinstance(uparams, ParamsUKF):
-        uparams = ParamsUKF(*uparams)
-    return _lib.bf_ukf_params(float(uparams.alpha), float(uparams.beta), float(uparams.kappa))
-
-
-def _inputs_desc(inputs, B, T, dev, keep):
-    """bf_cstream of the filter's inputs ((T,), (T, d) or (B, T, d); None = zeros)."""
-    ud = _lib.bf_cstream()
-    if inputs is not None:
-        u = _dev_f32(inputs, dev)
-        if u.dim() == 1:
-            u = u.reshape(1, T, 1)
-        elif u.dim() == 2:
-            u = u.reshape(1, T, -1)
-        if u.shape[1] != T or u.shape[0] not in (1, B):
-            raise ValueError(f"inputs must be (T,), (T,d) or (B,T,d); got {tuple(u.shape)}")
-        keep.append(u)
-        ud.ptr, ud.sB, ud.sT, ud.sE = u.data_ptr(), (u.stride(0) if u.shape[0] == B else 0), u.stride(1), 1
-    return ud
 
 
 class _Backward(NamedTuple):

@@ -37,6 +37,7 @@
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; LDS is dynamic): DESIGN.md 4d.
 #include <cstdlib>
 #include <vector>
+#include "forward_host.hpp"
 #include "agsf_generic_device.hpp"
 #include "user_model.hpp"
 
@@ -150,14 +151,13 @@ int launch_agsf_generic(const bf_model* p, const bf_ukf_params* up, const bf_cst
   }
   rc = hipGetLastError() == hipSuccess ? BF_OK : set_error(BF_EHIP, "launch of the normals kernel failed");
   if (rc == BF_OK) {
-    const CView yv{y->ptr, y->sB, y->sT, y->sE};
-    const UViewG uv{u && u->ptr ? u->ptr : nullptr, u ? u->sB : 0, u ? u->sT : 0};
-    const CarryView cr{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
+    const ForwardViews fv = forward_views(y, carry, out);   // (of its streams the tree emits three: AgsfOut)
+    const UViewG uv = input_view<UViewG>(u);
     const AgsfOut ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs), d_leaf_idx};
-    if (up) rc = nt == 64 ? launch_ag<64, AgUkfNodes<64>>(gu, tr, yv, uv, cr, ov, gs, ez, es, B, T, grid, lds_bytes, stream)
-                          : launch_ag<256, AgUkfNodes<256>>(gu, tr, yv, uv, cr, ov, gs, ez, es, B, T, grid, lds_bytes, stream);
-    else rc = nt == 64 ? launch_ag<64, AgEkfNodes<64>>(ge, tr, yv, uv, cr, ov, gs, ez, es, B, T, grid, lds_bytes, stream)
-                       : launch_ag<256, AgEkfNodes<256>>(ge, tr, yv, uv, cr, ov, gs, ez, es, B, T, grid, lds_bytes, stream);
+    if (up) rc = nt == 64 ? launch_ag<64, AgUkfNodes<64>>(gu, tr, fv.y, uv, fv.carry, ov, gs, ez, es, B, T, grid, lds_bytes, stream)
+                          : launch_ag<256, AgUkfNodes<256>>(gu, tr, fv.y, uv, fv.carry, ov, gs, ez, es, B, T, grid, lds_bytes, stream);
+    else rc = nt == 64 ? launch_ag<64, AgEkfNodes<64>>(ge, tr, fv.y, uv, fv.carry, ov, gs, ez, es, B, T, grid, lds_bytes, stream)
+                       : launch_ag<256, AgEkfNodes<256>>(ge, tr, fv.y, uv, fv.carry, ov, gs, ez, es, B, T, grid, lds_bytes, stream);
   }
   (void)hipFreeAsync(scratch, stream);
   return rc;

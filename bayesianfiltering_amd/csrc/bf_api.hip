@@ -3,6 +3,7 @@
 // their launchers: rts_smoother.hip, ffbs_sampler.hip, pf_sampler.hip.)
 #include <cstring>
 #include "bf_common.hpp"
+#include "forward_host.hpp"
 #include "user_model.hpp"
 #include "bf_rng.hpp"
 
@@ -145,71 +146,41 @@ int bf_device_count(void) {
 }
 
 static int set_option_impl(const char* name, int value, bool this_call_only) {
-  auto assign = [&](bf::Option& o) {
+  // {name, the option, which values it takes, what a refusal says}
+  struct Row {
+    const char* name;
+    bf::Option& option;
+    bool (*accept)(int);
+    const char* message;
+  };
+  const auto flag = [](int v) { return v == 0 || v == 1; };
+  const Row rows[] = {
+      {"kf_emit_mode", bf::g_kf_emit_mode, [](int v) { return v >= -1 && v <= 2; }, "kf_emit_mode must be -1..2"},
+      {"kf_lanes", bf::g_kf_lanes, [](int v) { return v >= 0 && v <= 64 && (v & (v - 1)) == 0; }, "kf_lanes must be 0 or a power of two <= 64"},
+      {"kf_small_mode", bf::g_kf_small_mode, flag, "kf_small_mode must be 0 or 1"},
+      {"force_generic", bf::g_force_generic, flag, "force_generic must be 0 or 1"},
+      {"ugsf_force_generic", bf::g_ugsf_force_generic, flag, "ugsf_force_generic must be 0 or 1"},
+      {"agsf_force_generic", bf::g_agsf_force_generic, flag, "agsf_force_generic must be 0 or 1"},
+      {"rts_load_mode", bf::rts_load_mode_option(), [](int v) { return v == -1 || v == 0 || v == 2; }, "rts_load_mode must be -1, 0 or 2"},
+      {"ffbs_spl", bf::ffbs_spl_option(), [](int v) { return v == 0 || v == 1 || v == 2 || v == 4 || v == 8; }, "ffbs_spl must be 0, 1, 2, 4 or 8"},
+      {"pkf_block", bf::pkf_block_option(), [](int v) { return v == 0 || (v >= 4 && v <= 4096); }, "pkf_block must be 0 or 4..4096"},
+      {"gsf_structured", bf::g_gsf_structured, flag, "gsf_structured must be 0 or 1"},
+      {"bpf_variant", bf::g_bpf_variant, flag, "bpf_variant must be 0 or 1"},
+      {"bpf_hbm_mode", bf::g_bpf_hbm_mode, [](int v) { return v >= 0 && v <= 2; }, "bpf_hbm_mode must be 0, 1 or 2"},
+      {"bpf_arith", bf::g_bpf_arith, flag, "bpf_arith must be 0 or 1"},
+      {"bpf_spec", bf::g_bpf_spec, flag, "bpf_spec must be 0 or 1"},
+  };
+  for (const Row& r : rows) {
+    if (!name || std::strcmp(name, r.name) != 0) continue;
+    if (!r.accept(value)) return bf::set_error(BF_EINVAL, "%s", r.message);
     if (this_call_only) {
       bf::CallOverrides& c = bf::call_overrides();
-      c.value[o.id] = value;
-      c.armed[o.id] = true;
+      c.value[r.option.id] = value;
+      c.armed[r.option.id] = true;
     } else {
-      o = value;
+      r.option = value;
     }
     return BF_OK;
-  };
-  if (name && std::strcmp(name, "kf_emit_mode") == 0) {
-    if (value < -1 || value > 2) return bf::set_error(BF_EINVAL, "kf_emit_mode must be -1..2");
-    return assign(bf::g_kf_emit_mode);
-  }
-  if (name && std::strcmp(name, "kf_lanes") == 0) {
-    if (value < 0 || value > 64 || (value & (value - 1)) != 0) return bf::set_error(BF_EINVAL, "kf_lanes must be 0 or a power of two <= 64");
-    return assign(bf::g_kf_lanes);
-  }
-  if (name && std::strcmp(name, "kf_small_mode") == 0) {
-    if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "kf_small_mode must be 0 or 1");
-    return assign(bf::g_kf_small_mode);
-  }
-  if (name && std::strcmp(name, "force_generic") == 0) {
-    if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "force_generic must be 0 or 1");
-    return assign(bf::g_force_generic);
-  }
-  if (name && std::strcmp(name, "ugsf_force_generic") == 0) {
-    if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "ugsf_force_generic must be 0 or 1");
-    return assign(bf::g_ugsf_force_generic);
-  }
-  if (name && std::strcmp(name, "agsf_force_generic") == 0) {
-    if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "agsf_force_generic must be 0 or 1");
-    return assign(bf::g_agsf_force_generic);
-  }
-  if (name && std::strcmp(name, "rts_load_mode") == 0) {
-    if (value != -1 && value != 0 && value != 2) return bf::set_error(BF_EINVAL, "rts_load_mode must be -1, 0 or 2");
-    return assign(bf::rts_load_mode_option());
-  }
-  if (name && std::strcmp(name, "ffbs_spl") == 0) {
-    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return bf::set_error(BF_EINVAL, "ffbs_spl must be 0, 1, 2, 4 or 8");
-    return assign(bf::ffbs_spl_option());
-  }
-  if (name && std::strcmp(name, "pkf_block") == 0) {
-    if (value != 0 && (value < 4 || value > 4096)) return bf::set_error(BF_EINVAL, "pkf_block must be 0 or 4..4096");
-    return assign(bf::pkf_block_option());
-  }
-  if (name && std::strcmp(name, "gsf_structured") == 0) {
-    if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "gsf_structured must be 0 or 1");
-    return assign(bf::g_gsf_structured);
-  }
-  if (name && std::strcmp(name, "bpf_variant") == 0) {
-    if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "bpf_variant must be 0 or 1");
-    return assign(bf::g_bpf_variant);
-  }
-  if (name && std::strcmp(name, "bpf_hbm_mode") == 0) {
-    if (value < 0 || value > 2) return bf::set_error(BF_EINVAL, "bpf_hbm_mode must be 0, 1 or 2");
-    return assign(bf::g_bpf_hbm_mode);
-  }
-  if (name && std::strcmp(name, "bpf_arith") == 0) {
-    if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "bpf_arith must be 0 or 1");
-    return assign(bf::g_bpf_arith);
-  }
-  if (name && std::strcmp(name, "bpf_spec") == 0) {
-    if (value < 0 || value > 1) return bf::set_error(BF_EINVAL, "bpf_spec must be 0 or 1");
-    return assign(bf::g_bpf_spec);
   }
   return bf::set_error(BF_EINVAL, "unknown option '%s'", name ? name : "(null)");
 }
@@ -243,14 +214,7 @@ int bf_kalman_filter_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, 
     return bf::set_error(BF_EINVAL, "collapsed streams are produced by bf_gsf_ekf_f32 (with one component they equal means / covs)");
   if (!model || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
   if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
-    return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->A || !model->H || !model->Q || !model->R) return bf::set_error(BF_EINVAL, "A, H, Q, R are required");
-  if (!model->G && model->dq != model->n) return bf::set_error(BF_EINVAL, "G == NULL requires dq == n");
-  if (!model->D && model->dr != model->m) return bf::set_error(BF_EINVAL, "D == NULL requires dr == m");
-  if (model->Q_steps < 1 || model->R_steps < 1) return bf::set_error(BF_EINVAL, "Q_steps / R_steps must be >= 1");
-  if (!y->ptr) return bf::set_error(BF_EINVAL, "observations pointer is NULL");
-  if (!carry->m_in || !carry->P_in) return bf::set_error(BF_EINVAL, "carry.m_in and carry.P_in are required");
+  if (int rc; (rc = bf::check_lgssm(model)) || (rc = bf::check_streams(y, carry))) return rc;
   hipStream_t hs = static_cast<hipStream_t>(stream);
   auto generic = [&]() { return bf::launch_kf_generic(model, y, B, T, carry, out, hs); };
   if (bf::g_force_generic.load()) return generic();
@@ -281,11 +245,7 @@ int bf_gsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream*
   bf::CallOptionScope call_option_scope;
   if (!model || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
   if (B <= 0 || T <= 0 || K <= 0) return bf::set_error(BF_EINVAL, "B, T and K must be positive");
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
-    return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
-  if (!y->ptr) return bf::set_error(BF_EINVAL, "observations pointer is NULL");
-  if (!carry->m_in || !carry->P_in) return bf::set_error(BF_EINVAL, "carry.m_in and carry.P_in are required");
+  if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_streams(y, carry))) return rc;
   hipStream_t hs = static_cast<hipStream_t>(stream);
   auto generic = [&]() { return bf::launch_gsf_generic(model, y, u, B, T, K, carry, out, hs); };
   if (model->user && bf::g_force_generic.load() == 0 && bf::gsf_user_regs_eligible(model, K, out))   // from source, n <= 8: state in registers
@@ -329,12 +289,7 @@ int bf_ugsf_ukf_f32(const bf_model* model, const bf_ukf_params* uparams, const b
   bf::CallOptionScope call_option_scope;
   if (!model || !uparams || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
   if (B <= 0 || T <= 0 || K <= 0) return bf::set_error(BF_EINVAL, "B, T and K must be positive");
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
-    return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
-  if (!y->ptr) return bf::set_error(BF_EINVAL, "observations pointer is NULL");
-  if (!carry->m_in || !carry->P_in) return bf::set_error(BF_EINVAL, "carry.m_in and carry.P_in are required");
-  if (!(uparams->alpha > 0.f)) return bf::set_error(BF_EINVAL, "ParamsUKF.alpha must be positive");
+  if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_streams(y, carry)) || (rc = bf::check_alpha(uparams))) return rc;
   return bf::launch_ugsf_ukf(model, uparams, y, u, B, T, K, carry, out, static_cast<hipStream_t>(stream));
 }
 
@@ -348,12 +303,8 @@ int bf_agsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream
   if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive");
   if (num_components[0] <= 0 || num_components[1] <= 0 || num_components[2] <= 0)
     return bf::set_error(BF_EINVAL, "num_components must be three positive counts");
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
-    return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
-  if (model->Q_steps < 1 || model->R_steps < 1) return bf::set_error(BF_EINVAL, "Q_steps / R_steps must be >= 1");
-  if (!y->ptr) return bf::set_error(BF_EINVAL, "observations pointer is NULL");
-  if (!carry->m_in || !carry->P_in) return bf::set_error(BF_EINVAL, "carry.m_in and carry.P_in are required");
+  if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_noise_steps(model->Q_steps, model->R_steps)) || (rc = bf::check_streams(y, carry)))
+    return rc;
   return bf::launch_agsf_ekf(model, y, u, B, T, num_components, key, opt_args, carry, out, leaf_idx, variant,
                              static_cast<hipStream_t>(stream));
 }
@@ -367,12 +318,7 @@ int bf_agsf_ukf_f32(const bf_model* model, const bf_ukf_params* uparams, const b
   if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive");
   if (num_components[0] <= 0 || num_components[1] <= 0 || num_components[2] <= 0)
     return bf::set_error(BF_EINVAL, "num_components must be three positive counts");
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0)
-    return bf::set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->Q || !model->R) return bf::set_error(BF_EINVAL, "Q and R are required");
-  if (!y->ptr) return bf::set_error(BF_EINVAL, "observations pointer is NULL");
-  if (!carry->m_in || !carry->P_in) return bf::set_error(BF_EINVAL, "carry.m_in and carry.P_in are required");
-  if (!(uparams->alpha > 0.f)) return bf::set_error(BF_EINVAL, "ParamsUKF.alpha must be positive");
+  if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_streams(y, carry)) || (rc = bf::check_alpha(uparams))) return rc;
   return bf::launch_agsf_ukf(model, uparams, y, u, B, T, num_components, key, opt_args, carry, out, leaf_idx, variant,
                              static_cast<hipStream_t>(stream));
 }

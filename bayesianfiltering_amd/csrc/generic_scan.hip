@@ -21,7 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "bf_common.hpp"
+#include "forward_host.hpp"
 #include "kf_math.hpp"
 #include "lgssm_pack.hpp"
 #include "scan_common.hpp"
@@ -210,11 +210,8 @@ int launch_gsf_generic(const bf_model* p, const bf_cstream* y, const bf_cstream*
     // (m_out / P_out may alias m_in / P_in: the kernel reads the inputs at t = 0 only, component by component,
     // before it writes that component's slot)
   }
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  UViewG uv{u && u->ptr ? u->ptr : nullptr, u ? u->sB : 0, u ? u->sT : 0};
-  CarryView cv{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
-  OutViews ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs),
-              make_sview(out->pred_means), make_sview(out->pred_covs), make_sview(out->loglik)};
+  auto [yv, cv, ov] = forward_views(y, carry, out);
+  UViewG uv = input_view<UViewG>(u);
   hipError_t le;
   if (p->user) {  // the run-time build of the same kernel with the caller's functions compiled in (user_model.hip)
     int kp = KP;

@@ -32,7 +32,7 @@
 #pragma once
 #include <cstring>
 #include <vector>
-#include "bf_common.hpp"
+#include "forward_host.hpp"
 #include "kf_math.hpp"
 #include "lane_group.hpp"
 #include "lgssm_pack.hpp"
@@ -714,12 +714,8 @@ static inline int launch_gsf(const bf_model* p, const bf_cstream* y, const bf_cs
   const int KP = next_pow2_i(K);
   if (KP * NL > 256)
     return set_error(BF_EUNSUPPORTED, "gaussian-sum filter: %d components x %d lanes exceed one workgroup (256 lanes)", K, NL);
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  UView uv{u && u->ptr ? u->ptr : nullptr, u ? u->sB : 0, u ? u->sT : 0};
-  CarryView cv{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
-  OutViews ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs),
-              make_sview(out->pred_means), make_sview(out->pred_covs), make_sview(out->loglik),
-              make_sview(out->coll_mean), make_sview(out->coll_cov)};
+  auto [yv, cv, ov] = forward_views(y, carry, out);
+  UView uv = input_view<UView>(u);
   const bool ref_layout = gsf_stream_is_reference(out->weights, 1, T, K) && gsf_stream_is_reference(out->loglik, 1, T, K) &&
                           gsf_stream_is_reference(out->means, N, T, K) && gsf_stream_is_reference(out->pred_means, N, T, K) &&
                           gsf_stream_is_reference(out->covs, N * N, T, K) && gsf_stream_is_reference(out->pred_covs, N * N, T, K);

@@ -4,7 +4,7 @@
 // Register instances (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): every instance n = 1 ... 6, m = 1 ... 4 of the
 // three kernels builds without scratch; at n = 7 the scan kernel spills 860 bytes per lane (n = 8: fold 436, scan 1628), so
 // the limit is n = 6.  Table per instance: DESIGN.md, section 6h.
-#include "bf_common.hpp"
+#include "forward_host.hpp"
 
 namespace bf {
 
@@ -53,7 +53,7 @@ static int resolve_block(long long B, long long T, int block) {
 }
 
 static int check_dims(int n, int m) {
-  if (n <= 0 || m <= 0) return set_error(BF_EINVAL, "non-positive model dimension");
+  if (const int rc = check_dimensions(n, 1, m, 1)) return rc;
   if (n > PSCAN_N_MAX || m > PSCAN_M_MAX)
     return set_error(BF_EUNSUPPORTED,
                      "parallel kalman filter: (n=%d, m=%d) is not compiled in (register kernels for n = 1..%d, m = 1..%d; the scan needs scratch from n = %d)", n, m,
@@ -78,20 +78,14 @@ int launch_kf_pscan(const bf_lgssm* model, const bf_cstream* y, long long B, lon
                     const bf_out_desc* out, void* workspace, long long workspace_bytes, hipStream_t stream) {
   if (!model || !y || !carry || !out || !workspace) return set_error(BF_EINVAL, "NULL argument");
   if (B <= 0 || T <= 0) return set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", B, T);
-  if (model->n <= 0 || model->m <= 0 || model->dq <= 0 || model->dr <= 0) return set_error(BF_EINVAL, "non-positive model dimension");
-  if (!model->A || !model->H || !model->Q || !model->R) return set_error(BF_EINVAL, "A, H, Q, R are required");
-  if (!model->G && model->dq != model->n) return set_error(BF_EINVAL, "G == NULL requires dq == n");
-  if (!model->D && model->dr != model->m) return set_error(BF_EINVAL, "D == NULL requires dr == m");
-  if (model->Q_steps < 1 || model->R_steps < 1) return set_error(BF_EINVAL, "Q_steps / R_steps must be >= 1");
+  int rc = check_lgssm(model);
+  if (rc != BF_OK) return rc;
   if (model->Q_steps > 1 || model->R_steps > 1)
     return set_error(BF_EUNSUPPORTED, "parallel kalman filter: constant Q and R only (Q_steps=%d, R_steps=%d)", model->Q_steps,
                      model->R_steps);
   if (out->coll_mean.ptr || out->coll_cov.ptr)
     return set_error(BF_EUNSUPPORTED, "parallel kalman filter: collapsed streams are not produced (with one component they equal means / covs)");
-  const int rc = check_dims(model->n, model->m);
-  if (rc != BF_OK) return rc;
-  if (!y->ptr) return set_error(BF_EINVAL, "observations pointer is NULL");
-  if (!carry->m_in || !carry->P_in) return set_error(BF_EINVAL, "carry.m_in and carry.P_in are required");
+  if ((rc = check_dims(model->n, model->m)) != BF_OK || (rc = check_streams(y, carry)) != BF_OK) return rc;
   const int L = resolve_block(B, T, 0);
   if (L < 0) return L;
   const long long need = kf_pscan_workspace_bytes(model->n, model->m, B, T, L);

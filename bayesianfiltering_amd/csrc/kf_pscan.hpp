@@ -520,10 +520,7 @@ static inline int launch_pscan_nm(const bf_lgssm* p, const bf_cstream* y, long l
   PsConst<N, M> c;
   if (!ps_fill_const<N, M>(p, c))
     return set_error(BF_EUNSUPPORTED, "parallel kalman filter: S = H G Q G^T H^T + D R D^T is singular, the step element does not exist");
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  CarryView cv{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
-  OutViews ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs),
-              make_sview(out->pred_means), make_sview(out->pred_covs), make_sview(out->loglik)};
+  auto [yv, cv, ov] = forward_views(y, carry, out);
   const long long NB = (T + L - 1) / L;
   const long long lanes = B * NB;
   float* agg = workspace;

@@ -7,7 +7,7 @@
 // order), no wave ever waits for another's factorization, and the CU holds eight independent trajectories (16.6 KB of LDS
 // each, two per workgroup) instead of two workgroups with three of four waves idle through the serial phase.
 // Smaller models ride zero-padded in the tile exactly as in launch_kf_mfma.
-#include "bf_common.hpp"
+#include "forward_host.hpp"
 #include "lgssm_pack.hpp"
 #include "mfma_multi.hpp"
 #include "mfma_tiles.hpp"
@@ -281,10 +281,7 @@ int launch_kf_bf32(const bf_lgssm* p, const bf_cstream* y, long long B, long lon
   if (crc != BF_OK) return crc;
   const Bf32Const* dc = static_cast<const Bf32Const*>(dv);
 
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  CarryView cv{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
-  OutViews ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs),
-              make_sview(out->pred_means), make_sview(out->pred_covs), make_sview(out->loglik)};
+  auto [yv, cv, ov] = forward_views(y, carry, out);
   // per-step tables (_get_params(x, 2, t), inference.py:21): T blocks of 32 x 32, formed on the device; MULTI: somewhere for
   // the log-likelihoods
   float *d_tvq = nullptr, *d_tvr = nullptr, *llscratch = nullptr;

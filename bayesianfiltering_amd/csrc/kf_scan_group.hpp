@@ -31,7 +31,7 @@
 #pragma once
 #include <cstdlib>
 #include <vector>
-#include "bf_common.hpp"
+#include "forward_host.hpp"
 #include "kf_math.hpp"
 #include "lane_group.hpp"
 #include "lgssm_pack.hpp"
@@ -430,10 +430,10 @@ static inline int launch_nml(const bf_lgssm* p, const bf_cstream* y, long long B
   using Cfg = GroupCfg<N, M, NL>;
   KFConst<N, M> c;
   fill_const<N, M>(p, c, p->Q, p->R);
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  CarryView cv{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
-  OutViews ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs),
-              make_sview(out->pred_means), make_sview(out->pred_covs), make_sview(out->loglik)};
+  const ForwardViews fv = forward_views(y, carry, out);
+  const CView& yv = fv.y;
+  const CarryView& cv = fv.carry;
+  const OutViews& ov = fv.out;
 
   const bool ref_layout = stream_is_reference(out->weights, 1, T) && stream_is_reference(out->loglik, 1, T) &&
                           stream_is_reference(out->means, N, T) && stream_is_reference(out->pred_means, N, T) &&

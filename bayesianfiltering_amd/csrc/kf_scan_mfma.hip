@@ -31,7 +31,7 @@
 // uses the Cholesky factor of the un-jittered S exactly like the reference (inference.py:104, :24).
 // The kernels this one superseded, and what was measured on them: DESIGN.md, "Retired matrix-core variants".
 #include <cstdlib>
-#include "bf_common.hpp"
+#include "forward_host.hpp"
 #include "lgssm_pack.hpp"
 #include "mfma_multi.hpp"
 #include "mfma_tiles.hpp"
@@ -386,10 +386,7 @@ int launch_kf_mfma(const bf_lgssm* p, const bf_cstream* y, long long B, long lon
   if (crc != BF_OK) return crc;
   const MfmaConst<N, M>* d = static_cast<const MfmaConst<N, M>*>(dv);
 
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  CarryView cv{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
-  OutViews ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs),
-              make_sview(out->pred_means), make_sview(out->pred_covs), make_sview(out->loglik)};
+  auto [yv, cv, ov] = forward_views(y, carry, out);
   // per-step tables (_get_params(x, 2, t), inference.py:21), formed on the device; MULTI: somewhere for the log-likelihoods
   float *d_tvq = nullptr, *d_tvr = nullptr, *llscratch = nullptr;
   auto free_tables = [&]() {

@@ -40,6 +40,7 @@
 // for sine dynamics + a dense linear emission at n = 12, m = 6)
 #include <cstdlib>
 #include <vector>
+#include "forward_host.hpp"
 #include "ugsf_scan.hpp"
 #include "ugsf_generic_device.hpp"
 #include "user_model.hpp"
@@ -139,11 +140,8 @@ int launch_ugsf_generic(const bf_model* p, const bf_ukf_params* up, const bf_cst
       if (!gP) gP = scratch + (size_t)B * K * n;
     }
   }
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  UViewG uv{u && u->ptr ? u->ptr : nullptr, u ? u->sB : 0, u ? u->sT : 0};
-  CarryView cr{carry->w_in, carry->m_in, carry->P_in, carry->w_out, carry->m_out, carry->P_out};
-  OutViews ov{make_sview(out->weights), make_sview(out->means), make_sview(out->covs),
-              make_sview(out->pred_means), make_sview(out->pred_covs), make_sview(out->loglik)};
+  auto [yv, cr, ov] = forward_views(y, carry, out);
+  UViewG uv = input_view<UViewG>(u);
   int dmax = n > dq ? n : dq;
   dmax = dmax > m ? dmax : m;
   dmax = dmax > dr ? dmax : dr;

@@ -152,69 +152,84 @@ class FilterCarry(NamedTuple):
     covariances: Any
 
 
-class _KalmanCall:
-    """The arguments of a Kalman entry point of the C-ABI (bf_kalman_filter_f32, bf_kalman_filter_pscan_f32) built from the
-    keyword set of :func:`kalman_filter`: model, observations, carry and output descriptors, with the tensors they point to."""
-
-    def result(self):
-        sq = self.squeeze
-        post = PosteriorGaussianSumFiltered(**{k: (v[0] if (sq and v is not None) else v) for k, v in self.bufs.items()})
-        extras = []
-        if self.ll is not None:
-            extras.append(self.ll[0] if sq else self.ll)
-        if self.c_out is not None:
-            extras.append(self.c_out)
-        return (post, *extras) if extras else post
+def _ukf_params(uparams, extended=False):
+    """``uparams`` (a :class:`ParamsUKF` or a 3-tuple) as the C struct; it excludes ``extended=True``."""
+    if extended:
+        raise ValueError("uparams selects the unscented route; it cannot be combined with extended=True")
+    if not isinstance(uparams, ParamsUKF):
+        uparams = ParamsUKF(*uparams)
+    return _lib.bf_ukf_params(float(uparams.alpha), float(uparams.beta), float(uparams.kappa))
 
 
-def _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
-                 return_carry, device):
-    torch = _torch()
-    mdl = _Lgssm(params)
-    n, m = mdl.n, mdl.m
+def _emissions_desc(emissions, m, device):
+    """``emissions`` (T, m) or (B, T, m) on ``device`` -> (y (B, T, m), its bf_cstream, whether it was unbatched, B, T).
+    Empty emissions pass: the callers that refuse them in Python do so themselves."""
     y = _dev_f32(emissions, device)
     squeeze = y.dim() == 2
     if squeeze:
         y = y.unsqueeze(0)
     if y.dim() != 3 or y.shape[2] != m:
         raise ValueError(f"emissions must be (T,{m}) or (B,T,{m}); got {tuple(y.shape)}")
-    B, T = int(y.shape[0]), int(y.shape[1])
-    if T == 0 or B == 0:
-        raise ValueError("empty emissions")
+    yd = _lib.bf_cstream()
+    yd.ptr, yd.sB, yd.sK, yd.sT, yd.sE = y.data_ptr(), y.stride(0), 0, y.stride(1), y.stride(2)
+    return y, yd, squeeze, int(y.shape[0]), int(y.shape[1])
 
-    # carry in
+
+def _inputs_desc(inputs, B, T, dev, keep):
+    """bf_cstream of the filter's inputs ((T,), (T, d) or (B, T, d); None = zeros); the tensor it points into joins ``keep``."""
+    ud = _lib.bf_cstream()
+    if inputs is not None:
+        u = _dev_f32(inputs, dev)
+        if u.dim() == 1:
+            u = u.reshape(1, T, 1)
+        elif u.dim() == 2:
+            u = u.reshape(1, T, -1)
+        if u.shape[1] != T or u.shape[0] not in (1, B):
+            raise ValueError(f"inputs must be (T,), (T,d) or (B,T,d); got {tuple(u.shape)}")
+        keep.append(u)
+        ud.ptr, ud.sB, ud.sT, ud.sE = u.data_ptr(), (u.stride(0) if u.shape[0] == B else 0), u.stride(1), 1
+    return ud
+
+
+def _carry_in(carry, initial_means, initial_covariances, B, K, n, label, device, reshape_weights=False):
+    """The scan's initial (weights or None, means (B, K, n), covariances (B, K, n, n)), contiguous on ``device``: a
+    :class:`FilterCarry`, or initial means (K, n) / (B, K, n) and covariances (n, n) / (K, n, n) / (B, K, n, n) expanded
+    over the batch.  ``label`` names K in the shape error ("1", "K", "N0")."""
     if carry is not None:
         w_in, m_in, P_in = (_dev_f32(v, device).contiguous() for v in carry)
-        w_in = w_in.reshape(B, 1)
+        if reshape_weights:
+            w_in = w_in.reshape(B, K)
     else:
         w_in = None
-        if initial_means is None:
-            m_in = _dev_f32(_host_f32(params.initial_mean), device).reshape(1, 1, n).expand(B, 1, n).contiguous()
+        m_in = _dev_f32(initial_means, device).reshape(-1, K, n)
+        m_in = m_in.expand(B, K, n).contiguous() if m_in.shape[0] == 1 else m_in.contiguous()
+        P_in = _dev_f32(initial_covariances, device)
+        if P_in.dim() == 2:
+            P_in = P_in.reshape(1, 1, n, n).expand(B, K, n, n).contiguous()
         else:
-            m_in = _dev_f32(initial_means, device).reshape(-1, 1, n)
-            m_in = m_in.expand(B, 1, n).contiguous() if m_in.shape[0] == 1 else m_in.contiguous()
-        P0 = params.initial_covariance if initial_covariances is None else initial_covariances
-        P_in = _dev_f32(P0, device).reshape(-1, 1, n, n)
-        P_in = P_in.expand(B, 1, n, n).contiguous() if P_in.shape[0] == 1 else P_in.contiguous()
-    if m_in.shape != (B, 1, n) or P_in.shape != (B, 1, n, n):
-        raise ValueError("initial means / covariances do not match (B, 1, n) / (B, 1, n, n)")
+            P_in = P_in.reshape(-1, K, n, n)
+            P_in = P_in.expand(B, K, n, n).contiguous() if P_in.shape[0] == 1 else P_in.contiguous()
+    if tuple(m_in.shape) != (B, K, n) or tuple(P_in.shape) != (B, K, n, n):
+        raise ValueError(f"initial means / covariances do not match (B, {label}, n) / (B, {label}, n, n)")
+    return w_in, m_in, P_in
 
+
+def _alloc_outputs(B, K, T, n, fields, layout, out, return_loglik, device):
     ev = {"weights": (), "means": (n,), "covariances": (n, n), "predicted_means": (n,), "predicted_covariances": (n, n)}
     bufs = {}
     for name in FULL5:
         if name in fields:
             reuse = getattr(out, name, None) if out is not None else None
             if reuse is not None:
-                _check_out_tensor(name, reuse, y.device)
-                if tuple(reuse.shape) != (B, 1, T) + ev[name]:
-                    raise ValueError(f"out.{name} has shape {tuple(reuse.shape)}")
+                _check_out_tensor(name, reuse, device)
+                if tuple(reuse.shape) != (B, K, T) + ev[name]:
+                    raise ValueError(f"out.{name} has shape {tuple(reuse.shape)}, expected {(B, K, T) + ev[name]}")
                 bufs[name] = reuse
             else:
-                bufs[name] = _alloc_stream((B, 1, T), ev[name], layout, y.device)
+                bufs[name] = _alloc_stream((B, K, T), ev[name], layout, device)
         else:
             bufs[name] = None
-    ll = _alloc_stream((B, 1, T), (), layout, y.device) if return_loglik else None
-
+    ll = _alloc_stream((B, K, T), (), layout, device) if return_loglik else None
     od = _lib.bf_out_desc()
     od.weights = _stream_desc(bufs["weights"], 0)
     od.means = _stream_desc(bufs["means"], 1)
@@ -222,27 +237,80 @@ def _kalman_call(params, emissions, initial_means, initial_covariances, carry, f
     od.pred_means = _stream_desc(bufs["predicted_means"], 1)
     od.pred_covs = _stream_desc(bufs["predicted_covariances"], 2)
     od.loglik = _stream_desc(ll, 0)
+    return bufs, ll, od
 
-    yd = _lib.bf_cstream()
-    yd.ptr, yd.sB, yd.sK, yd.sT, yd.sE = y.data_ptr(), y.stride(0), 0, y.stride(1), y.stride(2)
 
+def _carry_desc(carry_in, B, K, n, return_carry, device):
+    """bf_carry over the initial state of :func:`_carry_in` and, with ``return_carry``, a fresh :class:`FilterCarry` to end in."""
+    torch = _torch()
+    w_in, m_in, P_in = carry_in
     cr = _lib.bf_carry()
     cr.w_in = w_in.data_ptr() if w_in is not None else None
     cr.m_in, cr.P_in = m_in.data_ptr(), P_in.data_ptr()
     c_out = None
     if return_carry:
-        c_out = FilterCarry(torch.empty((B, 1), dtype=torch.float32, device=y.device),
-                            torch.empty((B, 1, n), dtype=torch.float32, device=y.device),
-                            torch.empty((B, 1, n, n), dtype=torch.float32, device=y.device))
+        c_out = FilterCarry(torch.empty((B, K), dtype=torch.float32, device=device),
+                            torch.empty((B, K, n), dtype=torch.float32, device=device),
+                            torch.empty((B, K, n, n), dtype=torch.float32, device=device))
         cr.w_out, cr.m_out, cr.P_out = (t.data_ptr() for t in c_out)
+    return cr, c_out
 
-    k = _KalmanCall()
-    k.mdl, k.y, k.B, k.T, k.squeeze = mdl, y, B, T, squeeze
-    k.carry_in = (w_in, m_in, P_in)      # (kept alive: cr points into them)
-    k.bufs, k.ll, k.c_out = bufs, ll, c_out
-    k.od, k.yd, k.cr = od, yd, cr
-    k.stream = torch.cuda.current_stream(y.device).cuda_stream
+
+class _FilterCall:
+    """What a five-stream entry point of the C-ABI takes (bf_kalman_filter_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32,
+    bf_ugsf_ukf_f32, bf_agsf_*_f32): the model ``mdl``, the descriptors of the observations ``yd``, the inputs ``ud``, the
+    carry ``cr`` and the outputs ``od``, the sizes, and the tensors those descriptors point into, which live as long as this
+    object.  Built by :func:`_filter_call` without touching the GPU; the stream is read when the call is made."""
+
+    @property
+    def stream(self):
+        return _torch().cuda.current_stream(self.y.device).cuda_stream
+
+    def unwrap(self, v):
+        """``v`` as the caller sees it: without the batch axis when the emissions had none."""
+        return v[0] if (self.squeeze and v is not None) else v
+
+    def result(self, *more, aux=None):
+        """The posterior; as ``(post, aux)`` when ``aux`` is given (the augmented filters), else followed by the
+        log-likelihood stream and the carry-out the call asked for and by ``more``, or alone when there is none."""
+        post = PosteriorGaussianSumFiltered(**{k: self.unwrap(v) for k, v in self.bufs.items()})
+        if aux is not None:
+            return post, aux
+        extras = [self.unwrap(self.ll)] if self.ll is not None else []
+        if self.c_out is not None:
+            extras.append(self.c_out)
+        extras += more
+        return (post, *extras) if extras else post
+
+
+def _filter_call(mdl, emissions, K, label, initial_means, initial_covariances, carry=None, inputs=None, fields=FULL5,
+                 layout="reference", out=None, return_loglik=False, return_carry=False, device="cuda", reshape_weights=False):
+    """The front half of a five-stream filter: everything its C call takes, as a :class:`_FilterCall`.  ``mdl``: a
+    :class:`_Lgssm` or :class:`_Model`; ``K``: the number of components, named ``label`` in the carry's shape error;
+    ``initial_means``: the caller's, or a function returning the family's default (called only when no carry is given)."""
+    k = _FilterCall()
+    k.mdl, k.K, n = mdl, K, mdl.n
+    k.y, k.yd, k.squeeze, B, T = _emissions_desc(emissions, mdl.m, device)
+    k.B, k.T = B, T
+    if T == 0 or B == 0:
+        raise ValueError("empty emissions")
+    if carry is None and callable(initial_means):
+        initial_means = initial_means()
+    k.carry_in = _carry_in(carry, initial_means, initial_covariances, B, K, n, label, device, reshape_weights)
+    k.bufs, k.ll, k.od = _alloc_outputs(B, K, T, n, fields, layout, out, return_loglik, k.y.device)
+    k.keep = []
+    k.ud = _inputs_desc(inputs, B, T, device, k.keep)
+    k.cr, k.c_out = _carry_desc(k.carry_in, B, K, n, return_carry, k.y.device)
     return k
+
+
+def _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
+                 return_carry, device):
+    """:func:`_filter_call` for the keyword set of :func:`kalman_filter`: one component that starts at ``params.initial_mean``."""
+    return _filter_call(_Lgssm(params), emissions, 1, "1",
+                        (lambda: _host_f32(params.initial_mean)) if initial_means is None else initial_means,
+                        params.initial_covariance if initial_covariances is None else initial_covariances, carry, None, fields,
+                        layout, out, return_loglik, return_carry, device, reshape_weights=True)
 
 
 def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
@@ -350,32 +418,6 @@ def sample_initial_component_means(params, num_components, key=None):
     return (m0[None, :] + z @ L.T).astype(F32)
 
 
-def _alloc_outputs(B, K, T, n, fields, layout, out, return_loglik, device):
-    ev = {"weights": (), "means": (n,), "covariances": (n, n), "predicted_means": (n,), "predicted_covariances": (n, n)}
-    bufs = {}
-    for name in FULL5:
-        if name in fields:
-            reuse = getattr(out, name, None) if out is not None else None
-            if reuse is not None:
-                _check_out_tensor(name, reuse, device)
-                if tuple(reuse.shape) != (B, K, T) + ev[name]:
-                    raise ValueError(f"out.{name} has shape {tuple(reuse.shape)}, expected {(B, K, T) + ev[name]}")
-                bufs[name] = reuse
-            else:
-                bufs[name] = _alloc_stream((B, K, T), ev[name], layout, device)
-        else:
-            bufs[name] = None
-    ll = _alloc_stream((B, K, T), (), layout, device) if return_loglik else None
-    od = _lib.bf_out_desc()
-    od.weights = _stream_desc(bufs["weights"], 0)
-    od.means = _stream_desc(bufs["means"], 1)
-    od.covs = _stream_desc(bufs["covariances"], 2)
-    od.pred_means = _stream_desc(bufs["predicted_means"], 1)
-    od.pred_covs = _stream_desc(bufs["predicted_covariances"], 2)
-    od.loglik = _stream_desc(ll, 0)
-    return bufs, ll, od
-
-
 def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: int = 1, inputs=None, *,
                         initial_means=None, initial_covariances=None, carry=None,
                         fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
@@ -400,86 +442,24 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
     K = int(num_components)
     if K < 1:
         raise ValueError("num_components must be >= 1")
-    mdl = _Model(params)
-    n, m = mdl.n, mdl.m
-    y = _dev_f32(emissions, device)
-    squeeze = y.dim() == 2
-    if squeeze:
-        y = y.unsqueeze(0)
-    if y.dim() != 3 or y.shape[2] != m:
-        raise ValueError(f"emissions must be (T,{m}) or (B,T,{m}); got {tuple(y.shape)}")
-    B, T = int(y.shape[0]), int(y.shape[1])
-    if T == 0 or B == 0:
-        raise ValueError("empty emissions")
-
-    if carry is not None:
-        w_in, m_in, P_in = (_dev_f32(v, device).contiguous() for v in carry)
-    else:
-        w_in = None
-        im = sample_initial_component_means(params, K) if initial_means is None else initial_means
-        m_in = _dev_f32(im, device).reshape(-1, K, n)
-        m_in = m_in.expand(B, K, n).contiguous() if m_in.shape[0] == 1 else m_in.contiguous()
-        P0 = params.initial_covariance if initial_covariances is None else initial_covariances
-        P_in = _dev_f32(P0, device)
-        if P_in.dim() == 2:
-            P_in = P_in.reshape(1, 1, n, n).expand(B, K, n, n).contiguous()
-        else:
-            P_in = P_in.reshape(-1, K, n, n)
-            P_in = P_in.expand(B, K, n, n).contiguous() if P_in.shape[0] == 1 else P_in.contiguous()
-    if tuple(m_in.shape) != (B, K, n) or tuple(P_in.shape) != (B, K, n, n):
-        raise ValueError("initial means / covariances do not match (B, K, n) / (B, K, n, n)")
-
-    bufs, ll, od = _alloc_outputs(B, K, T, n, fields, layout, out, return_loglik, y.device)
-    coll = None
+    k = _filter_call(_Model(params), emissions, K, "K",
+                     (lambda: sample_initial_component_means(params, K)) if initial_means is None else initial_means,
+                     params.initial_covariance if initial_covariances is None else initial_covariances, carry, inputs, fields,
+                     layout, out, return_loglik, return_carry, device)
+    B, T, n, od = k.B, k.T, k.mdl.n, k.od
+    coll = ()
     if return_collapsed:
-        coll = (torch.empty((B, T, n), dtype=torch.float32, device=y.device),
-                torch.empty((B, T, n, n), dtype=torch.float32, device=y.device))
+        coll = (torch.empty((B, T, n), dtype=torch.float32, device=k.y.device),
+                torch.empty((B, T, n, n), dtype=torch.float32, device=k.y.device))
         od.coll_mean.ptr, od.coll_mean.sB, od.coll_mean.sK, od.coll_mean.sT, od.coll_mean.sE = coll[0].data_ptr(), T * n, 0, n, 1
         od.coll_cov.ptr, od.coll_cov.sB, od.coll_cov.sK, od.coll_cov.sT, od.coll_cov.sE = coll[1].data_ptr(), T * n * n, 0, n * n, 1
-
-    yd = _lib.bf_cstream()
-    yd.ptr, yd.sB, yd.sK, yd.sT, yd.sE = y.data_ptr(), y.stride(0), 0, y.stride(1), y.stride(2)
-    ud = _lib.bf_cstream()
-    u_keep = None
-    if inputs is not None:
-        u_keep = _dev_f32(inputs, device)
-        if u_keep.dim() == 1:
-            u_keep = u_keep.reshape(1, T, 1)
-        elif u_keep.dim() == 2:
-            u_keep = u_keep.reshape(1, T, -1)
-        if u_keep.shape[1] != T or u_keep.shape[0] not in (1, B):
-            raise ValueError(f"inputs must be (T,), (T,d) or (B,T,d); got {tuple(u_keep.shape)}")
-        ud.ptr, ud.sB, ud.sT, ud.sE = u_keep.data_ptr(), (u_keep.stride(0) if u_keep.shape[0] == B else 0), u_keep.stride(1), 1
-
-    cr = _lib.bf_carry()
-    cr.w_in = w_in.data_ptr() if w_in is not None else None
-    cr.m_in, cr.P_in = m_in.data_ptr(), P_in.data_ptr()
-    c_out = None
-    if return_carry:
-        c_out = FilterCarry(torch.empty((B, K), dtype=torch.float32, device=y.device),
-                            torch.empty((B, K, n), dtype=torch.float32, device=y.device),
-                            torch.empty((B, K, n, n), dtype=torch.float32, device=y.device))
-        cr.w_out, cr.m_out, cr.P_out = (t.data_ptr() for t in c_out)
-
-    stream = torch.cuda.current_stream(y.device).cuda_stream
+        coll = (tuple(k.unwrap(v) for v in coll),)
+    # (_uparams: the unscented bank -- same carry / streams, sigma-point moment matching instead of Jacobians)
+    fn, head = (lib.bf_gsf_ekf_f32, ()) if _uparams is None else (lib.bf_ugsf_ukf_f32, (C.byref(_uparams),))
     _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
-    if _uparams is None:
-        _lib.check(lib.bf_gsf_ekf_f32(C.byref(mdl.c), C.byref(yd), C.byref(ud), B, T, K, C.byref(cr), C.byref(od),
-                                      C.c_void_p(stream)))
-    else:  # the unscented bank: same carry / streams, sigma-point moment matching instead of Jacobians
-        up = _lib.bf_ukf_params(float(_uparams.alpha), float(_uparams.beta), float(_uparams.kappa))
-        _lib.check(lib.bf_ugsf_ukf_f32(C.byref(mdl.c), C.byref(up), C.byref(yd), C.byref(ud), B, T, K, C.byref(cr),
-                                       C.byref(od), C.c_void_p(stream)))
-
-    post = PosteriorGaussianSumFiltered(**{k: (v[0] if (squeeze and v is not None) else v) for k, v in bufs.items()})
-    extras = []
-    if return_loglik:
-        extras.append(ll[0] if squeeze else ll)
-    if return_carry:
-        extras.append(c_out)
-    if return_collapsed:
-        extras.append(tuple(v[0] for v in coll) if squeeze else coll)
-    return (post, *extras) if extras else post
+    _lib.check(fn(C.byref(k.mdl.c), *head, C.byref(k.yd), C.byref(k.ud), B, T, K, C.byref(k.cr), C.byref(od),
+                  C.c_void_p(k.stream)))
+    return k.result(*coll)
 
 
 def unscented_gaussian_sum_filter(params, uparams, emissions, num_components: int = 1, num_iter: int = 1, inputs=None, *,
@@ -498,12 +478,10 @@ def unscented_gaussian_sum_filter(params, uparams, emissions, num_components: in
     runs on the run-time-dimension kernel (state in LDS, any number of components, bounded by 160 KiB of LDS: about n = 70 with
     n / 2 observations).  ``options={"ugsf_force_generic": 1}`` sends a small model through that kernel too.
     """
-    if not isinstance(uparams, ParamsUKF):
-        uparams = ParamsUKF(*uparams)
     return gaussian_sum_filter(params, emissions, num_components, num_iter, inputs, initial_means=initial_means,
                                initial_covariances=initial_covariances, carry=carry, fields=fields, layout=layout, out=out,
                                return_loglik=return_loglik, return_carry=return_carry, device=device, options=options,
-                               _uparams=uparams)
+                               _uparams=_ukf_params(uparams))
 
 
 def speedy_augmented_gaussian_sum_filter(params, emissions, num_components, rng_key=None, num_iter: int = 1,
@@ -536,78 +514,24 @@ def speedy_augmented_gaussian_sum_filter(params, emissions, num_components, rng_
     if nc.size != 3 or np.any(nc < 1):
         raise ValueError("num_components must hold three positive counts (N0, N1, N2)")
     N0 = int(nc[0])
-    mdl = _Model(params)
-    n, m = mdl.n, mdl.m
-    y = _dev_f32(emissions, device)
-    squeeze = y.dim() == 2
-    if squeeze:
-        y = y.unsqueeze(0)
-    if y.dim() != 3 or y.shape[2] != m:
-        raise ValueError(f"emissions must be (T,{m}) or (B,T,{m}); got {tuple(y.shape)}")
-    B, T = int(y.shape[0]), int(y.shape[1])
-    if T == 0 or B == 0:
-        raise ValueError("empty emissions")
-    if carry is not None:
-        w_in, m_in, P_in = (_dev_f32(v, device).contiguous() for v in carry)
-    else:
-        w_in = None
-        im = sample_initial_component_means(params, N0) if initial_means is None else initial_means
-        m_in = _dev_f32(im, device).reshape(-1, N0, n)
-        m_in = m_in.expand(B, N0, n).contiguous() if m_in.shape[0] == 1 else m_in.contiguous()
-        P0 = params.initial_covariance if initial_covariances is None else initial_covariances
-        P_in = _dev_f32(P0, device)
-        if P_in.dim() == 2:
-            P_in = P_in.reshape(1, 1, n, n).expand(B, N0, n, n).contiguous()
-        else:
-            P_in = P_in.reshape(-1, N0, n, n)
-            P_in = P_in.expand(B, N0, n, n).contiguous() if P_in.shape[0] == 1 else P_in.contiguous()
-    if tuple(m_in.shape) != (B, N0, n) or tuple(P_in.shape) != (B, N0, n, n):
-        raise ValueError("initial means / covariances do not match (B, N0, n) / (B, N0, n, n)")
-    bufs, _, od = _alloc_outputs(B, N0, T, n, ("weights", "means", "covariances"), "reference", None, False, y.device)
-    yd = _lib.bf_cstream()
-    yd.ptr, yd.sB, yd.sK, yd.sT, yd.sE = y.data_ptr(), y.stride(0), 0, y.stride(1), y.stride(2)
-    ud = _lib.bf_cstream()
-    u_keep = None
-    if inputs is not None:
-        u_keep = _dev_f32(inputs, device)
-        if u_keep.dim() == 1:
-            u_keep = u_keep.reshape(1, T, 1)
-        elif u_keep.dim() == 2:
-            u_keep = u_keep.reshape(1, T, -1)
-        if u_keep.shape[1] != T or u_keep.shape[0] not in (1, B):
-            raise ValueError(f"inputs must be (T,), (T,d) or (B,T,d); got {tuple(u_keep.shape)}")
-        ud.ptr, ud.sB, ud.sT, ud.sE = u_keep.data_ptr(), (u_keep.stride(0) if u_keep.shape[0] == B else 0), u_keep.stride(1), 1
-    cr = _lib.bf_carry()
-    cr.w_in = w_in.data_ptr() if w_in is not None else None
-    cr.m_in, cr.P_in = m_in.data_ptr(), P_in.data_ptr()
-    c_out = None
-    if return_carry:
-        c_out = FilterCarry(torch.empty((B, N0), dtype=torch.float32, device=y.device),
-                            torch.empty((B, N0, n), dtype=torch.float32, device=y.device),
-                            torch.empty((B, N0, n, n), dtype=torch.float32, device=y.device))
-        cr.w_out, cr.m_out, cr.P_out = (t.data_ptr() for t in c_out)
+    k = _filter_call(_Model(params), emissions, N0, "N0",
+                     (lambda: sample_initial_component_means(params, N0)) if initial_means is None else initial_means,
+                     params.initial_covariance if initial_covariances is None else initial_covariances, carry, inputs, FILTERED,
+                     return_carry=return_carry, device=device)
     key = np.ascontiguousarray(np.asarray(PRNGKey(0) if rng_key is None else rng_key, dtype=np.uint32).reshape(2))
     opt = np.ascontiguousarray(np.asarray(opt_args, dtype=F32).reshape(2))
-    leaf = torch.empty((B, T, N0), dtype=torch.int32, device=y.device) if return_leaf_indices else None
-    stream = torch.cuda.current_stream(y.device).cuda_stream
-    leaf_ptr = C.c_void_p(leaf.data_ptr() if leaf is not None else None)
+    leaf = torch.empty((k.B, k.T, N0), dtype=torch.int32, device=k.y.device) if return_leaf_indices else None
+    fn, head = (lib.bf_agsf_ekf_f32, ()) if _uparams is None else (lib.bf_agsf_ukf_f32, (C.byref(_uparams),))
     _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
-    if _uparams is None:
-        _lib.check(lib.bf_agsf_ekf_f32(C.byref(mdl.c), C.byref(yd), C.byref(ud), B, T, nc.ctypes.data_as(C.POINTER(C.c_int32)),
-                                       key.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(opt), C.byref(cr), C.byref(od),
-                                       leaf_ptr, int(_variant), C.c_void_p(stream)))
-    else:
-        up = _lib.bf_ukf_params(float(_uparams.alpha), float(_uparams.beta), float(_uparams.kappa))
-        _lib.check(lib.bf_agsf_ukf_f32(C.byref(mdl.c), C.byref(up), C.byref(yd), C.byref(ud), B, T,
-                                       nc.ctypes.data_as(C.POINTER(C.c_int32)), key.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                       _fp(opt), C.byref(cr), C.byref(od), leaf_ptr, int(_variant), C.c_void_p(stream)))
-    post = PosteriorGaussianSumFiltered(**{k: (v[0] if (squeeze and v is not None) else v) for k, v in bufs.items()})
+    _lib.check(fn(C.byref(k.mdl.c), *head, C.byref(k.yd), C.byref(k.ud), k.B, k.T, nc.ctypes.data_as(C.POINTER(C.c_int32)),
+                  key.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(opt), C.byref(k.cr), C.byref(k.od),
+                  C.c_void_p(leaf.data_ptr() if leaf is not None else None), int(_variant), C.c_void_p(k.stream)))
     aux = {}
     if return_leaf_indices:
-        aux["leaf_indices"] = leaf[0] if squeeze else leaf
+        aux["leaf_indices"] = k.unwrap(leaf)
     if return_carry:
-        aux["carry"] = c_out
-    return post, aux
+        aux["carry"] = k.c_out
+    return k.result(aux=aux)
 
 
 def augmented_gaussian_sum_filter(params, emissions, num_components, rng_key=None, num_iter: int = 1, opt_args=(0.1, 0.1),
@@ -627,20 +551,16 @@ def speedy_unscented_agsf(params, uparams, emissions, num_components, rng_key=No
     """Augmented Gaussian-sum filter with unscented nodes, gaussfiltax/inference.py:966-1156, on the HIP engine:
     :func:`speedy_augmented_gaussian_sum_filter` with ``_ukf_predict_nonadditive`` / ``_ukf_condition_on_nonadditive``
     at the tree nodes.  Same positional signature as the reference (``uparams``: :class:`ParamsUKF`)."""
-    if not isinstance(uparams, ParamsUKF):
-        uparams = ParamsUKF(*uparams)
     return speedy_augmented_gaussian_sum_filter(params, emissions, num_components, rng_key, num_iter, opt_args, inputs,
-                                                _uparams=uparams, **kwargs)
+                                                _uparams=_ukf_params(uparams), **kwargs)
 
 
 def unscented_agsf(params, uparams, emissions, num_components, rng_key=None, num_iter: int = 1, opt_args=(0.1, 0.1), inputs=None,
                    **kwargs):
     """gaussfiltax/inference.py:813-965: the unscented augmented filter with the container-based branches of
     :func:`augmented_gaussian_sum_filter`."""
-    if not isinstance(uparams, ParamsUKF):
-        uparams = ParamsUKF(*uparams)
     return speedy_augmented_gaussian_sum_filter(params, emissions, num_components, rng_key, num_iter, opt_args, inputs,
-                                                _variant=1, _uparams=uparams, **kwargs)
+                                                _variant=1, _uparams=_ukf_params(uparams), **kwargs)
 
 
 def augmented_gaussian_sum_filter_optimal(params, emissions, num_components, rng_key=None, num_iter: int = 1,
@@ -739,24 +659,10 @@ def bootstrap_particle_filter(params, emissions, num_particles: int, key=None, i
         rev = np.ascontiguousarray(lp.r_eval.reshape(mdl.dr))
     bm.m0, bm.P0, bm.lp_cov, bm.r_eval = _fp(m0), _fp(P0), _fp(lpc), _fp(rev)
 
-    y = _dev_f32(emissions, device)
-    squeeze = y.dim() == 2
-    if squeeze:
-        y = y.unsqueeze(0)
-    if y.dim() != 3 or y.shape[2] != m:
-        raise ValueError(f"emissions must be (T,{m}) or (B,T,{m}); got {tuple(y.shape)}")
-    B, T = int(y.shape[0]), int(y.shape[1])
+    y, yd, squeeze, B, T = _emissions_desc(emissions, m, device)   # (empty emissions: the C entry point refuses them)
     dev = y.device
-    yd = _lib.bf_cstream()
-    yd.ptr, yd.sB, yd.sK, yd.sT, yd.sE = y.data_ptr(), y.stride(0), 0, y.stride(1), y.stride(2)
-    ud = _lib.bf_cstream()
-    u_keep = None
-    if inputs is not None:
-        u_keep = _dev_f32(inputs, device)
-        u_keep = u_keep.reshape(1, T, -1) if u_keep.dim() <= 2 else u_keep
-        if u_keep.shape[1] != T or u_keep.shape[0] not in (1, B):
-            raise ValueError(f"inputs must be (T,), (T,d) or (B,T,d); got {tuple(u_keep.shape)}")
-        ud.ptr, ud.sB, ud.sT, ud.sE = u_keep.data_ptr(), (u_keep.stride(0) if u_keep.shape[0] == B else 0), u_keep.stride(1), 1
+    keep = []
+    ud = _inputs_desc(inputs, B, T, device, keep)
 
     key = PRNGKey(0) if key is None else np.asarray(key, dtype=np.uint32).reshape(2)
     key_c = (C.c_uint32 * 2)(int(key[0]), int(key[1]))
@@ -780,7 +686,6 @@ def bootstrap_particle_filter(params, emissions, num_particles: int, key=None, i
         od.mean, od.ess, od.logz, od.resampled = (res[k].data_ptr() for k in ("mean", "ess", "logz", "resampled"))
 
     cr = _lib.bf_bpf_carry()
-    keep = []
     if carry is not None:
         w_in = _dev_f32(carry.weights, device).reshape(B, NP).contiguous()
         x_in = _dev_f32(carry.particles, device).reshape(B, NP, n).contiguous()

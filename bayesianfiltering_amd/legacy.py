@@ -63,25 +63,15 @@ class SSM:
 
 def _run_gsf(ssm, ys, init_means, P0, flags, K):
     """bf_gsf_ekf_f32 with legacy flags; returns torch tensors (K,T,...) + loglik."""
-    import torch
     params = ssm._params(init_means[0], P0, with_bias=False)
     lib = _lib.require_gpu()
     mdl = _inf._Model(params)
     mdl.c.flags = flags
-    n, m = mdl.n, mdl.m
-    y = _inf._dev_f32(ys, "cuda").reshape(1, -1, m)
-    T = y.shape[1]
-    m_in = _inf._dev_f32(init_means, "cuda").reshape(1, K, n).contiguous()
-    P_in = _inf._dev_f32(P0, "cuda").reshape(1, 1, n, n).expand(1, K, n, n).contiguous()
-    bufs, ll, od = _inf._alloc_outputs(1, K, T, n, _inf.FILTERED, "reference", None, True, y.device)
-    yd = _lib.bf_cstream()
-    yd.ptr, yd.sB, yd.sK, yd.sT, yd.sE = y.data_ptr(), y.stride(0), 0, y.stride(1), y.stride(2)
-    ud = _lib.bf_cstream()
-    cr = _lib.bf_carry()
-    cr.m_in, cr.P_in = m_in.data_ptr(), P_in.data_ptr()
-    stream = torch.cuda.current_stream(y.device).cuda_stream
-    _lib.check(lib.bf_gsf_ekf_f32(C.byref(mdl.c), C.byref(yd), C.byref(ud), 1, T, K, C.byref(cr), C.byref(od), C.c_void_p(stream)))
-    return bufs, ll
+    y = _inf._dev_f32(ys, "cuda").reshape(1, -1, mdl.m)
+    k = _inf._filter_call(mdl, y, K, "K", init_means, P0, fields=_inf.FILTERED, return_loglik=True)
+    _lib.check(lib.bf_gsf_ekf_f32(C.byref(mdl.c), C.byref(k.yd), C.byref(k.ud), 1, k.T, K, C.byref(k.cr), C.byref(k.od),
+                                  C.c_void_p(k.stream)))
+    return k.bufs, k.ll
 
 
 class EKF:

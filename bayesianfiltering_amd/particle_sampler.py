@@ -17,7 +17,7 @@ from typing import NamedTuple, Any
 import numpy as np
 
 from . import _lib
-from .inference import _torch, _dev_f32, _Model, bootstrap_particle_filter
+from .inference import _torch, _dev_f32, _inputs_desc, _Model, bootstrap_particle_filter
 from .nonlinearities import DeviceFunction
 from .sampler import _keys_for
 
@@ -139,15 +139,8 @@ def particle_posterior_sample(params, filtered, num_samples: int = 1, *, method:
         keep.append(kd)
         sd.keys = kd.data_ptr()
 
-    ud = _lib.bf_cstream()
-    u = None
-    if inputs is not None:
-        u = _dev_f32(inputs, dev)
-        u = u.reshape(1, T, -1) if u.dim() <= 2 else u
-        if u.shape[1] != T or u.shape[0] not in (1, B):
-            raise ValueError(f"inputs must be (T,), (T,d) or (B,T,d); got {tuple(u.shape)}")
-        keep.append(u)
-        ud.ptr, ud.sB, ud.sT, ud.sE = u.data_ptr(), (u.stride(0) if u.shape[0] == B else 0), u.stride(1), 1
+    ud = _inputs_desc(inputs, B, T, dev, keep)
+    u = keep[-1] if inputs is not None else None      # (1 or B, T, d)
 
     cr = _lib.bf_pf_sample_carry()
     if carry is not None:
