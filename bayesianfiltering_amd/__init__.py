@@ -18,7 +18,8 @@ from .gaussian_sum_sampler import (GaussianSumSamplerCarry, gaussian_sum_posteri
 from .sampler import (SamplerCarry, posterior_sample, kalman_posterior_sample, extended_kalman_posterior_sample,
                       unscented_kalman_posterior_sample)
 from .particle_sampler import (ParticleSamplerCarry, particle_posterior_sample, bootstrap_particle_posterior_sample)
-from .parallel import parallel_kalman_filter, parallel_kalman_workspace_bytes
+from .parallel import (parallel_kalman_filter, parallel_kalman_workspace_bytes, parallel_rts_smoother,
+                       parallel_rts_workspace_bytes, parallel_kalman_smoother)
 from ._lib import BayesFiltError
 from . import nonlinearities, utils
 
@@ -32,4 +33,5 @@ __all__ = ["ParamsNLSSM", "ParamsBPF", "NonlinearSSM", "GaussianComponent", "Gau
            "extended_gaussian_sum_posterior_sample", "unscented_gaussian_sum_posterior_sample",
            "SamplerCarry", "posterior_sample", "kalman_posterior_sample", "extended_kalman_posterior_sample", "unscented_kalman_posterior_sample",
            "ParticleSamplerCarry", "particle_posterior_sample", "bootstrap_particle_posterior_sample",
-           "parallel_kalman_filter", "parallel_kalman_workspace_bytes"]
+           "parallel_kalman_filter", "parallel_kalman_workspace_bytes", "parallel_rts_smoother", "parallel_rts_workspace_bytes",
+           "parallel_kalman_smoother"]

@@ -166,6 +166,10 @@ SYMBOLS = {
     "bf_smoother_abi_check": (C.c_int, [C.c_size_t, C.c_size_t]),
     "bf_rts_smoother_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_out_desc), C.c_int64, C.c_int64,
                                       C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p]),
+    "bf_rts_pscan_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
+    "bf_rts_smoother_pscan_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_out_desc), C.c_int64, C.c_int64,
+                                            C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p, C.c_int64,
+                                            C.c_void_p]),
     "bf_eks_smoother_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_out_desc), C.c_int64,
                                       C.c_int64, C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p]),
     "bf_uks_smoother_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_ukf_params), C.POINTER(bf_cstream),

@@ -94,6 +94,10 @@ int backward_launch_user_generic(const bf_model* p, int jit_kind, const char* no
 // run-time-dimension kernel.  The Gaussian-sum smoother calls it with B K trajectories where the layout flattens.
 int rts_run(const BackwardRoute& r, const RtsViews& v, long long B, long long T, void* stream);
 Option& rts_load_mode_option();  // rts_smoother.hip
+// bf_out_desc / bf_smooth_carry / bf_smooth_desc -> RtsViews with the checks every smoother entry point makes (rts_smoother.hip):
+// required streams and outputs, the carry's pairs
+int rts_views(const bf_out_desc* f, const bf_smooth_carry* carry, const bf_smooth_desc* out, const bf_cstream* u, bool need_pred,
+              RtsViews& v);
 int launch_collapse(const bf_stream* w, const bf_stream* m, const bf_stream* P, long long B, long long T, int K, int n,
                     float* mean_out, float* cov_out, hipStream_t stream);  // collapse.hip
 

@@ -185,9 +185,10 @@ struct RtsProduct {
   }
 };
 
-// bf_out_desc / bf_smooth_carry / bf_smooth_desc -> RtsViews, with the checks the three entry points share
-static int rts_views(const bf_out_desc* f, const bf_smooth_carry* carry, const bf_smooth_desc* out, const bf_cstream* u,
-                     bool need_pred, RtsViews& v) {
+// bf_out_desc / bf_smooth_carry / bf_smooth_desc -> RtsViews, with the checks the entry points share (the parallel-in-time
+// smoother, rts_pscan.hip, among them)
+int rts_views(const bf_out_desc* f, const bf_smooth_carry* carry, const bf_smooth_desc* out, const bf_cstream* u, bool need_pred,
+              RtsViews& v) {
   if (!f->means.ptr || !f->covs.ptr) return set_error(BF_EINVAL, "filtered means and covariances are required");
   if (need_pred && (!f->pred_means.ptr || !f->pred_covs.ptr))
     return set_error(BF_EINVAL, "the extended and the unscented smoother need the predicted means and covariances");

@@ -1,4 +1,4 @@
-"""Parallel-in-time Kalman filter: :func:`kalman_filter` for few long trajectories.
+"""Parallel-in-time Kalman filter and RTS smoother: :func:`kalman_filter` and :func:`rts_smoother` for few long trajectories.
 
 ``kalman_filter`` gets its parallelism from the batch axis and walks time serially: one long series occupies one lane.
 :func:`parallel_kalman_filter` cuts time into blocks of ``block`` steps that run on separate lanes (associative filtering
@@ -6,12 +6,21 @@ elements combined by a prefix scan; the scheme is stated at the head of ``csrc/k
 are the ordinary filter's from that block's start state; the start states come from a jitter-free recursion, so the result
 agrees with ``kalman_filter`` to fp32 tolerance (1e-5 relative), not bit for bit.  It is worth calling up to a few thousand
 trajectories (DESIGN.md has the measured crossover); ``kalman_filter`` never dispatches to it.
+
+:func:`parallel_rts_smoother` is the backward pass with the same structure (associative smoothing elements combined by a
+suffix scan; ``csrc/rts_pscan.hpp``): inside a block the outputs are ``rts_smoother``'s from that block's carry, the last
+block -- with ``T <= block`` the whole call -- equals ``rts_smoother`` bit for bit, the rest agrees to fp32 tolerance.
+:func:`parallel_kalman_smoother` runs the two in turn.  ``rts_smoother`` and ``kalman_smoother`` never dispatch to them.
 """
 import ctypes as C
 from typing import Sequence
 
+import numpy as np
+
 from . import _lib
-from .inference import FULL5, _kalman_call, _torch
+from ._backward import _front, _wrapper_kw, _LinearDynamics
+from .inference import FULL5, _kalman_call, _param_dims, _torch
+from .smoother import _out_buffer, _smoothed_buffers, _smoothed_result
 
 
 def parallel_kalman_workspace_bytes(n: int, m: int, B: int, T: int, block=None) -> int:
@@ -21,6 +30,17 @@ def parallel_kalman_workspace_bytes(n: int, m: int, B: int, T: int, block=None) 
     if need < 0:
         _lib.check(int(need))
     return int(need)
+
+
+def _workspace(workspace, need, dev):
+    """The call's workspace: ``workspace`` after its checks, or ``need`` fresh bytes on ``dev``."""
+    torch = _torch()
+    if workspace is None:
+        return torch.empty(int(need), dtype=torch.uint8, device=dev)
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev \
+            or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous uint8 tensor on {dev}")
+    return workspace
 
 
 def parallel_kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
@@ -44,14 +64,81 @@ def parallel_kalman_filter(params, emissions, *, initial_means=None, initial_cov
     need = lib.bf_kalman_pscan_workspace_bytes(k.mdl.n, k.mdl.m, k.B, k.T, L)
     if need < 0:
         _lib.check(int(need))
-    if workspace is None:
-        workspace = torch.empty(int(need), dtype=torch.uint8, device=k.y.device)
-    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != k.y.device \
-            or not workspace.is_contiguous():
-        raise ValueError(f"workspace must be a contiguous uint8 tensor on {k.y.device}")
+    workspace = _workspace(workspace, need, k.y.device)
     opts = dict(options or {})
     opts["pkf_block"] = L
     _lib.arm_call_options(lib, opts)         # tuning options for THIS call only (bf_set_call_option)
     _lib.check(lib.bf_kalman_filter_pscan_f32(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od),
                                               C.c_void_p(workspace.data_ptr()), workspace.numel(), C.c_void_p(k.stream)))
     return k.result()
+
+
+def parallel_rts_workspace_bytes(n: int, B: int, T: int, block=None) -> int:
+    """Bytes of device workspace :func:`parallel_rts_smoother` needs at these sizes: ``4 B ceil(T / L) (3 n^2 + 2 n)``."""
+    lib = _lib.load()
+    need = lib.bf_rts_pscan_workspace_bytes(n, B, T, int(block or 0))
+    if need < 0:
+        _lib.check(int(need))
+    return int(need)
+
+
+def parallel_rts_smoother(params, posterior, *, carry=None, cross_covariances: bool = False, layout: str = "reference",
+                          out=None, return_carry: bool = False, device="cuda", options=None, block=None, workspace=None):
+    """``rts_smoother`` with time parallelism for linear dynamics: same posterior (with the predicted streams, or without:
+    they are recomputed), container (:class:`PosteriorGaussianSmoothed`), :class:`SmootherCarry`, ``out=`` rules and
+    cross-covariance step counts (T-1, or T with a carry).
+
+    block: steps per block, 4 ... 4096; ``None`` = the default of :func:`parallel_kalman_filter` for (B, T).  A trajectory's
+    bits depend on (T, block) and on whether the predictions were given, on nothing else.
+    workspace: a reusable ``torch.uint8`` device tensor of at least :func:`parallel_rts_workspace_bytes` bytes; allocated
+    when absent.  Its contents mean nothing before or after the call.
+    Linear registry dynamics, constant Q, state dimension <= 6.
+    """
+    torch = _torch()
+
+    def out_shapes(B, T, n, squeeze):
+        """``out``'s shapes, refused before the device is asked for (the full checks follow in ``_smoothed_buffers``)."""
+        c_steps = T if carry is not None else T - 1
+        for name, want in (("smoothed_means", (B, 1, T, n)), ("smoothed_covariances", (B, 1, T, n, n)),
+                           ("smoothed_cross_covariances", (B, 1, c_steps, n, n))):
+            _out_buffer(out, name, want, squeeze, None)
+
+    bw = _front("smoother", params, posterior, False, None, product_checks=out_shapes)
+    if getattr(bw.f, "M", None) is None:
+        raise ValueError("params.dynamics_function must be linear_dynamics for the parallel smoother")
+    ms, Ps, Cs, sd, cr, keep, c_out = _smoothed_buffers(bw, out, carry, cross_covariances, layout, return_carry)
+    mdl = _LinearDynamics(params, bw.f)
+    L = int(block or 0)
+    need = bw.lib.bf_rts_pscan_workspace_bytes(bw.n, bw.B, bw.T, L)
+    if need < 0:
+        _lib.check(int(need))
+    workspace = _workspace(workspace, need, bw.dev)
+    cur = torch.cuda.current_stream(bw.dev)
+    opts = dict(options or {})
+    opts["prs_block"] = L
+    _lib.arm_call_options(bw.lib, opts)      # tuning options for THIS call only (bf_set_call_option)
+    _lib.check(bw.lib.bf_rts_smoother_pscan_f32(C.byref(mdl.c), C.byref(bw.fd), bw.B, bw.T, C.byref(cr), C.byref(sd),
+                                                C.c_void_p(workspace.data_ptr()), workspace.numel(),
+                                                C.c_void_p(cur.cuda_stream)))
+    for t_ in keep:
+        t_.record_stream(cur)
+    return _smoothed_result(bw, ms, Ps, Cs, c_out, return_carry)
+
+
+def parallel_kalman_smoother(params, emissions, **kw):
+    """:func:`parallel_kalman_filter` emitting the filtered fields only, then :func:`parallel_rts_smoother` on the recompute
+    path.  Keywords of the filter (``initial_means``, ``initial_covariances``, ``layout``, ``device``) go to the filter, the
+    others to the smoother; ``block`` goes to both passes.  One workspace of the larger -- the filter's -- size is allocated
+    once and handed to both (or ``workspace=`` is)."""
+    torch = _torch()
+    fkw, skw = _wrapper_kw(params, kw, False)
+    block = kw.get("block")
+    if kw.get("workspace") is None:
+        shape = tuple(emissions.shape) if hasattr(emissions, "shape") else np.shape(emissions)
+        T, m = int(shape[-2]), int(shape[-1])
+        B = int(shape[0]) if len(shape) == 3 else 1
+        n = _param_dims(params)[0]
+        need = max(parallel_kalman_workspace_bytes(n, m, B, T, block), parallel_rts_workspace_bytes(n, B, T, block))
+        skw["workspace"] = torch.empty(need, dtype=torch.uint8, device=kw.get("device", "cuda"))
+    fkw["block"], fkw["workspace"] = block, skw["workspace"]
+    return parallel_rts_smoother(params, parallel_kalman_filter(params, emissions, **fkw), **skw)

@@ -31,6 +31,64 @@ class SmootherCarry(NamedTuple):
     covariances: Any
 
 
+def _out_buffer(out, name, want, squeeze, dev):
+    """out.<name> after the checks a raw-pointer store needs (float32, the streams' device, the exact shape ``want`` =
+    (B, 1, steps, ...)), or None.  ``dev`` = None: the shape alone (what can be refused before the device is known)."""
+    reuse = getattr(out, name, None) if out is not None else None
+    if reuse is None:
+        return None
+    if dev is not None:
+        _check_out_tensor(name, reuse, dev)
+    if squeeze and tuple(reuse.shape) == want[1:]:
+        return reuse.unsqueeze(0)
+    if tuple(reuse.shape) != want:
+        raise ValueError(f"out.{name} has shape {tuple(reuse.shape)}, expected {want[1:] if squeeze else want}")
+    return reuse
+
+
+def _smoothed_buffers(bw, out, carry, cross_covariances, layout, return_carry):
+    """The output half every smoother of one-component streams shares (:func:`rts_smoother`, ``parallel_rts_smoother``): the
+    smoothed streams -- ``out``'s where given, else allocated in ``layout`` --, their bf_smooth_desc, the bf_smooth_carry
+    with the tensors made for it (``keep``) and the carry to return."""
+    torch = _torch()
+    B, T, n, squeeze, dev = bw.B, bw.T, bw.n, bw.squeeze, bw.dev
+    ms = _out_buffer(out, "smoothed_means", (B, 1, T, n), squeeze, dev)
+    Ps = _out_buffer(out, "smoothed_covariances", (B, 1, T, n, n), squeeze, dev)
+    # the cross-covariances a call returns have T-1 steps, T with a carry: that is the shape a given buffer must have
+    c_steps = T if carry is not None else T - 1
+    Cs = _out_buffer(out, "smoothed_cross_covariances", (B, 1, c_steps, n, n), squeeze, dev)
+    if ms is None:
+        ms = _alloc_stream((B, 1, T), (n,), layout, dev)
+    if Ps is None:
+        Ps = _alloc_stream((B, 1, T), (n, n), layout, dev)
+    if Cs is None and cross_covariances:
+        Cs = _alloc_stream((B, 1, T), (n, n), layout, dev)[:, :, :c_steps]
+    sd = _lib.bf_smooth_desc()
+    # (T = 1 without a carry: the cross-covariances have no step, the kernel is not given the empty stream)
+    sd.means, sd.covs, sd.cross_covs = _stream_desc(ms, 1), _stream_desc(Ps, 2), _stream_desc(Cs if c_steps > 0 else None, 2)
+
+    cr = _lib.bf_smooth_carry()
+    keep = []
+    if carry is not None:
+        cm, cP = (_dev_f32(v, dev).contiguous() for v in carry)
+        if cm.numel() != B * n or cP.numel() != B * n * n:
+            raise ValueError("carry does not match (B, n) / (B, n, n)")
+        keep += [cm, cP]
+        cr.m_in, cr.P_in = cm.data_ptr(), cP.data_ptr()
+    c_out = None
+    if return_carry:
+        c_out = SmootherCarry(torch.empty((B, n), dtype=torch.float32, device=dev),
+                              torch.empty((B, n, n), dtype=torch.float32, device=dev))
+        cr.m_out, cr.P_out = c_out.means.data_ptr(), c_out.covariances.data_ptr()
+    return ms, Ps, Cs, sd, cr, keep, c_out
+
+
+def _smoothed_result(bw, ms, Ps, Cs, c_out, return_carry):
+    sq = (lambda x: x[0] if (bw.squeeze and x is not None) else x)
+    post = PosteriorGaussianSmoothed(sq(bw.m_b), sq(bw.P_b), sq(ms), sq(Ps), sq(Cs))
+    return (post, c_out) if return_carry else post
+
+
 def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariances: bool = False, layout: str = "reference",
                  out=None, return_carry: bool = False, extended: Optional[bool] = None, uparams=None, device="cuda",
                  options=None):
@@ -57,57 +115,12 @@ def rts_smoother(params, posterior, *, inputs=None, carry=None, cross_covariance
     without a carry that is the empty (B, 1, 0, n, n) tensor and nothing is stored into it), anything else is refused
     before a kernel is launched.  Returns :class:`PosteriorGaussianSmoothed` (and the carry when ``return_carry``).
     """
-    torch = _torch()
     bw = _front("smoother", params, posterior, extended, uparams)
-    m_b, P_b, B, T, n, squeeze, dev = bw.m_b, bw.P_b, bw.B, bw.T, bw.n, bw.squeeze, bw.dev
-
-    def buf(name, ev, steps):
-        """out.<name> after the checks a raw-pointer store needs (float32, the streams' device, the exact shape), or None."""
-        reuse = getattr(out, name, None) if out is not None else None
-        if reuse is None:
-            return None
-        _check_out_tensor(name, reuse, dev)
-        want = (B, 1, steps) + ev
-        if squeeze and tuple(reuse.shape) == want[1:]:
-            return reuse.unsqueeze(0)
-        if tuple(reuse.shape) != want:
-            raise ValueError(f"out.{name} has shape {tuple(reuse.shape)}, expected {want[1:] if squeeze else want}")
-        return reuse
-
-    ms, Ps = buf("smoothed_means", (n,), T), buf("smoothed_covariances", (n, n), T)
-    # the cross-covariances a call returns have T-1 steps, T with a carry: that is the shape a given buffer must have
-    c_steps = T if carry is not None else T - 1
-    Cs = buf("smoothed_cross_covariances", (n, n), c_steps)
-    if ms is None:
-        ms = _alloc_stream((B, 1, T), (n,), layout, dev)
-    if Ps is None:
-        Ps = _alloc_stream((B, 1, T), (n, n), layout, dev)
-    if Cs is None and cross_covariances:
-        Cs = _alloc_stream((B, 1, T), (n, n), layout, dev)[:, :, :c_steps]
-    sd = _lib.bf_smooth_desc()
-    # (T = 1 without a carry: the cross-covariances have no step, the kernel is not given the empty stream)
-    sd.means, sd.covs, sd.cross_covs = _stream_desc(ms, 1), _stream_desc(Ps, 2), _stream_desc(Cs if c_steps > 0 else None, 2)
-
-    cr = _lib.bf_smooth_carry()
-    keep = []
-    if carry is not None:
-        cm, cP = (_dev_f32(v, dev).contiguous() for v in carry)
-        if cm.numel() != B * n or cP.numel() != B * n * n:
-            raise ValueError("carry does not match (B, n) / (B, n, n)")
-        keep += [cm, cP]
-        cr.m_in, cr.P_in = cm.data_ptr(), cP.data_ptr()
-    c_out = None
-    if return_carry:
-        c_out = SmootherCarry(torch.empty((B, n), dtype=torch.float32, device=dev),
-                              torch.empty((B, n, n), dtype=torch.float32, device=dev))
-        cr.m_out, cr.P_out = c_out.means.data_ptr(), c_out.covariances.data_ptr()
+    ms, Ps, Cs, sd, cr, keep, c_out = _smoothed_buffers(bw, out, carry, cross_covariances, layout, return_carry)
 
     _call("smoother", ("bf_rts_smoother_f32", "bf_eks_smoother_f32", "bf_uks_smoother_f32"), bw, params, inputs, options,
-          (C.byref(cr), C.byref(sd)), keep, torch.cuda.current_stream(dev))
-
-    sq = (lambda x: x[0] if (squeeze and x is not None) else x)
-    post = PosteriorGaussianSmoothed(sq(m_b), sq(P_b), sq(ms), sq(Ps), sq(Cs))
-    return (post, c_out) if return_carry else post
+          (C.byref(cr), C.byref(sd)), keep, _torch().cuda.current_stream(bw.dev))
+    return _smoothed_result(bw, ms, Ps, Cs, c_out, return_carry)
 
 
 def kalman_smoother(params, emissions, **kw):

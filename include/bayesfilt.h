@@ -144,6 +144,8 @@ int bf_device_count(void);
  *                   the kernels built around dynamics given as source have the same four counts.
  *   "pkf_block":    block length L of bf_kalman_filter_pscan_f32: 0 (default) = from (B, T), otherwise 4 ... 4096 (the arithmetic of
  *                   a trajectory depends on T and L alone).
+ *   "prs_block":    block length L of bf_rts_smoother_pscan_f32: 0 (default) = from (B, T) by the rule of "pkf_block", otherwise
+ *                   4 ... 4096.
  *   "gsf_structured": 1 (default) lets bf_gsf_ekf_f32 use the structure-aware kernel instances
  *                   (banded Lorenz-96 Jacobian, selection emission) when the model qualifies;
  *                   0 forces the dense generic instances.
@@ -163,7 +165,7 @@ int bf_device_count(void);
  * bf_set_option changes the PROCESS-WIDE default.  A library or a thread that must not disturb -- or be disturbed by -- other
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
  * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
- * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_eks_smoother_f32,
+ * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_rts_smoother_pscan_f32, bf_eks_smoother_f32,
  * bf_ffbs_sample_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_gs_smoother_f32, bf_gs_sample_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
 int bf_set_option(const char* name, int value);
@@ -196,7 +198,7 @@ int bf_kalman_filter_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, 
  * BF_EUNSUPPORTED: n > 6 or m > 4 (register kernels: the scan needs scratch from n = 7; the message names the limit), per-step covariances (Q_steps or
  * R_steps > 1: "constant Q and R"), collapsed streams, a singular S = H G Q G^T H^T + D R D^T.  BF_EINVAL: NULL arguments,
  * B or T <= 0, a workspace that is too small (the message names the bytes needed).  Every check precedes the first HIP call.
- * With these two, this header declares 41 entry points. */
+ * With these two, this header declares 41 entry points (43 with the two of the parallel-in-time smoother below). */
 int64_t bf_kalman_pscan_workspace_bytes(int32_t n, int32_t m, int64_t B, int64_t T, int32_t block); /* < 0: BF_E* */
 int bf_kalman_filter_pscan_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T,
                                const bf_carry* carry, const bf_out_desc* out,
@@ -460,6 +462,30 @@ int bf_smoother_abi_check(size_t sizeof_smooth_desc, size_t sizeof_smooth_carry)
  * one lane per trajectory; larger n: the run-time-dimension kernel (one workgroup per trajectory, state in LDS). */
 int bf_rts_smoother_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T,
                         const bf_smooth_carry* carry, const bf_smooth_desc* out, void* stream);
+
+/* Parallel-in-time RTS smoother for few long trajectories: the model, streams, carry and outputs of bf_rts_smoother_f32 (both
+ * of its routes: predictions given, or both NULL and recomputed), with time cut into blocks of L steps that run on separate
+ * lanes (the associative smoothing elements of Sarkka & Garcia-Fernandez 2021; the scheme is stated at the head of
+ * csrc/rts_pscan.hpp).  Three launches on `stream`, no waiting between workgroups: fold (one lane per (trajectory, block) builds
+ * the block's aggregate; the last block's is its smoothed first-step state), scan (one workgroup per trajectory turns the
+ * aggregates into the smoothed state at every block's first step), emit (one lane per (trajectory, block) runs the ordinary
+ * backward step of bf_rts_smoother_f32 from the state after its block and stores the streams, any strides).
+ * Inside a block the outputs are the ordinary smoother's from that block's carry: the last block, and with T <= L the whole
+ * call, equals bf_rts_smoother_f32 bit for bit; elsewhere the two agree to fp32 tolerance (1e-5 relative).  A trajectory's bits
+ * depend on (T, L) and the route alone.  NaN handling is bf_rts_smoother_f32's (from a step backwards, in that trajectory only).
+ * L: option "prs_block" (4..4096; 0 = default: the rule of "pkf_block").
+ * workspace: a caller-owned DEVICE buffer of at least bf_rts_pscan_workspace_bytes(n, B, T, L) =
+ *   4 B ceil(T / L) (3 n^2 + 2 n) bytes, 4-byte aligned; its contents before and after the call mean nothing.
+ * bf_rts_pscan_workspace_bytes: `block` = 0 reads "prs_block" as the call would and else uses the default; a negative result is
+ * a BF_E* code (B or T <= 0, a block length outside 4..4096, n that is not built, B ceil(T / L) >= 2^31).
+ * BF_EUNSUPPORTED: n > 6 (the parallel filter's limit; the message names it), a per-step Q (Q_steps > 1: "constant Q").
+ * BF_EINVAL: NULL arguments (carry may be NULL), missing streams or outputs, one predicted stream without the other, B or
+ * T <= 0, a workspace that is too small (the message names the bytes needed) or misaligned.  Every check precedes the first HIP
+ * call.  With these two, this header declares 43 entry points. */
+int64_t bf_rts_pscan_workspace_bytes(int32_t n, int64_t B, int64_t T, int32_t block); /* < 0: BF_E* */
+int bf_rts_smoother_pscan_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T,
+                              const bf_smooth_carry* carry, const bf_smooth_desc* out,
+                              void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Extended RTS smoother (K = 1; the streams of bf_gsf_ekf_f32 with one component) for registry dynamics and for dynamics
  * given as source.  pred_means / pred_covs are required.  u: the filter's inputs (NULL or u->ptr == NULL = zeros).
