@@ -19,7 +19,8 @@ from .sampler import (SamplerCarry, posterior_sample, kalman_posterior_sample, e
                       unscented_kalman_posterior_sample)
 from .particle_sampler import (ParticleSamplerCarry, particle_posterior_sample, bootstrap_particle_posterior_sample)
 from .parallel import (parallel_kalman_filter, parallel_kalman_workspace_bytes, parallel_rts_smoother,
-                       parallel_rts_workspace_bytes, parallel_kalman_smoother)
+                       parallel_rts_workspace_bytes, parallel_kalman_smoother, parallel_posterior_sample,
+                       parallel_ffbs_workspace_bytes, parallel_kalman_posterior_sample)
 from ._lib import BayesFiltError
 from . import nonlinearities, utils
 
@@ -34,4 +35,5 @@ __all__ = ["ParamsNLSSM", "ParamsBPF", "NonlinearSSM", "GaussianComponent", "Gau
            "SamplerCarry", "posterior_sample", "kalman_posterior_sample", "extended_kalman_posterior_sample", "unscented_kalman_posterior_sample",
            "ParticleSamplerCarry", "particle_posterior_sample", "bootstrap_particle_posterior_sample",
            "parallel_kalman_filter", "parallel_kalman_workspace_bytes", "parallel_rts_smoother", "parallel_rts_workspace_bytes",
-           "parallel_kalman_smoother"]
+           "parallel_kalman_smoother", "parallel_posterior_sample", "parallel_ffbs_workspace_bytes",
+           "parallel_kalman_posterior_sample"]

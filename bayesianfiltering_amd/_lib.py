@@ -185,6 +185,10 @@ SYMBOLS = {
     "bf_sampler_abi_check": (C.c_int, [C.c_size_t, C.c_size_t]),
     "bf_ffbs_sample_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.c_int32,
                                      C.POINTER(bf_sample_carry), C.POINTER(bf_sample_desc), C.c_void_p]),
+    "bf_ffbs_pscan_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "bf_ffbs_sample_pscan_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_out_desc), C.c_int64, C.c_int64, C.c_int32,
+                                           C.POINTER(bf_sample_carry), C.POINTER(bf_sample_desc), C.c_void_p, C.c_int64,
+                                           C.c_void_p]),
     "bf_effbs_sample_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_out_desc), C.c_int64,
                                       C.c_int64, C.c_int32, C.POINTER(bf_sample_carry), C.POINTER(bf_sample_desc),
                                       C.c_void_p]),

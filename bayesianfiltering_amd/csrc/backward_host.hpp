@@ -98,6 +98,11 @@ Option& rts_load_mode_option();  // rts_smoother.hip
 // required streams and outputs, the carry's pairs
 int rts_views(const bf_out_desc* f, const bf_smooth_carry* carry, const bf_smooth_desc* out, const bf_cstream* u, bool need_pred,
               RtsViews& v);
+// bf_out_desc / bf_sample_carry / bf_sample_desc -> FfbsViews with the checks every linear or extended sampler entry point makes
+// (ffbs_sampler.hip): sizes, required streams and output, noise or keys, the key mode's count limit
+int ffbs_views(const bf_out_desc* f, const bf_sample_carry* carry, const bf_sample_desc* out, const bf_cstream* u, long long B,
+               long long T, int S, int n, bool need_pred, FfbsViews& v);
+Option& ffbs_spl_option();  // ffbs_sampler.hip
 int launch_collapse(const bf_stream* w, const bf_stream* m, const bf_stream* P, long long B, long long T, int K, int n,
                     float* mean_out, float* cov_out, hipStream_t stream);  // collapse.hip
 

@@ -97,6 +97,7 @@ Option& force_generic_option() { return g_force_generic; }  // read by the backw
 Option& ffbs_spl_option();  // ffbs_sampler.hip: 0 = from S and n, else samples per lane of the register kernel
 Option& pkf_block_option();  // kf_pscan.hip: 0 = from (B, T), else the block length of the parallel-in-time Kalman filter
 Option& prs_block_option();  // rts_pscan.hip: 0 = from (B, T), else the block length of the parallel-in-time RTS smoother
+Option& pfs_block_option();  // ffbs_pscan.hip: 0 = from (B, S, T), else the block length of the parallel-in-time posterior sampler
 long long kf_pscan_workspace_bytes(int n, int m, long long B, long long T, int block);
 int launch_kf_pscan(const bf_lgssm* model, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
                     const bf_out_desc* out, void* workspace, long long workspace_bytes, hipStream_t stream);
@@ -166,6 +167,7 @@ static int set_option_impl(const char* name, int value, bool this_call_only) {
       {"ffbs_spl", bf::ffbs_spl_option(), [](int v) { return v == 0 || v == 1 || v == 2 || v == 4 || v == 8; }, "ffbs_spl must be 0, 1, 2, 4 or 8"},
       {"pkf_block", bf::pkf_block_option(), [](int v) { return v == 0 || (v >= 4 && v <= 4096); }, "pkf_block must be 0 or 4..4096"},
       {"prs_block", bf::prs_block_option(), [](int v) { return v == 0 || (v >= 4 && v <= 4096); }, "prs_block must be 0 or 4..4096"},
+      {"pfs_block", bf::pfs_block_option(), [](int v) { return v == 0 || (v >= 4 && v <= 4096); }, "pfs_block must be 0 or 4..4096"},
       {"gsf_structured", bf::g_gsf_structured, flag, "gsf_structured must be 0 or 1"},
       {"bpf_variant", bf::g_bpf_variant, flag, "bpf_variant must be 0 or 1"},
       {"bpf_hbm_mode", bf::g_bpf_hbm_mode, [](int v) { return v >= 0 && v <= 2; }, "bpf_hbm_mode must be 0, 1 or 2"},

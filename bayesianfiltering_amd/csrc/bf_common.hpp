@@ -32,7 +32,7 @@ int set_error(int code, const char* fmt, ...);
 // that one caller's choices never leak into another caller's launches.  Reads behave like the std::atomic<int> it replaces.
 enum OptionId { OPT_KF_EMIT_MODE, OPT_KF_LANES, OPT_KF_SMALL_MODE, OPT_FORCE_GENERIC, OPT_GSF_STRUCTURED,
                 OPT_BPF_VARIANT, OPT_BPF_HBM_MODE, OPT_BPF_SPEC, OPT_BPF_ARITH, OPT_RTS_LOAD_MODE, OPT_UGSF_FORCE_GENERIC, OPT_FFBS_SPL,
-                OPT_AGSF_FORCE_GENERIC, OPT_PKF_BLOCK, OPT_PRS_BLOCK,
+                OPT_AGSF_FORCE_GENERIC, OPT_PKF_BLOCK, OPT_PRS_BLOCK, OPT_PFS_BLOCK,
                 OPT_COUNT };
 struct CallOverrides {
   int value[OPT_COUNT];

@@ -177,8 +177,9 @@ struct FfbsProduct {
   }
 };
 
-// bf_out_desc / bf_sample_carry / bf_sample_desc -> FfbsViews, with the checks the three entry points share
-static int ffbs_views(const bf_out_desc* f, const bf_sample_carry* carry, const bf_sample_desc* out, const bf_cstream* u,
+// bf_out_desc / bf_sample_carry / bf_sample_desc -> FfbsViews, with the checks the sampler entry points share (the parallel
+// sampler, ffbs_pscan.hip, among them)
+int ffbs_views(const bf_out_desc* f, const bf_sample_carry* carry, const bf_sample_desc* out, const bf_cstream* u,
                       long long B, long long T, int S, int n, bool need_pred, FfbsViews& v) {
   if (B <= 0 || T <= 0) return set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", B, T);
   if (S <= 0) return set_error(BF_EINVAL, "the number of samples S must be positive (S=%d)", S);

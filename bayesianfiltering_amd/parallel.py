@@ -1,4 +1,5 @@
-"""Parallel-in-time Kalman filter and RTS smoother: :func:`kalman_filter` and :func:`rts_smoother` for few long trajectories.
+"""Parallel-in-time Kalman filter, RTS smoother and posterior sampler: :func:`kalman_filter`, :func:`rts_smoother` and
+:func:`posterior_sample` for few long trajectories.
 
 ``kalman_filter`` gets its parallelism from the batch axis and walks time serially: one long series occupies one lane.
 :func:`parallel_kalman_filter` cuts time into blocks of ``block`` steps that run on separate lanes (associative filtering
@@ -11,6 +12,12 @@ trajectories (DESIGN.md has the measured crossover); ``kalman_filter`` never dis
 suffix scan; ``csrc/rts_pscan.hpp``): inside a block the outputs are ``rts_smoother``'s from that block's carry, the last
 block -- with ``T <= block`` the whole call -- equals ``rts_smoother`` bit for bit, the rest agrees to fp32 tolerance.
 :func:`parallel_kalman_smoother` runs the two in turn.  ``rts_smoother`` and ``kalman_smoother`` never dispatch to them.
+
+:func:`parallel_posterior_sample` is the third consumer of those streams (the backward-sampling step is an affine map of the
+sample at t+1, so spans of steps combine by a suffix scan; ``csrc/ffbs_pscan.hpp``): inside a block the samples are
+``posterior_sample``'s from that block's start, the last block -- with ``T <= block`` the whole call -- equals it bit for bit
+on the same streams and noise, the rest agrees to fp32 tolerance.  :func:`parallel_kalman_posterior_sample` runs the parallel
+filter and then it.  ``posterior_sample`` and ``kalman_posterior_sample`` never dispatch to them.
 """
 import ctypes as C
 from typing import Sequence
@@ -20,6 +27,8 @@ import numpy as np
 from . import _lib
 from ._backward import _front, _wrapper_kw, _LinearDynamics
 from .inference import FULL5, _kalman_call, _param_dims, _torch
+from .nonlinearities import DeviceFunction
+from .sampler import _sampler_front, _sampler_args
 from .smoother import _out_buffer, _smoothed_buffers, _smoothed_result
 
 
@@ -142,3 +151,82 @@ def parallel_kalman_smoother(params, emissions, **kw):
         skw["workspace"] = torch.empty(need, dtype=torch.uint8, device=kw.get("device", "cuda"))
     fkw["block"], fkw["workspace"] = block, skw["workspace"]
     return parallel_rts_smoother(params, parallel_kalman_filter(params, emissions, **fkw), **skw)
+
+
+def parallel_ffbs_workspace_bytes(n: int, B: int, T: int, S: int, block=None) -> int:
+    """Bytes of device workspace :func:`parallel_posterior_sample` needs at these sizes: ``4 B ceil(T / L) (n^2 + 2 S n)``."""
+    lib = _lib.load()
+    need = lib.bf_ffbs_pscan_workspace_bytes(n, B, T, S, int(block or 0))
+    if need < 0:
+        _lib.check(int(need))
+    return int(need)
+
+
+def parallel_posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise=None, carry=None,
+                              return_carry: bool = False, layout: str = "reference", out=None, device="cuda", options=None,
+                              block=None, workspace=None, **unsupported):
+    """``posterior_sample`` with time parallelism for linear dynamics: same posterior (with the predicted streams, or without:
+    they are recomputed), ``key`` / ``noise`` rules, result shapes, :class:`SamplerCarry` and ``out=`` rules.
+
+    block: steps per block, 4 ... 4096; ``None`` = a default from (B, S, T): the largest of ceil(B ceil(S / 4) T / 65 536) (one
+    (trajectory, block, four samples) lane per lane of the device), sqrt(T / 250) (the measured balance between the scan and
+    the lanes' work) and 16.  A sample's bits
+    depend on (T, block), on whether the predictions were given, on its trajectory's streams and on its own noise row (with
+    ``key``: on (S, T) too, through the key's definition), on nothing else.
+    workspace: a reusable ``torch.uint8`` device tensor of at least :func:`parallel_ffbs_workspace_bytes` bytes; allocated
+    when absent.  Its contents mean nothing before or after the call.
+    ``options``: e.g. ``{"ffbs_spl": 2}`` (samples per lane: 1, 2 or 4).
+    Linear registry dynamics, constant Q, state dimension <= 6; ``extended``, ``uparams`` and ``inputs`` are refused.
+    """
+    torch = _torch()
+    for name in unsupported:
+        if name not in ("extended", "uparams", "inputs"):
+            raise TypeError(f"parallel_posterior_sample() got an unexpected keyword argument {name!r}")
+        raise ValueError(f"the parallel sampler serves linear dynamics without inputs: it does not take {name}=")
+    linear = "params.dynamics_function must be linear_dynamics for the parallel sampler"
+    if isinstance(params.dynamics_function, DeviceFunction) and getattr(params.dynamics_function, "M", None) is None:
+        raise ValueError(linear)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8):
+        raise ValueError("workspace must be a contiguous uint8 tensor on the posterior's device")
+    S = int(num_samples)
+    bw = _sampler_front(params, posterior, S, key, noise, False, None, device)
+    if getattr(bw.f, "M", None) is None:   # a plain Python function, recorded by the front half
+        raise ValueError(linear)
+    xs, sd, cr, c_out, keep = _sampler_args(bw, S, key, noise, carry, return_carry, layout, out)
+    mdl = _LinearDynamics(params, bw.f)
+    L = int(block or 0)
+    need = bw.lib.bf_ffbs_pscan_workspace_bytes(bw.n, bw.B, bw.T, S, L)
+    if need < 0:
+        _lib.check(int(need))
+    workspace = _workspace(workspace, need, bw.dev)
+    cur = torch.cuda.current_stream(bw.dev)
+    opts = dict(options or {})
+    opts["pfs_block"] = L
+    _lib.arm_call_options(bw.lib, opts)      # tuning options for THIS call only (bf_set_call_option)
+    _lib.check(bw.lib.bf_ffbs_sample_pscan_f32(C.byref(mdl.c), C.byref(bw.fd), bw.B, bw.T, S, C.byref(cr), C.byref(sd),
+                                               C.c_void_p(workspace.data_ptr()), workspace.numel(),
+                                               C.c_void_p(cur.cuda_stream)))
+    for t_ in keep:
+        t_.record_stream(cur)
+    res = xs[0] if bw.squeeze else xs
+    return (res, c_out) if return_carry else res
+
+
+def parallel_kalman_posterior_sample(params, emissions, num_samples, key, **kw):
+    """:func:`parallel_kalman_filter` emitting the filtered fields only, then :func:`parallel_posterior_sample` on the
+    recompute path.  Keywords of the filter (``initial_means``, ``initial_covariances``, ``layout``, ``device``) go to the
+    filter, the others to the sampler (``noise=`` among them: then ``key`` is None); ``block`` goes to both passes.  One
+    workspace of the larger size is allocated once and handed to both (or ``workspace=`` is)."""
+    torch = _torch()
+    fkw, skw = _wrapper_kw(params, kw, False)
+    block = kw.get("block")
+    if kw.get("workspace") is None:
+        shape = tuple(emissions.shape) if hasattr(emissions, "shape") else np.shape(emissions)
+        T, m = int(shape[-2]), int(shape[-1])
+        B = int(shape[0]) if len(shape) == 3 else 1
+        n = _param_dims(params)[0]
+        need = max(parallel_kalman_workspace_bytes(n, m, B, T, block),
+                   parallel_ffbs_workspace_bytes(n, B, T, int(num_samples), block))
+        skw["workspace"] = torch.empty(need, dtype=torch.uint8, device=kw.get("device", "cuda"))
+    fkw["block"], fkw["workspace"] = block, skw["workspace"]
+    return parallel_posterior_sample(params, parallel_kalman_filter(params, emissions, **fkw), num_samples, key=key, **skw)

@@ -35,33 +35,14 @@ def _keys_for(key, B):
     return bfr.split(k.astype(np.uint32), B)
 
 
-def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise=None, inputs=None, carry=None,
-                     return_carry: bool = False, layout: str = "reference", out=None, extended: Optional[bool] = None,
-                     uparams=None, device="cuda", options=None):
-    """Draw ``num_samples`` joint trajectories per filtered trajectory of ``posterior`` (a ``PosteriorGaussianSumFiltered``
-    of ``kalman_filter``, or of ``gaussian_sum_filter`` with one component) on the device.  Returns a float32 device
-    tensor (S, T, n) for one trajectory, (B, S, T, n) for a batch.
-
-    Exactly one of ``key`` and ``noise``.  ``noise``: a device float32 tensor of standard normals shaped like the result.
-    ``key``: ``keys = random.split(key, B)`` (a (B, 2) array of keys is taken as it is) and trajectory b uses
-    ``random.normal(keys[b], (S, T, n))``; chunked calls take a key per chunk.
-    Linear dynamics run ``bf_ffbs_sample_f32`` (without the predicted streams in ``posterior`` they are recomputed);
-    other registry dynamics, ``nonlinearities.user_dynamics`` source and plain Python functions (recorded at the model's
-    dimensions) run ``bf_effbs_sample_f32`` and need them, ``extended=True`` sends a linear model there too.
-    ``uparams`` (a :class:`ParamsUKF` or a 3-tuple): the posterior is ``unscented_gaussian_sum_filter``'s with one component
-    and the gain uses the sigma-point cross-covariance of the filter's predict (``bf_uffbs_sample_f32``, the contract and
-    its float32 error model as in :func:`rts_smoother`; registry dynamics only); it needs the predicted streams and excludes
-    ``extended=True``.
-    ``carry``: the :class:`SamplerCarry` returned (``return_carry=True``) by the sampling of the steps that FOLLOW these.
-    ``out``: a tensor a previous call returned, reused.  ``device`` must name the device the posterior's streams live on.
-    ``options``: e.g. ``{"ffbs_spl": 4}``, ``{"force_generic": 1}``.
-    """
+def _sampler_front(params, posterior, S, key, noise, extended, uparams, device):
+    """:func:`_front` for a sampler with ``S`` samples per trajectory: the checks of ``num_samples``, ``key`` / ``noise`` and
+    ``device`` that every sampler of one-component streams makes before device work."""
     torch = _torch()
-    S = int(num_samples)
 
     def checks(B, T, n, squeeze):
         if S <= 0:
-            raise ValueError(f"num_samples must be positive; got {num_samples}")
+            raise ValueError(f"num_samples must be positive; got {S}")
         if (key is None) == (noise is None):
             raise ValueError("exactly one of key and noise must be given")
         if noise is not None:
@@ -72,11 +53,17 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
                 raise ValueError(f"noise has shape {tuple(noise.shape)}, expected {want}")
 
     bw = _front("sampler", params, posterior, extended, uparams, checks, (noise,), "posterior streams and noise")
-    B, T, n, squeeze, dev = bw.B, bw.T, bw.n, bw.squeeze, bw.dev
     want_dev = torch.device(device)
-    if want_dev.type != dev.type or (want_dev.index is not None and want_dev.index != dev.index):
-        raise ValueError(f"device={device!r}, but the posterior lives on {dev}: the sampler runs where its streams are")
+    if want_dev.type != bw.dev.type or (want_dev.index is not None and want_dev.index != bw.dev.index):
+        raise ValueError(f"device={device!r}, but the posterior lives on {bw.dev}: the sampler runs where its streams are")
+    return bw
 
+
+def _sampler_args(bw, S, key, noise, carry, return_carry, layout, out):
+    """The sample buffer (``out`` after its checks, or fresh in ``layout``), the bf_sample_desc and bf_sample_carry of one
+    call, the :class:`SamplerCarry` to return (or None) and the tensors made for the call, to keep until it has run."""
+    torch = _torch()
+    B, T, n, squeeze, dev = bw.B, bw.T, bw.n, bw.squeeze, bw.dev
     keep = []
     if out is not None:
         if not isinstance(out, torch.Tensor):
@@ -112,11 +99,37 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
     if return_carry:
         c_out = SamplerCarry(torch.empty((B, S, n), dtype=torch.float32, device=dev))
         cr.x_out = c_out.states.data_ptr()
+    return xs, sd, cr, c_out, keep
 
+
+def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise=None, inputs=None, carry=None,
+                     return_carry: bool = False, layout: str = "reference", out=None, extended: Optional[bool] = None,
+                     uparams=None, device="cuda", options=None):
+    """Draw ``num_samples`` joint trajectories per filtered trajectory of ``posterior`` (a ``PosteriorGaussianSumFiltered``
+    of ``kalman_filter``, or of ``gaussian_sum_filter`` with one component) on the device.  Returns a float32 device
+    tensor (S, T, n) for one trajectory, (B, S, T, n) for a batch.
+
+    Exactly one of ``key`` and ``noise``.  ``noise``: a device float32 tensor of standard normals shaped like the result.
+    ``key``: ``keys = random.split(key, B)`` (a (B, 2) array of keys is taken as it is) and trajectory b uses
+    ``random.normal(keys[b], (S, T, n))``; chunked calls take a key per chunk.
+    Linear dynamics run ``bf_ffbs_sample_f32`` (without the predicted streams in ``posterior`` they are recomputed);
+    other registry dynamics, ``nonlinearities.user_dynamics`` source and plain Python functions (recorded at the model's
+    dimensions) run ``bf_effbs_sample_f32`` and need them, ``extended=True`` sends a linear model there too.
+    ``uparams`` (a :class:`ParamsUKF` or a 3-tuple): the posterior is ``unscented_gaussian_sum_filter``'s with one component
+    and the gain uses the sigma-point cross-covariance of the filter's predict (``bf_uffbs_sample_f32``, the contract and
+    its float32 error model as in :func:`rts_smoother`; registry dynamics only); it needs the predicted streams and excludes
+    ``extended=True``.
+    ``carry``: the :class:`SamplerCarry` returned (``return_carry=True``) by the sampling of the steps that FOLLOW these.
+    ``out``: a tensor a previous call returned, reused.  ``device`` must name the device the posterior's streams live on.
+    ``options``: e.g. ``{"ffbs_spl": 4}``, ``{"force_generic": 1}``.
+    """
+    S = int(num_samples)
+    bw = _sampler_front(params, posterior, S, key, noise, extended, uparams, device)
+    xs, sd, cr, c_out, keep = _sampler_args(bw, S, key, noise, carry, return_carry, layout, out)
     _call("sampler", ("bf_ffbs_sample_f32", "bf_effbs_sample_f32", "bf_uffbs_sample_f32"), bw, params, inputs, options,
-          (S, C.byref(cr), C.byref(sd)), keep, torch.cuda.current_stream(dev))
+          (S, C.byref(cr), C.byref(sd)), keep, _torch().cuda.current_stream(bw.dev))
 
-    res = xs[0] if squeeze else xs
+    res = xs[0] if bw.squeeze else xs
     return (res, c_out) if return_carry else res
 
 

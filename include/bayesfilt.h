@@ -146,6 +146,7 @@ int bf_device_count(void);
  *                   a trajectory depends on T and L alone).
  *   "prs_block":    block length L of bf_rts_smoother_pscan_f32: 0 (default) = from (B, T) by the rule of "pkf_block", otherwise
  *                   4 ... 4096.
+ *   "pfs_block":    block length L of bf_ffbs_sample_pscan_f32: 0 (default) = from (B, S, T), otherwise 4 ... 4096.
  *   "gsf_structured": 1 (default) lets bf_gsf_ekf_f32 use the structure-aware kernel instances
  *                   (banded Lorenz-96 Jacobian, selection emission) when the model qualifies;
  *                   0 forces the dense generic instances.
@@ -166,7 +167,7 @@ int bf_device_count(void);
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
  * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
  * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_rts_smoother_pscan_f32, bf_eks_smoother_f32,
- * bf_ffbs_sample_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_gs_smoother_f32, bf_gs_sample_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
+ * bf_ffbs_sample_f32, bf_ffbs_sample_pscan_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_gs_smoother_f32, bf_gs_sample_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
 int bf_set_option(const char* name, int value);
 int bf_set_call_option(const char* name, int value);
@@ -481,7 +482,7 @@ int bf_rts_smoother_f32(const bf_lgssm* model, const bf_out_desc* filtered, int6
  * BF_EUNSUPPORTED: n > 6 (the parallel filter's limit; the message names it), a per-step Q (Q_steps > 1: "constant Q").
  * BF_EINVAL: NULL arguments (carry may be NULL), missing streams or outputs, one predicted stream without the other, B or
  * T <= 0, a workspace that is too small (the message names the bytes needed) or misaligned.  Every check precedes the first HIP
- * call.  With these two, this header declares 43 entry points. */
+ * call.  With these two, this header declares 43 entry points (45 with the two of the parallel-in-time sampler below). */
 int64_t bf_rts_pscan_workspace_bytes(int32_t n, int64_t B, int64_t T, int32_t block); /* < 0: BF_E* */
 int bf_rts_smoother_pscan_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T,
                               const bf_smooth_carry* carry, const bf_smooth_desc* out,
@@ -628,6 +629,37 @@ int bf_sampler_abi_check(size_t sizeof_sample_desc, size_t sizeof_sample_carry);
  * (BF_EUNSUPPORTED when n exceeds its capacity). */
 int bf_ffbs_sample_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T, int32_t S,
                        const bf_sample_carry* carry, const bf_sample_desc* out, void* stream);
+
+/* Parallel-in-time posterior sampler for few long trajectories: the model, streams, noise, carry and output of bf_ffbs_sample_f32
+ * (both of its routes: predictions given, or both NULL and recomputed), with time cut into blocks of L steps that run on separate
+ * lanes.  The backward-sampling step is an affine map x_t = G_t x_{t+1} + c_{s,t} of the sample at t+1, so a span of steps is
+ * (E, g_s) with E shared by a trajectory's samples; spans combine without a solve (E = E_i E_j, g = E_i g_j + g_i; the scheme is
+ * stated at the head of csrc/ffbs_pscan.hpp).  Three launches on `stream`, no waiting between workgroups: fold (one lane per
+ * (trajectory, block, block of samples) builds the block's aggregate; the last block's is its first-step sample), scan (one
+ * workgroup per (trajectory, sample) turns the aggregates into the sample at every block's first step), emit (one lane per
+ * (trajectory, block, block of samples) runs the ordinary backward-sampling step of bf_ffbs_sample_f32 from the sample after
+ * its block and stores through the strided view).
+ * Inside a block the samples are the serial sampler's from that block's start: the last block, and with T <= L the whole call,
+ * equals bf_ffbs_sample_f32 on the same streams and noise bit for bit; elsewhere the two agree to fp32 tolerance (1e-5
+ * relative).  A sample's bits depend on (T, L), the route, its trajectory's streams and its own noise row (with keys: also on
+ * (S, T), through element (s, t, i) = value (s T + t) n + i of S T n), not on B, the other samples, "ffbs_spl", the layout
+ * or the workspace's contents.  With keys each normal is generated twice (fold and emit).  NaN and zero pivots are
+ * bf_ffbs_sample_f32's (NaN from a step backwards, in that trajectory's samples only).
+ * L: option "pfs_block" (4..4096; 0 = default: the largest of ceil(B ceil(S / 4) T / 65 536), the smallest s with
+ * 250 s^2 >= T, and 16; at most 4096).  Samples per lane: option
+ * "ffbs_spl" 0, 1, 2 or 4 (0: the smallest of 1, 2, 4 that holds S, 4 for S > 4).
+ * workspace: a caller-owned DEVICE buffer of at least bf_ffbs_pscan_workspace_bytes(n, B, T, S, L) =
+ *   4 B ceil(T / L) (n^2 + 2 S n) bytes, 4-byte aligned; its contents before and after the call mean nothing.
+ * bf_ffbs_pscan_workspace_bytes: `block` = 0 reads "pfs_block" as the call would and else uses the default; a negative result is
+ * a BF_E* code (B, T or S <= 0, a block length outside 4..4096, n that is not built, B S ceil(T / L) >= 2^31).
+ * BF_EUNSUPPORTED: n > 6 (the parallel filter's limit; the message names it), a per-step Q (Q_steps > 1: "constant Q").
+ * BF_EINVAL: NULL arguments (carry may be NULL), missing streams or output, one predicted stream without the other, B, T or
+ * S <= 0, neither or both of noise and keys, "ffbs_spl" = 8, a workspace that is too small (the message names the bytes needed)
+ * or misaligned.  Every check precedes the first HIP call.  With these two, this header declares 45 entry points. */
+int64_t bf_ffbs_pscan_workspace_bytes(int32_t n, int64_t B, int64_t T, int32_t S, int32_t block); /* < 0: BF_E* */
+int bf_ffbs_sample_pscan_f32(const bf_lgssm* model, const bf_out_desc* filtered, int64_t B, int64_t T, int32_t S,
+                             const bf_sample_carry* carry, const bf_sample_desc* out,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Posterior samples over extended Kalman streams (pred_* required) for registry dynamics and for dynamics given as source
  * (model->user with dyn_id = BF_FN_USER: F_t by dual numbers as in bf_eks_smoother_f32, kernels compiled on first use; n <= 8:
