@@ -4,6 +4,7 @@
 #include <cstring>
 #include "bf_common.hpp"
 #include "forward_host.hpp"
+#include "pscan_host.hpp"
 #include "user_model.hpp"
 #include "bf_rng.hpp"
 
@@ -156,6 +157,8 @@ static int set_option_impl(const char* name, int value, bool this_call_only) {
     const char* message;
   };
   const auto flag = [](int v) { return v == 0 || v == 1; };
+  const auto pscan_block = [](int v) { return v == 0 || (v >= bf::PSCAN_L_MIN && v <= bf::PSCAN_L_MAX); };
+  static_assert(bf::PSCAN_L_MIN == 4 && bf::PSCAN_L_MAX == 4096, "the *_block messages below spell the limits out");
   const Row rows[] = {
       {"kf_emit_mode", bf::g_kf_emit_mode, [](int v) { return v >= -1 && v <= 2; }, "kf_emit_mode must be -1..2"},
       {"kf_lanes", bf::g_kf_lanes, [](int v) { return v >= 0 && v <= 64 && (v & (v - 1)) == 0; }, "kf_lanes must be 0 or a power of two <= 64"},
@@ -165,9 +168,9 @@ static int set_option_impl(const char* name, int value, bool this_call_only) {
       {"agsf_force_generic", bf::g_agsf_force_generic, flag, "agsf_force_generic must be 0 or 1"},
       {"rts_load_mode", bf::rts_load_mode_option(), [](int v) { return v == -1 || v == 0 || v == 2; }, "rts_load_mode must be -1, 0 or 2"},
       {"ffbs_spl", bf::ffbs_spl_option(), [](int v) { return v == 0 || v == 1 || v == 2 || v == 4 || v == 8; }, "ffbs_spl must be 0, 1, 2, 4 or 8"},
-      {"pkf_block", bf::pkf_block_option(), [](int v) { return v == 0 || (v >= 4 && v <= 4096); }, "pkf_block must be 0 or 4..4096"},
-      {"prs_block", bf::prs_block_option(), [](int v) { return v == 0 || (v >= 4 && v <= 4096); }, "prs_block must be 0 or 4..4096"},
-      {"pfs_block", bf::pfs_block_option(), [](int v) { return v == 0 || (v >= 4 && v <= 4096); }, "pfs_block must be 0 or 4..4096"},
+      {"pkf_block", bf::pkf_block_option(), pscan_block, "pkf_block must be 0 or 4..4096"},
+      {"prs_block", bf::prs_block_option(), pscan_block, "prs_block must be 0 or 4..4096"},
+      {"pfs_block", bf::pfs_block_option(), pscan_block, "pfs_block must be 0 or 4..4096"},
       {"gsf_structured", bf::g_gsf_structured, flag, "gsf_structured must be 0 or 1"},
       {"bpf_variant", bf::g_bpf_variant, flag, "bpf_variant must be 0 or 1"},
       {"bpf_hbm_mode", bf::g_bpf_hbm_mode, [](int v) { return v >= 0 && v <= 2; }, "bpf_hbm_mode must be 0, 1 or 2"},

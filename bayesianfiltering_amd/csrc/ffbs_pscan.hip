@@ -7,21 +7,16 @@
 // both routes, SPL = 1, 2, 4, builds without scratch.  Table per instance: DESIGN.md, section 6j.  n <= 6 is the parallel
 // filter's limit (kf_pscan.hip), whose streams this pass samples from.
 #include "backward_host.hpp"
+#include "pscan_host.hpp"
 
 namespace bf {
 
-#define BF_DECL(F_)                                                                                                        \
-  int F_(const BackwardRoute& r, const FfbsViews& v, long long B, long long T, int S, int spl, float* workspace, int L, \
-         hipStream_t stream, bool* matched)
-BF_DECL(launch_ffbs_pscan_group_a);
-BF_DECL(launch_ffbs_pscan_group_b);
-BF_DECL(launch_ffbs_pscan_group_c);
-BF_DECL(launch_ffbs_pscan_group_d);
-BF_DECL(launch_ffbs_pscan_group_e);
-#undef BF_DECL
+using FfbsPscanGroup = int(const BackwardRoute& r, const FfbsViews& v, long long B, long long T, int S, int spl, float* workspace,
+                           int L, hipStream_t stream, bool* matched);
+FfbsPscanGroup launch_ffbs_pscan_group_a, launch_ffbs_pscan_group_b, launch_ffbs_pscan_group_c, launch_ffbs_pscan_group_d,
+    launch_ffbs_pscan_group_e;
 
-constexpr int PFS_N_MAX = 6;
-constexpr int PFS_L_MIN = 4, PFS_L_MAX = 4096;
+static const char NAME[] = "parallel sampler";
 constexpr int PFS_SPL_MAX = 4;
 
 static Option g_pfs_block{0, OPT_PFS_BLOCK};   // 0 = from (B, S, T)
@@ -38,46 +33,20 @@ Option& pfs_block_option() { return g_pfs_block; }
 // scan is cheaper against a lane's step than the filter's and the balance sits at sqrt(T / 250) (64 at T = 10^6), not
 // sqrt(T / 50).  The count is that of the default samples per lane whatever "ffbs_spl" says: the block length, and with it
 // a sample's bits, must not depend on that option.  DESIGN.md, section 6j.
-int ffbs_pscan_default_block(long long B, int S, long long T) {
-  const long long device_lanes = 256LL * 4 * 64;
-  long long L = (B * ((S + PFS_SPL_MAX - 1) / PFS_SPL_MAX) * T + device_lanes - 1) / device_lanes;
-  long long s = 1;
-  while (250 * s * s < T && s < PFS_L_MAX) ++s;
-  if (L < s) L = s;
-  if (L < 16) L = 16;
-  if (L > PFS_L_MAX) L = PFS_L_MAX;
-  return (int)L;
-}
-
-// `block` = 0: the call option "pfs_block", else the default for (B, S, T).  < 0: BF_E* (text set).
-static int resolve_block(long long B, int S, long long T, int block) {
-  if (block == 0) block = g_pfs_block.load();
-  if (block == 0) return ffbs_pscan_default_block(B, S, T);
-  if (block < PFS_L_MIN || block > PFS_L_MAX)
-    return set_error(BF_EINVAL, "parallel sampler: block length %d is outside %d..%d", block, PFS_L_MIN, PFS_L_MAX);
-  return block;
-}
-
-static int check_n(int n) {
-  if (n <= 0) return set_error(BF_EINVAL, "non-positive model dimension");
-  if (n > PFS_N_MAX)
-    return set_error(BF_EUNSUPPORTED, "parallel sampler: n=%d is not compiled in (register kernels for n = 1..%d, the parallel filter's limit)", n,
-                     PFS_N_MAX);
-  return BF_OK;
+static int default_block(long long B, int S, long long T) {
+  return pscan_default_block(B * ((S + PFS_SPL_MAX - 1) / PFS_SPL_MAX), T, 250);
 }
 
 // 4 B ceil(T / L) (n^2 + 2 S n) bytes: per (trajectory, block) E (n^2 floats) and, per sample, g and the start sample (n each)
 long long ffbs_pscan_workspace_bytes(int n, long long B, long long T, int S, int block) {
   if (B <= 0 || T <= 0) return set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", B, T);
   if (S <= 0) return set_error(BF_EINVAL, "the number of samples S must be positive (S=%d)", S);
-  const int rc = check_n(n);
+  const int rc = pscan_check_n(NAME, n);
   if (rc != BF_OK) return rc;
-  const int L = resolve_block(B, S, T, block);
+  const int L = resolve_block(NAME, g_pfs_block, block, default_block(B, S, T));
   if (L < 0) return L;
-  const long long NB = (T + L - 1) / L;
-  if ((double)B * (double)S * (double)NB >= 2147483648.0)
-    return set_error(BF_EINVAL, "parallel sampler: B * S * ceil(T / block) = %lld * %d * %lld must stay below 2^31", B, S, NB);
-  return 4LL * B * NB * ((long long)n * n + 2LL * S * n);
+  const long long NB = pscan_blocks(NAME, B, S, T, L);
+  return NB < 0 ? NB : 4LL * B * NB * ((long long)n * n + 2LL * S * n);
 }
 
 // samples per lane: option "ffbs_spl" where it names a count compiled here, else the smallest compiled count that holds all S
@@ -101,7 +70,7 @@ int launch_ffbs_pscan(const bf_lgssm* model, const bf_out_desc* filtered, long l
   if (B <= 0 || T <= 0) return set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", B, T);
   if (S <= 0) return set_error(BF_EINVAL, "the number of samples S must be positive (S=%d)", S);
   int rc = backward_check_lgssm(model);
-  if (rc != BF_OK || (rc = check_n(model->n)) != BF_OK) return rc;
+  if (rc != BF_OK || (rc = pscan_check_n(NAME, model->n)) != BF_OK) return rc;
   if (model->Q_steps > 1)
     return set_error(BF_EUNSUPPORTED, "parallel sampler: constant Q only (Q_steps=%d)", model->Q_steps);
   FfbsViews v;
@@ -111,28 +80,19 @@ int launch_ffbs_pscan(const bf_lgssm* model, const bf_out_desc* filtered, long l
   if (recompute && (rc = backward_check_recompute(model, T)) != BF_OK) return rc;
   int spl;
   if ((rc = resolve_spl(S, &spl)) != BF_OK) return rc;
-  const int L = resolve_block(B, S, T, 0);
+  const int L = resolve_block(NAME, g_pfs_block, 0, default_block(B, S, T));
   if (L < 0) return L;
   const long long need = ffbs_pscan_workspace_bytes(model->n, B, T, S, L);
   if (need < 0) return (int)need;
-  if (workspace_bytes < need)
-    return set_error(BF_EINVAL, "parallel sampler: workspace of %lld bytes is too small: B=%lld, T=%lld, S=%d, block=%d need %lld bytes (bf_ffbs_pscan_workspace_bytes)",
-                     workspace_bytes, B, T, S, L, need);
-  if (reinterpret_cast<uintptr_t>(workspace) % 4 != 0) return set_error(BF_EINVAL, "parallel sampler: workspace must be 4-byte aligned");
+  if ((rc = pscan_check_workspace(NAME, "bf_ffbs_pscan_workspace_bytes", workspace, workspace_bytes, need, B, T, S, L)) != BF_OK)
+    return rc;
 
   BackwardRoute r;
   if ((rc = backward_route(model, recompute, r)) != BF_OK) return rc;
-  float* ws = static_cast<float*>(workspace);
-  bool matched = false;
-  rc = launch_ffbs_pscan_group_a(r, v, B, T, S, spl, ws, L, stream, &matched);
-  if (matched) return rc;
-  rc = launch_ffbs_pscan_group_b(r, v, B, T, S, spl, ws, L, stream, &matched);
-  if (matched) return rc;
-  rc = launch_ffbs_pscan_group_c(r, v, B, T, S, spl, ws, L, stream, &matched);
-  if (matched) return rc;
-  rc = launch_ffbs_pscan_group_d(r, v, B, T, S, spl, ws, L, stream, &matched);
-  if (matched) return rc;
-  rc = launch_ffbs_pscan_group_e(r, v, B, T, S, spl, ws, L, stream, &matched);
+  FfbsPscanGroup* const groups[] = {launch_ffbs_pscan_group_a, launch_ffbs_pscan_group_b, launch_ffbs_pscan_group_c,
+                                    launch_ffbs_pscan_group_d, launch_ffbs_pscan_group_e};
+  bool matched;
+  rc = pscan_run_groups(groups, &matched, r, v, B, T, S, spl, static_cast<float*>(workspace), L, stream);
   if (matched) return rc;
   return set_error(BF_EUNSUPPORTED, "parallel sampler: n=%d is not compiled in", model->n);
 }

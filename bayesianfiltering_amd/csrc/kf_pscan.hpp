@@ -25,20 +25,16 @@
 //   m' = A (I + P J)^-1 (m + P eta) + b        P' = A (I + P J)^-1 P A^T + C      (P' symmetrised)
 // A filtered state is itself the span (0, m, P, 0, 0); combining it with a later span is exactly this rule.
 //
-// Three launches, no waiting between workgroups of any kind (no look-back, no flags, no grid synchronisation); NB = ceil(T / L):
-//   fold   one lane per (trajectory, block).  Blocks 1 ... NB-2 build their L elements from y and fold them left to right
-//          into the block aggregate; block 0 is filtered from the carry with the ordinary step and its filtered end state is
-//          stored as the span (0, m, P, 0, 0); the last block needs no aggregate.  Workspace: agg[e][b NB + k], the element
-//          index e outermost so that the lanes of a wave store (and the scan loads) consecutive addresses.
-//   scan   one workgroup per trajectory walks the spans k = 0 ... NB-2 in tiles of one span per thread (64 threads for
-//          NB <= 65, else 256).  Inclusive scan inside a wave by __shfl_up (wave64, six combinations), wave totals through
-//          LDS, the running filtered state from tile to tile through LDS.  Every prefix starts at step 0, so it is a plain
+// Three launches, fold, scan and emit; the scheme and the scan are pscan_common.hpp's, here as a PREFIX scan over NB = ceil(T / L):
+//   fold   blocks 1 ... NB-2 build their L elements from y and fold them left to right into the block aggregate; block 0 is
+//          filtered from the carry with the ordinary step and its filtered end state is stored as the span (0, m, P, 0, 0); the
+//          last block needs no aggregate.  Workspace: agg[e][b NB + k].
+//   scan   one workgroup per trajectory over the spans k = 0 ... NB-2.  Every prefix starts at step 0, so it is a plain
 //          Gaussian: per block the scan writes only the prediction A m + u, A P A^T + Qb for the next block's first step,
 //          start[e][b NB + k + 1], n + n^2 floats.
-//   emit   one lane per (trajectory, block) runs the ordinary step from its block's start state -- condition_on<N, M> with the
-//          reference's 1e-6 jitter, mvn_logpdf_chol, predict_cov<N>, in the association of kf_scan_group.hpp at one lane per
-//          trajectory -- and stores the requested streams through the strided views; the last block writes the carry-out.
-// NB = 1 is the emit launch alone.
+//   emit   the ordinary step from the block's start state -- condition_on<N, M> with the reference's 1e-6 jitter,
+//          mvn_logpdf_chol, predict_cov<N>, in the association of kf_scan_group.hpp at one lane per trajectory -- and stores the
+//          requested streams through the strided views; the last block writes the carry-out.
 //
 // Consequences.  Inside a block the outputs are, for finite data, the ordinary filter's from that block's start state; the only new arithmetic
 // is in the block-start states, which are jitter-free: the product agrees with bf_kalman_filter_f32 to a tolerance, not bit for
@@ -53,13 +49,12 @@
 // Registers: every per-lane array is indexed by compile-time constants only (fully unrolled loops).  A combination holds two
 // spans of 3 n^2 + 2 n floats plus the solve's right-hand sides: no scratch up to n = 6 (table in DESIGN.md, section 6h).
 #pragma once
+#include <cstring>
 #include "kf_scan_group.hpp"
+#include "pscan_common.hpp"
+#include "pscan_host.hpp"
 
 namespace bf {
-
-// floats of one span and of one block-start state
-constexpr int ps_agg_floats(int n) { return 3 * n * n + 2 * n; }
-constexpr int ps_start_floats(int n) { return n * n + n; }
 
 template <int N, int M>
 struct PsConst {
@@ -69,40 +64,25 @@ struct PsConst {
   float W[N * M];     // eta_e = W v
   float hud[M];       // H u + d
 };
-
+// what the scan's prediction reads of KFConst
 template <int N>
-struct PsSpan {
-  float A[N * N], b[N], C[N * N], eta[N], J[N * N];
+struct PsPredict {
+  float A[N * N], GQG[N * N], Gq0[N];
 };
 
+// A | b | C | eta | J, the workspace's entry order
 template <int N>
-__device__ __forceinline__ void ps_symmetrise(float* a) {
-  BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = i + 1; j < N; ++j) {
-    const float s = 0.5f * (a[i * N + j] + a[j * N + i]);
-    a[i * N + j] = s;
-    a[j * N + i] = s;
-  }
-}
-
-// workspace <-> registers: entry e of lane g lives at ws[e * stride + g]
-template <int N>
-__device__ __forceinline__ void ps_load_span(const float* __restrict__ ws, long long stride, long long g, PsSpan<N>& s) {
-  const float* p = ws + g;
-  BF_UNROLL for (int e = 0; e < N * N; ++e) s.A[e] = p[(long long)e * stride];
-  BF_UNROLL for (int e = 0; e < N; ++e) s.b[e] = p[(long long)(N * N + e) * stride];
-  BF_UNROLL for (int e = 0; e < N * N; ++e) s.C[e] = p[(long long)(N * N + N + e) * stride];
-  BF_UNROLL for (int e = 0; e < N; ++e) s.eta[e] = p[(long long)(2 * N * N + N + e) * stride];
-  BF_UNROLL for (int e = 0; e < N * N; ++e) s.J[e] = p[(long long)(2 * N * N + 2 * N + e) * stride];
-}
-template <int N>
-__device__ __forceinline__ void ps_store_span(float* __restrict__ ws, long long stride, long long g, const PsSpan<N>& s) {
-  float* p = ws + g;
-  BF_UNROLL for (int e = 0; e < N * N; ++e) p[(long long)e * stride] = s.A[e];
-  BF_UNROLL for (int e = 0; e < N; ++e) p[(long long)(N * N + e) * stride] = s.b[e];
-  BF_UNROLL for (int e = 0; e < N * N; ++e) p[(long long)(N * N + N + e) * stride] = s.C[e];
-  BF_UNROLL for (int e = 0; e < N; ++e) p[(long long)(2 * N * N + N + e) * stride] = s.eta[e];
-  BF_UNROLL for (int e = 0; e < N * N; ++e) p[(long long)(2 * N * N + 2 * N + e) * stride] = s.J[e];
-}
+struct PsSpan {
+  static constexpr int F = 3 * N * N + 2 * N;
+  float v[F];
+  __device__ float* A() { return v; }                         __device__ const float* A() const { return v; }
+  __device__ float* b() { return v + N * N; }                 __device__ const float* b() const { return v + N * N; }
+  __device__ float* C() { return v + N * N + N; }             __device__ const float* C() const { return v + N * N + N; }
+  __device__ float* eta() { return v + 2 * N * N + N; }       __device__ const float* eta() const { return v + 2 * N * N + N; }
+  __device__ float* J() { return v + 2 * N * N + 2 * N; }     __device__ const float* J() const { return v + 2 * N * N + 2 * N; }
+};
+// a block-start state: m | P
+constexpr int ps_state_floats(int n) { return n + n * n; }
 
 // o = i (+) j, i the earlier span.  o may alias i or j: everything is read before the first write.
 template <int N>
@@ -110,70 +90,71 @@ __device__ __forceinline__ void ps_combine(const PsSpan<N>& i, const PsSpan<N>& 
   constexpr int C1 = 2 * N + 1, C2 = N + 1;
   // (I + C_i J_j) X = [A_i | C_i | b_i + C_i eta_j]
   float M1[N * N], X[N * C1], t[N];
-  mm<N, N, N>(i.C, j.J, M1);
+  mm<N, N, N>(i.C(), j.J(), M1);
   BF_UNROLL for (int r = 0; r < N; ++r) M1[r * N + r] += 1.0f;
-  mv<N, N>(i.C, j.eta, t);
+  mv<N, N>(i.C(), j.eta(), t);
   BF_UNROLL for (int r = 0; r < N; ++r) {
     BF_UNROLL for (int c = 0; c < N; ++c) {
-      X[r * C1 + c] = i.A[r * N + c];
-      X[r * C1 + N + c] = i.C[r * N + c];
+      X[r * C1 + c] = i.A()[r * N + c];
+      X[r * C1 + N + c] = i.C()[r * N + c];
     }
-    X[r * C1 + 2 * N] = i.b[r] + t[r];
+    X[r * C1 + 2 * N] = i.b()[r] + t[r];
   }
   psd_solve<N, C1>(M1, X, 0.0f);
   // (I + J_j C_i) Y = [J_j A_i | eta_j - J_j b_i]
   float M2[N * N], Y[N * C2], JA[N * N];
-  mm<N, N, N>(j.J, i.C, M2);
+  mm<N, N, N>(j.J(), i.C(), M2);
   BF_UNROLL for (int r = 0; r < N; ++r) M2[r * N + r] += 1.0f;
-  mm<N, N, N>(j.J, i.A, JA);
-  mv<N, N>(j.J, i.b, t);
+  mm<N, N, N>(j.J(), i.A(), JA);
+  mv<N, N>(j.J(), i.b(), t);
   BF_UNROLL for (int r = 0; r < N; ++r) {
     BF_UNROLL for (int c = 0; c < N; ++c) Y[r * C2 + c] = JA[r * N + c];
-    Y[r * C2 + N] = j.eta[r] - t[r];
+    Y[r * C2 + N] = j.eta()[r] - t[r];
   }
   psd_solve<N, C2>(M2, Y, 0.0f);
 
   float oA[N * N], ob[N], oC[N * N], oe[N], oJ[N * N], T1[N * N];
   BF_UNROLL for (int r = 0; r < N; ++r) {
     BF_UNROLL for (int c = 0; c < N; ++c) {
-      float sa = j.A[r * N] * X[c], sc = j.A[r * N] * X[N + c];
+      float sa = j.A()[r * N] * X[c], sc = j.A()[r * N] * X[N + c];
       BF_UNROLL for (int k = 1; k < N; ++k) {
-        sa = fmaf(j.A[r * N + k], X[k * C1 + c], sa);
-        sc = fmaf(j.A[r * N + k], X[k * C1 + N + c], sc);
+        sa = fmaf(j.A()[r * N + k], X[k * C1 + c], sa);
+        sc = fmaf(j.A()[r * N + k], X[k * C1 + N + c], sc);
       }
       oA[r * N + c] = sa;
       T1[r * N + c] = sc;   // A_j (I + C_i J_j)^-1 C_i
     }
-    float sb = j.A[r * N] * X[2 * N];
-    BF_UNROLL for (int k = 1; k < N; ++k) sb = fmaf(j.A[r * N + k], X[k * C1 + 2 * N], sb);
-    ob[r] = sb + j.b[r];
+    float sb = j.A()[r * N] * X[2 * N];
+    BF_UNROLL for (int k = 1; k < N; ++k) sb = fmaf(j.A()[r * N + k], X[k * C1 + 2 * N], sb);
+    ob[r] = sb + j.b()[r];
   }
-  mm_nt<N, N, N>(T1, j.A, oC);
-  BF_UNROLL for (int e = 0; e < N * N; ++e) oC[e] += j.C[e];
+  mm_nt<N, N, N>(T1, j.A(), oC);
+  BF_UNROLL for (int e = 0; e < N * N; ++e) oC[e] += j.C()[e];
   BF_UNROLL for (int r = 0; r < N; ++r) {   // A_i^T Y
     BF_UNROLL for (int c = 0; c < N; ++c) {
-      float s = i.A[r] * Y[c];
-      BF_UNROLL for (int k = 1; k < N; ++k) s = fmaf(i.A[k * N + r], Y[k * C2 + c], s);
-      oJ[r * N + c] = s + i.J[r * N + c];
+      float s = i.A()[r] * Y[c];
+      BF_UNROLL for (int k = 1; k < N; ++k) s = fmaf(i.A()[k * N + r], Y[k * C2 + c], s);
+      oJ[r * N + c] = s + i.J()[r * N + c];
     }
-    float s = i.A[r] * Y[N];
-    BF_UNROLL for (int k = 1; k < N; ++k) s = fmaf(i.A[k * N + r], Y[k * C2 + N], s);
-    oe[r] = s + i.eta[r];
+    float s = i.A()[r] * Y[N];
+    BF_UNROLL for (int k = 1; k < N; ++k) s = fmaf(i.A()[k * N + r], Y[k * C2 + N], s);
+    oe[r] = s + i.eta()[r];
   }
-  ps_symmetrise<N>(oC);
-  ps_symmetrise<N>(oJ);
-  BF_UNROLL for (int e = 0; e < N * N; ++e) { o.A[e] = oA[e]; o.C[e] = oC[e]; o.J[e] = oJ[e]; }
-  BF_UNROLL for (int e = 0; e < N; ++e) { o.b[e] = ob[e]; o.eta[e] = oe[e]; }
+  symmetrise<N>(oC);
+  symmetrise<N>(oJ);
+  BF_UNROLL for (int e = 0; e < N * N; ++e) { o.A()[e] = oA[e]; o.C()[e] = oC[e]; o.J()[e] = oJ[e]; }
+  BF_UNROLL for (int e = 0; e < N; ++e) { o.b()[e] = ob[e]; o.eta()[e] = oe[e]; }
 }
 
-// (m, P) <- the span s applied to the filtered state (m, P)
+// x = (m | P) <- the span s applied to the filtered state x
 template <int N>
-__device__ __forceinline__ void ps_apply(const PsSpan<N>& s, float* m, float* P) {
+__device__ __forceinline__ void ps_apply(const PsSpan<N>& s, float* x) {
   constexpr int C2 = N + 1;
+  float *m = x, *P = x + N;
   float M1[N * N], X[N * C2], t[N];
-  mm<N, N, N>(P, s.J, M1);
+  mm<N, N, N>(P, s.J(), M1);
   BF_UNROLL for (int r = 0; r < N; ++r) M1[r * N + r] += 1.0f;
-  mv<N, N>(P, s.eta, t);
+  mv<N, N>(P, s.eta(), t);
   BF_UNROLL for (int r = 0; r < N; ++r) {
     BF_UNROLL for (int c = 0; c < N; ++c) X[r * C2 + c] = P[r * N + c];
     X[r * C2 + N] = m[r] + t[r];
@@ -182,17 +163,17 @@ __device__ __forceinline__ void ps_apply(const PsSpan<N>& s, float* m, float* P)
   float T1[N * N];
   BF_UNROLL for (int r = 0; r < N; ++r) {
     BF_UNROLL for (int c = 0; c < N; ++c) {
-      float sc = s.A[r * N] * X[c];
-      BF_UNROLL for (int k = 1; k < N; ++k) sc = fmaf(s.A[r * N + k], X[k * C2 + c], sc);
+      float sc = s.A()[r * N] * X[c];
+      BF_UNROLL for (int k = 1; k < N; ++k) sc = fmaf(s.A()[r * N + k], X[k * C2 + c], sc);
       T1[r * N + c] = sc;
     }
-    float sb = s.A[r * N] * X[N];
-    BF_UNROLL for (int k = 1; k < N; ++k) sb = fmaf(s.A[r * N + k], X[k * C2 + N], sb);
-    m[r] = sb + s.b[r];
+    float sb = s.A()[r * N] * X[N];
+    BF_UNROLL for (int k = 1; k < N; ++k) sb = fmaf(s.A()[r * N + k], X[k * C2 + N], sb);
+    m[r] = sb + s.b()[r];
   }
-  mm_nt<N, N, N>(T1, s.A, P);
-  BF_UNROLL for (int e = 0; e < N * N; ++e) P[e] += s.C[e];
-  ps_symmetrise<N>(P);
+  mm_nt<N, N, N>(T1, s.A(), P);
+  BF_UNROLL for (int e = 0; e < N * N; ++e) P[e] += s.C()[e];
+  symmetrise<N>(P);
 }
 
 // ---- the ordinary step, one lane per trajectory (kf_scan_group.hpp at NL = 1) -------------------------------------------
@@ -219,9 +200,9 @@ __device__ __forceinline__ float ps_update(const KFConst<N, M>& c, const float* 
   BF_UNROLL for (int i = 0; i < N; ++i) m[i] = finite ? m[i] : __builtin_nanf("");   // (an Inf observation alone gives +-Inf here)
   return finite ? ll : __builtin_nanf("");
 }
-// predict: (m, P) filtered -> prediction for the next step
-template <int N, int M>
-__device__ __forceinline__ void ps_predict(const KFConst<N, M>& c, float* m, float* P) {
+// predict: (m, P) filtered -> prediction for the next step; Const: KFConst<N, M> or PsPredict<N>
+template <int N, class Const>
+__device__ __forceinline__ void ps_predict(const Const& c, float* m, float* P) {
   predict_cov<N>(c.A, c.GQG, P);
   float mp[N];
   mv<N, N>(c.A, m, mp);
@@ -232,10 +213,9 @@ __device__ __forceinline__ void ps_predict(const KFConst<N, M>& c, float* m, flo
 template <int N, int M>
 __device__ __forceinline__ void ps_fold_body(const PsConst<N, M>& c, const CView& y, const CarryView& carry,
                                              float* __restrict__ agg, long long B, long long NB, int L) {
-  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = B * NB;
-  if (g >= stride) return;
-  const long long b = g / NB, k = g % NB;
+  long long g, b, k;
+  int j;
+  if (!pscan_lane(B, 1, NB, g, b, j, k)) return;
   if (k == NB - 1) return;   // the last block is only emitted
   PsSpan<N> s;
   if (k == 0) {
@@ -246,13 +226,13 @@ __device__ __forceinline__ void ps_fold_body(const PsConst<N, M>& c, const CView
     for (int t = 0; t < L; ++t) {
       ps_load_y<N, M>(y, b, t, yv);
       ps_update<N, M>(c.kf, yv, m, P);
-      if (t + 1 < L) ps_predict<N, M>(c.kf, m, P);
+      if (t + 1 < L) ps_predict<N>(c.kf, m, P);
     }
-    BF_UNROLL for (int e = 0; e < N * N; ++e) { s.A[e] = 0.f; s.C[e] = P[e]; s.J[e] = 0.f; }
-    BF_UNROLL for (int e = 0; e < N; ++e) { s.b[e] = m[e]; s.eta[e] = 0.f; }
+    BF_UNROLL for (int e = 0; e < N * N; ++e) { s.A()[e] = 0.f; s.C()[e] = P[e]; s.J()[e] = 0.f; }
+    BF_UNROLL for (int e = 0; e < N; ++e) { s.b()[e] = m[e]; s.eta()[e] = 0.f; }
   } else {
     PsSpan<N> e;
-    BF_UNROLL for (int i = 0; i < N * N; ++i) { e.A[i] = c.Ae[i]; e.C[i] = c.Ce[i]; e.J[i] = c.Je[i]; }
+    BF_UNROLL for (int i = 0; i < N * N; ++i) { e.A()[i] = c.Ae[i]; e.C()[i] = c.Ce[i]; e.J()[i] = c.Je[i]; }
     const long long t0 = k * (long long)L;
     for (int q = 0; q < L; ++q) {
       float yv[M], v[M];
@@ -264,131 +244,59 @@ __device__ __forceinline__ void ps_fold_body(const PsConst<N, M>& c, const CView
           sb = fmaf(c.K[i * M + a], v[a], sb);
           se = fmaf(c.W[i * M + a], v[a], se);
         }
-        e.b[i] = c.kf.Gq0[i] + sb;
-        e.eta[i] = se;
+        e.b()[i] = c.kf.Gq0[i] + sb;
+        e.eta()[i] = se;
       }
       if (q == 0) {
-        BF_UNROLL for (int i = 0; i < N * N; ++i) { s.A[i] = e.A[i]; s.C[i] = e.C[i]; s.J[i] = e.J[i]; }
-        BF_UNROLL for (int i = 0; i < N; ++i) { s.b[i] = e.b[i]; s.eta[i] = e.eta[i]; }
+        BF_UNROLL for (int i = 0; i < PsSpan<N>::F; ++i) s.v[i] = e.v[i];
       } else {
         ps_combine<N>(s, e, s);
       }
     }
   }
-  ps_store_span<N>(agg, stride, g, s);
+  pscan_col_store<PsSpan<N>::F>(agg, B * NB, g, s.v);
 }
 
-// ---- launch 2: scan -----------------------------------------------------------------------------------------------------
+// ---- launch 2: scan (pscan_common.hpp) -----------------------------------------------------------------------------------
+// Span 0 has A = 0, eta = 0, J = 0 and maps any finite state to (b, C) exactly.  finish: the state is the filtered (m, P) at
+// the last step of block k; its prediction starts block k + 1.
 template <int N>
-__device__ __forceinline__ void ps_shfl_up_span(const PsSpan<N>& s, int off, PsSpan<N>& o) {
-  BF_UNROLL for (int e = 0; e < N * N; ++e) {
-    o.A[e] = __shfl_up(s.A[e], off, 64);
-    o.C[e] = __shfl_up(s.C[e], off, 64);
-    o.J[e] = __shfl_up(s.J[e], off, 64);
+struct PsScan {
+  using Span = PsSpan<N>;
+  static constexpr int STATE = ps_state_floats(N);
+  static constexpr int DIM = N;
+  static constexpr bool SUFFIX = false;
+  struct Args {
+    PsPredict<N> c;
+    const float* __restrict__ agg;
+    float* __restrict__ start;
+    long long col0, stride;   // b NB and B NB
+  };
+  static __device__ __forceinline__ void load(const Args& a, long long k, Span& s) {
+    pscan_col_load<Span::F>(a.agg, a.stride, a.col0 + k, s.v);
   }
-  BF_UNROLL for (int e = 0; e < N; ++e) {
-    o.b[e] = __shfl_up(s.b[e], off, 64);
-    o.eta[e] = __shfl_up(s.eta[e], off, 64);
+  static __device__ __forceinline__ void combine(const Span& i, const Span& j, Span& o) { ps_combine<N>(i, j, o); }
+  static __device__ __forceinline__ void apply(const Span& s, float* x) { ps_apply<N>(s, x); }
+  static __device__ __forceinline__ void finish(const Args& a, long long k, float* x) {
+    ps_predict<N>(a.c, x, x + N);
+    pscan_col_store<STATE>(a.start, a.stride, a.col0 + k + 1, x);
   }
-}
-
-// One workgroup (blockDim.x = 64 or 256) per trajectory.  lds: ps_scan_lds_floats<N>() floats (four wave totals, the running state).
-template <int N>
-constexpr int ps_scan_lds_floats() { return 4 * ps_agg_floats(N) + ps_start_floats(N); }
-
-template <int N, int M>
-__device__ __forceinline__ void ps_scan_body(const KFConst<N, M>& c, const float* __restrict__ agg, float* __restrict__ start,
-                                             long long B, long long NB, float* lds) {
-  constexpr int AGG = ps_agg_floats(N);
-  const long long b = blockIdx.x;
-  const long long stride = B * NB;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* tot = lds;             // [4][AGG]: the waves' totals of this tile
-  float* run = lds + 4 * AGG;   // the filtered state at the end of the previous tile
-  const long long nspan = NB - 1;   // spans k = 0 ... NB-2
-  // before the first tile there is no state; span 0 has A = 0, eta = 0, J = 0 and maps any finite state to (b, C) exactly
-  float gm[N], gP[N * N];
-  BF_UNROLL for (int i = 0; i < N; ++i) gm[i] = 0.f;
-  BF_UNROLL for (int i = 0; i < N * N; ++i) gP[i] = 0.f;
-
-  for (long long base = 0; base < nspan; base += blockDim.x) {
-    const long long k = base + tid;
-    const bool valid = k < nspan;
-    PsSpan<N> s;
-    ps_load_span<N>(agg, stride, b * NB + (valid ? k : nspan - 1), s);
-    if (!valid) {   // the identity span
-      BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = 0; j < N; ++j) {
-        s.A[i * N + j] = (i == j) ? 1.f : 0.f;
-        s.C[i * N + j] = 0.f;
-        s.J[i * N + j] = 0.f;
-      }
-      BF_UNROLL for (int i = 0; i < N; ++i) { s.b[i] = 0.f; s.eta[i] = 0.f; }
-    }
-    // inclusive scan of the wave's 64 spans
-#pragma unroll 1
-    for (int off = 1; off < 64; off <<= 1) {
-      PsSpan<N> p, r;
-      ps_shfl_up_span<N>(s, off, p);
-      ps_combine<N>(p, s, r);
-      const bool take = lane >= off;
-      BF_UNROLL for (int e = 0; e < N * N; ++e) {
-        s.A[e] = take ? r.A[e] : s.A[e];
-        s.C[e] = take ? r.C[e] : s.C[e];
-        s.J[e] = take ? r.J[e] : s.J[e];
-      }
-      BF_UNROLL for (int e = 0; e < N; ++e) {
-        s.b[e] = take ? r.b[e] : s.b[e];
-        s.eta[e] = take ? r.eta[e] : s.eta[e];
-      }
-    }
-    if (lane == 63) ps_store_span<N>(tot + wave * AGG, 1, 0, s);
-    __syncthreads();
-    // the filtered state in front of this wave: the running state through the totals of the waves before it
-    float m[N], P[N * N];
-    BF_UNROLL for (int i = 0; i < N; ++i) m[i] = gm[i];
-    BF_UNROLL for (int i = 0; i < N * N; ++i) P[i] = gP[i];
-#pragma unroll 1
-    for (int w = 0; w < wave; ++w) {
-      PsSpan<N> tw;
-      ps_load_span<N>(tot + w * AGG, 1, 0, tw);
-      ps_apply<N>(tw, m, P);
-    }
-    ps_apply<N>(s, m, P);   // filtered (m, P) at the last step of block k
-    __syncthreads();
-    if (tid == (int)blockDim.x - 1) {
-      BF_UNROLL for (int i = 0; i < N; ++i) run[i] = m[i];
-      BF_UNROLL for (int i = 0; i < N * N; ++i) run[N + i] = P[i];
-    }
-    if (valid) {
-      ps_predict<N, M>(c, m, P);
-      float* p = start + b * NB + k + 1;
-      BF_UNROLL for (int i = 0; i < N; ++i) p[(long long)i * stride] = m[i];
-      BF_UNROLL for (int i = 0; i < N * N; ++i) p[(long long)(N + i) * stride] = P[i];
-    }
-    __syncthreads();
-    BF_UNROLL for (int i = 0; i < N; ++i) gm[i] = run[i];
-    BF_UNROLL for (int i = 0; i < N * N; ++i) gP[i] = run[N + i];
-  }
-}
+};
 
 // ---- launch 3: emit -----------------------------------------------------------------------------------------------------
 template <int N, int M>
 __device__ __forceinline__ void ps_emit_body(const KFConst<N, M>& c, const CView& y, const CarryView& carry, const OutViews& out,
                                              const float* __restrict__ start, long long B, long long T, long long NB, int L) {
-  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = B * NB;
-  if (g >= stride) return;
-  const long long b = g / NB, k = g % NB;
-  float m[N], P[N * N];
+  long long g, b, k;
+  int j;
+  if (!pscan_lane(B, 1, NB, g, b, j, k)) return;
+  float x[ps_state_floats(N)], *m = x, *P = x + N;
   float w = carry.w_in ? carry.w_in[b] : 1.0f;
   if (k == 0) {
     BF_UNROLL for (int i = 0; i < N; ++i) m[i] = carry.m_in[b * N + i];
     BF_UNROLL for (int i = 0; i < N * N; ++i) P[i] = carry.P_in[b * N * N + i];
   } else {
-    const float* p = start + g;
-    BF_UNROLL for (int i = 0; i < N; ++i) m[i] = p[(long long)i * stride];
-    BF_UNROLL for (int i = 0; i < N * N; ++i) P[i] = p[(long long)(N + i) * stride];
+    pscan_col_load<ps_state_floats(N)>(start, B * NB, g, x);
     w = reweight_single(0.f, w);   // the weight after any earlier step: 1, or NaN for a carry weight that is not a positive number
   }
   const long long t0 = k * (long long)L;
@@ -402,7 +310,7 @@ __device__ __forceinline__ void ps_emit_body(const KFConst<N, M>& c, const CView
     if (out.ll.p) out.ll.p[b * out.ll.sB + t * out.ll.sT] = ll;
     if (out.m.p) BF_UNROLL for (int i = 0; i < N; ++i) out.m.p[b * out.m.sB + t * out.m.sT + i * out.m.sE] = m[i];
     if (out.P.p) BF_UNROLL for (int i = 0; i < N * N; ++i) out.P.p[b * out.P.sB + t * out.P.sT + i * out.P.sE] = P[i];
-    ps_predict<N, M>(c, m, P);
+    ps_predict<N>(c, m, P);
     if (out.pm.p) BF_UNROLL for (int i = 0; i < N; ++i) out.pm.p[b * out.pm.sB + t * out.pm.sT + i * out.pm.sE] = m[i];
     if (out.pP.p) BF_UNROLL for (int i = 0; i < N * N; ++i) out.pP.p[b * out.pP.sB + t * out.pP.sT + i * out.pP.sE] = P[i];
   }
@@ -418,11 +326,11 @@ __global__ void __launch_bounds__(64) kf_pscan_fold_kernel(PsConst<N, M> c, CVie
                                                            long long NB, int L) {
   ps_fold_body<N, M>(c, y, carry, agg, B, NB, L);
 }
-template <int N, int M>
-__global__ void __launch_bounds__(256) kf_pscan_scan_kernel(KFConst<N, M> c, const float* agg, float* start, long long B,
+template <int N>   // one workgroup per trajectory
+__global__ void __launch_bounds__(256) kf_pscan_scan_kernel(PsPredict<N> c, const float* agg, float* start, long long B,
                                                             long long NB) {
-  __shared__ float lds[ps_scan_lds_floats<N>()];
-  ps_scan_body<N, M>(c, agg, start, B, NB, lds);
+  __shared__ float lds[pscan_lds_floats<PsScan<N>>()];
+  pscan_scan<PsScan<N>>({c, agg, start, blockIdx.x * NB, B * NB}, NB, lds);
 }
 template <int N, int M>
 __global__ void __launch_bounds__(64) kf_pscan_emit_kernel(KFConst<N, M> c, CView y, CarryView carry, OutViews out,
@@ -521,18 +429,20 @@ static inline int launch_pscan_nm(const bf_lgssm* p, const bf_cstream* y, long l
   if (!ps_fill_const<N, M>(p, c))
     return set_error(BF_EUNSUPPORTED, "parallel kalman filter: S = H G Q G^T H^T + D R D^T is singular, the step element does not exist");
   auto [yv, cv, ov] = forward_views(y, carry, out);
-  const long long NB = (T + L - 1) / L;
-  const long long lanes = B * NB;
+  const PscanGeom g = pscan_geom(B, 1, T, L);
   float* agg = workspace;
-  float* start = workspace + lanes * ps_agg_floats(N);
-  const unsigned grid = (unsigned)((lanes + 63) / 64);
-  if (NB > 1) {
-    hipLaunchKernelGGL((kf_pscan_fold_kernel<N, M>), dim3(grid), dim3(64), 0, stream, c, yv, cv, agg, B, NB, L);
-    hipLaunchKernelGGL((kf_pscan_scan_kernel<N, M>), dim3((unsigned)B), dim3(NB - 1 <= 64 ? 64 : 256), 0, stream, c.kf,
-                       (const float*)agg, start, B, NB);
+  float* start = workspace + g.lanes * PsSpan<N>::F;
+  if (g.NB > 1) {
+    PsPredict<N> pc;
+    std::memcpy(pc.A, c.kf.A, sizeof(pc.A));
+    std::memcpy(pc.GQG, c.kf.GQG, sizeof(pc.GQG));
+    std::memcpy(pc.Gq0, c.kf.Gq0, sizeof(pc.Gq0));
+    hipLaunchKernelGGL((kf_pscan_fold_kernel<N, M>), dim3(g.grid), dim3(64), 0, stream, c, yv, cv, agg, B, g.NB, L);
+    hipLaunchKernelGGL((kf_pscan_scan_kernel<N>), dim3((unsigned)B), dim3(g.scan_threads), 0, stream, pc, (const float*)agg, start,
+                       B, g.NB);
   }
-  hipLaunchKernelGGL((kf_pscan_emit_kernel<N, M>), dim3(grid), dim3(64), 0, stream, c.kf, yv, cv, ov, (const float*)start, B, T,
-                     NB, L);
+  hipLaunchKernelGGL((kf_pscan_emit_kernel<N, M>), dim3(g.grid), dim3(64), 0, stream, c.kf, yv, cv, ov, (const float*)start, B, T,
+                     g.NB, L);
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;
 }

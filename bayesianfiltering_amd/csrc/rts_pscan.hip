@@ -7,62 +7,36 @@
 // both routes, builds without scratch.  Table per instance: DESIGN.md, section 6i.  n <= 6 is the parallel filter's limit
 // (kf_pscan.hip), whose streams this pass smooths.
 #include "backward_host.hpp"
+#include "pscan_host.hpp"
 
 namespace bf {
 
-#define BF_DECL(F_) \
-  int F_(const BackwardRoute& r, const RtsViews& v, long long B, long long T, float* workspace, int L, hipStream_t stream, bool* matched)
-BF_DECL(launch_rts_pscan_group_a);
-BF_DECL(launch_rts_pscan_group_b);
-BF_DECL(launch_rts_pscan_group_c);
-BF_DECL(launch_rts_pscan_group_d);
-#undef BF_DECL
+using RtsPscanGroup = int(const BackwardRoute& r, const RtsViews& v, long long B, long long T, float* workspace, int L,
+                          hipStream_t stream, bool* matched);
+RtsPscanGroup launch_rts_pscan_group_a, launch_rts_pscan_group_b, launch_rts_pscan_group_c, launch_rts_pscan_group_d;
 
-constexpr int PRS_N_MAX = 6;
-constexpr int PRS_L_MIN = 4, PRS_L_MAX = 4096;
+static const char NAME[] = "parallel rts smoother";
 
 static Option g_prs_block{0, OPT_PRS_BLOCK};   // 0 = from (B, T)
 Option& prs_block_option() { return g_prs_block; }
 
-int kf_pscan_default_block(long long B, long long T);   // kf_pscan.hip
-
-// Default block length: the parallel filter's rule for (B, T) -- the largest of ceil(B T / 65 536), the smallest s with
+// Default block length: kf_pscan_default_block(B, T), the parallel filter's rule -- the largest of ceil(B T / 65 536), the smallest s with
 // 50 s^2 >= T, and 16, at most 4096 --, kept after the sweep in profiles/parallel_smoother_probe.txt (n = 4): at B = 1, T = 10^6
 // the rule's L = 142 takes 0.833 ms (predictions given) / 0.750 ms (recomputed) where the best swept L takes 0.749 ms (L = 64) /
 // 0.703 ms (L = 128), L = 16 takes 1.985 / 1.873 ms and L = 1024 4.192 / 3.855 ms; at B = 64, T = 10^5 the rule's L = 98 is the
 // fastest recomputed and 5 % behind L = 256 given; at B = 1024, T = 10^4 its L = 157 is 23 % / 8 % behind the best fixed L.  The
 // combination has no solve, so the optimum sits somewhat below the filter's; at these margins one rule for both passes (one
 // workspace for parallel_kalman_smoother) is worth more than a second formula.  DESIGN.md, section 6i.
-int rts_pscan_default_block(long long B, long long T) { return kf_pscan_default_block(B, T); }
-
-// `block` = 0: the call option "prs_block", else the default for (B, T).  < 0: BF_E* (text set).
-static int resolve_block(long long B, long long T, int block) {
-  if (block == 0) block = g_prs_block.load();
-  if (block == 0) return rts_pscan_default_block(B, T);
-  if (block < PRS_L_MIN || block > PRS_L_MAX)
-    return set_error(BF_EINVAL, "parallel rts smoother: block length %d is outside %d..%d", block, PRS_L_MIN, PRS_L_MAX);
-  return block;
-}
-
-static int check_n(int n) {
-  if (n <= 0) return set_error(BF_EINVAL, "non-positive model dimension");
-  if (n > PRS_N_MAX)
-    return set_error(BF_EUNSUPPORTED, "parallel rts smoother: n=%d is not compiled in (register kernels for n = 1..%d, the parallel filter's limit)", n,
-                     PRS_N_MAX);
-  return BF_OK;
-}
 
 // 4 B ceil(T / L) (3 n^2 + 2 n) bytes: per (trajectory, block) one span (2 n^2 + n floats) and one start state (n^2 + n)
 long long rts_pscan_workspace_bytes(int n, long long B, long long T, int block) {
   if (B <= 0 || T <= 0) return set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", B, T);
-  const int rc = check_n(n);
+  const int rc = pscan_check_n(NAME, n);
   if (rc != BF_OK) return rc;
-  const int L = resolve_block(B, T, block);
+  const int L = resolve_block(NAME, g_prs_block, block, kf_pscan_default_block(B, T));
   if (L < 0) return L;
-  const long long NB = (T + L - 1) / L;
-  if ((double)B * (double)NB >= 2147483648.0)
-    return set_error(BF_EINVAL, "parallel rts smoother: B * ceil(T / block) = %lld * %lld must stay below 2^31", B, NB);
-  return 4LL * B * NB * (3LL * n * n + 2LL * n);
+  const long long NB = pscan_blocks(NAME, B, 0, T, L);
+  return NB < 0 ? NB : 4LL * B * NB * (3LL * n * n + 2LL * n);
 }
 
 int launch_rts_pscan(const bf_lgssm* model, const bf_out_desc* filtered, long long B, long long T, const bf_smooth_carry* carry,
@@ -70,7 +44,7 @@ int launch_rts_pscan(const bf_lgssm* model, const bf_out_desc* filtered, long lo
   if (!model || !filtered || !out || !workspace) return set_error(BF_EINVAL, "NULL argument");
   if (B <= 0 || T <= 0) return set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", B, T);
   int rc = backward_check_lgssm(model);
-  if (rc != BF_OK || (rc = check_n(model->n)) != BF_OK) return rc;
+  if (rc != BF_OK || (rc = pscan_check_n(NAME, model->n)) != BF_OK) return rc;
   if (model->Q_steps > 1)
     return set_error(BF_EUNSUPPORTED, "parallel rts smoother: constant Q only (Q_steps=%d)", model->Q_steps);
   const bool has_pm = filtered->pred_means.ptr != nullptr, has_pP = filtered->pred_covs.ptr != nullptr;
@@ -79,26 +53,19 @@ int launch_rts_pscan(const bf_lgssm* model, const bf_out_desc* filtered, long lo
   if (recompute && (rc = backward_check_recompute(model, T)) != BF_OK) return rc;
   RtsViews v;
   if ((rc = rts_views(filtered, carry, out, nullptr, false, v)) != BF_OK) return rc;
-  const int L = resolve_block(B, T, 0);
+  const int L = resolve_block(NAME, g_prs_block, 0, kf_pscan_default_block(B, T));
   if (L < 0) return L;
   const long long need = rts_pscan_workspace_bytes(model->n, B, T, L);
   if (need < 0) return (int)need;
-  if (workspace_bytes < need)
-    return set_error(BF_EINVAL, "parallel rts smoother: workspace of %lld bytes is too small: B=%lld, T=%lld, block=%d need %lld bytes (bf_rts_pscan_workspace_bytes)",
-                     workspace_bytes, B, T, L, need);
-  if (reinterpret_cast<uintptr_t>(workspace) % 4 != 0) return set_error(BF_EINVAL, "parallel rts smoother: workspace must be 4-byte aligned");
+  if ((rc = pscan_check_workspace(NAME, "bf_rts_pscan_workspace_bytes", workspace, workspace_bytes, need, B, T, 0, L)) != BF_OK)
+    return rc;
 
   BackwardRoute r;
   if ((rc = backward_route(model, recompute, r)) != BF_OK) return rc;
-  float* ws = static_cast<float*>(workspace);
-  bool matched = false;
-  rc = launch_rts_pscan_group_a(r, v, B, T, ws, L, stream, &matched);
-  if (matched) return rc;
-  rc = launch_rts_pscan_group_b(r, v, B, T, ws, L, stream, &matched);
-  if (matched) return rc;
-  rc = launch_rts_pscan_group_c(r, v, B, T, ws, L, stream, &matched);
-  if (matched) return rc;
-  rc = launch_rts_pscan_group_d(r, v, B, T, ws, L, stream, &matched);
+  RtsPscanGroup* const groups[] = {launch_rts_pscan_group_a, launch_rts_pscan_group_b, launch_rts_pscan_group_c,
+                                   launch_rts_pscan_group_d};
+  bool matched;
+  rc = pscan_run_groups(groups, &matched, r, v, B, T, static_cast<float*>(workspace), L, stream);
   if (matched) return rc;
   return set_error(BF_EUNSUPPORTED, "parallel rts smoother: n=%d is not compiled in", model->n);
 }

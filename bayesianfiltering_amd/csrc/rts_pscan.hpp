@@ -19,22 +19,17 @@
 //   m' = E m + g     P' = E P E^T + L   (symmetrised)
 // A smoothed state is itself the span (0, m, P); combining a span with it is exactly this rule and leaves E = 0.
 //
-// Three launches, no waiting between workgroups of any kind (no look-back, no flags, no grid synchronisation); NB = ceil(T / L):
-//   fold   one lane per (trajectory, block).  Blocks 1 ... NB-2 build their L elements and fold them (from the block's last
-//          step backwards) into the block aggregate of 2 n^2 + n floats; the last block runs the ordinary backward recursion
-//          from the call's end -- the carry if one is given, else m^s = m, P^s = P at T-1 -- and stores its smoothed first-step
-//          state as the span (0, m^s, P^s); block 0 needs no aggregate.  Workspace: span[e][b NB + k], the element index e
-//          outermost so that the lanes of a wave store (and the scan loads) consecutive addresses.
-//   scan   one workgroup per trajectory runs a suffix scan over the spans k = NB-1 ... 1, in tiles of one span per thread (64
-//          threads up to 65 blocks, else 256), thread r of a tile holding span NB-1-r: on these reversed indices the suffix
-//          scan is an inclusive scan by __shfl_up (wave64, six combinations), wave totals through LDS, the running smoothed
-//          state from tile to tile through LDS.  Every suffix ends at the terminal span, so it is a plain Gaussian: per block
-//          the scan writes only start[e][b NB + k], the smoothed state at the first step of block k, n + n^2 floats.
-//   emit   one lane per (trajectory, block) runs the ordinary rts_linearize / rts_step of rts_smoother.hpp backwards over its
-//          block.  The carry-in is start[k+1] for inner blocks and the call's carry, or none, for the last block.  It stores
-//          m^s, P^s and, when asked, C_t = G_t P^s_{t+1} through the strided views (any strides, both layouts); block 0 writes
-//          the carry-out.
-// NB = 1 is the emit launch alone.
+// Three launches, fold, scan and emit; the scheme and the scan are pscan_common.hpp's, here as a SUFFIX scan over NB = ceil(T / L):
+//   fold   blocks 1 ... NB-2 build their L elements and fold them (from the block's last step backwards) into the block
+//          aggregate of 2 n^2 + n floats; the last block runs the ordinary backward recursion from the call's end -- the carry if
+//          one is given, else m^s = m, P^s = P at T-1 -- and stores its smoothed first-step state as the span (0, m^s, P^s);
+//          block 0 needs no aggregate.  Workspace: span[e][b NB + k].
+//   scan   one workgroup per trajectory over the spans k = NB-1 ... 1.  Every suffix ends at the terminal span, so it is a
+//          plain Gaussian: per block the scan writes only start[e][b NB + k], the smoothed state at the first step of block k,
+//          n + n^2 floats.
+//   emit   the ordinary rts_linearize / rts_step of rts_smoother.hpp backwards over the block.  The carry-in is start[k+1] for
+//          inner blocks and the call's carry, or none, for the last block.  It stores m^s, P^s and, when asked,
+//          C_t = G_t P^s_{t+1} through the strided views (any strides, both layouts); block 0 writes the carry-out.
 //
 // Consequences.  Inside a block the outputs are the ordinary smoother's from that block's carry.  The last block equals
 // bf_rts_smoother_f32 on the same streams bit for bit, and with T <= L so does the whole call; elsewhere the two agree to fp32
@@ -49,86 +44,54 @@
 // Registers: every per-lane array is indexed by compile-time constants only (fully unrolled loops).  A combination holds
 // three spans of 2 n^2 + n floats: no scratch up to n = 6, the parallel filter's limit (table in DESIGN.md, section 6i).
 //
-// Block length: option "prs_block", else rts_pscan_default_block(B, T) in rts_pscan.hip -- the parallel filter's rule (the
+// Block length: option "prs_block", else kf_pscan_default_block(B, T) -- the parallel filter's rule (the
 // largest of ceil(B T / 65 536), the smallest s with 50 s^2 >= T, and 16; at most 4096), with the sweep behind it in
 // profiles/parallel_smoother_probe.txt.
 #pragma once
 #include "rts_smoother.hpp"
+#include "pscan_common.hpp"
+#include "pscan_host.hpp"
 
 namespace bf {
 
-// floats of one span and of one block-start state
-constexpr int prs_span_floats(int n) { return 2 * n * n + n; }
-constexpr int prs_start_floats(int n) { return n * n + n; }
-
+// E | g | L, the workspace's entry order
 template <int N>
 struct PrsSpan {
-  float E[N * N], g[N], L[N * N];
+  static constexpr int F = 2 * N * N + N;
+  float v[F];
+  __device__ float* E() { return v; }               __device__ const float* E() const { return v; }
+  __device__ float* g() { return v + N * N; }       __device__ const float* g() const { return v + N * N; }
+  __device__ float* L() { return v + N * N + N; }   __device__ const float* L() const { return v + N * N + N; }
 };
-
-template <int N>
-__device__ __forceinline__ void prs_symmetrise(float* a) {
-  BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = i + 1; j < N; ++j) {
-    const float s = 0.5f * (a[i * N + j] + a[j * N + i]);
-    a[i * N + j] = s;
-    a[j * N + i] = s;
-  }
-}
-
-// workspace <-> registers: entry e of lane g lives at ws[e * stride + g]
-template <int N>
-__device__ __forceinline__ void prs_load_span(const float* __restrict__ ws, long long stride, long long g, PrsSpan<N>& s) {
-  const float* p = ws + g;
-  BF_UNROLL for (int e = 0; e < N * N; ++e) s.E[e] = p[(long long)e * stride];
-  BF_UNROLL for (int e = 0; e < N; ++e) s.g[e] = p[(long long)(N * N + e) * stride];
-  BF_UNROLL for (int e = 0; e < N * N; ++e) s.L[e] = p[(long long)(N * N + N + e) * stride];
-}
-template <int N>
-__device__ __forceinline__ void prs_store_span(float* __restrict__ ws, long long stride, long long g, const PrsSpan<N>& s) {
-  float* p = ws + g;
-  BF_UNROLL for (int e = 0; e < N * N; ++e) p[(long long)e * stride] = s.E[e];
-  BF_UNROLL for (int e = 0; e < N; ++e) p[(long long)(N * N + e) * stride] = s.g[e];
-  BF_UNROLL for (int e = 0; e < N * N; ++e) p[(long long)(N * N + N + e) * stride] = s.L[e];
-}
+// a block-start state: m | P
+constexpr int prs_state_floats(int n) { return n + n * n; }
 
 // o = i (+) j, i the earlier span.  o may alias i or j: everything is read before the first write.
 template <int N>
 __device__ __forceinline__ void prs_combine(const PrsSpan<N>& i, const PrsSpan<N>& j, PrsSpan<N>& o) {
   float oE[N * N], og[N], oL[N * N], T1[N * N];
-  mm<N, N, N>(i.E, j.E, oE);
-  mv<N, N>(i.E, j.g, og);
-  mm<N, N, N>(i.E, j.L, T1);
-  mm_nt<N, N, N>(T1, i.E, oL);
-  BF_UNROLL for (int e = 0; e < N; ++e) og[e] += i.g[e];
-  BF_UNROLL for (int e = 0; e < N * N; ++e) oL[e] += i.L[e];
-  prs_symmetrise<N>(oL);
-  BF_UNROLL for (int e = 0; e < N * N; ++e) { o.E[e] = oE[e]; o.L[e] = oL[e]; }
-  BF_UNROLL for (int e = 0; e < N; ++e) o.g[e] = og[e];
+  mm<N, N, N>(i.E(), j.E(), oE);
+  mv<N, N>(i.E(), j.g(), og);
+  mm<N, N, N>(i.E(), j.L(), T1);
+  mm_nt<N, N, N>(T1, i.E(), oL);
+  BF_UNROLL for (int e = 0; e < N; ++e) og[e] += i.g()[e];
+  BF_UNROLL for (int e = 0; e < N * N; ++e) oL[e] += i.L()[e];
+  symmetrise<N>(oL);
+  BF_UNROLL for (int e = 0; e < N * N; ++e) { o.E()[e] = oE[e]; o.L()[e] = oL[e]; }
+  BF_UNROLL for (int e = 0; e < N; ++e) o.g()[e] = og[e];
 }
 
-// (m, P) <- the span s applied to the smoothed state (m, P)
+// x = (m | P) <- the span s applied to the smoothed state x
 template <int N>
-__device__ __forceinline__ void prs_apply(const PrsSpan<N>& s, float* m, float* P) {
+__device__ __forceinline__ void prs_apply(const PrsSpan<N>& s, float* x) {
+  float *m = x, *P = x + N;
   float om[N], T1[N * N];
-  mv<N, N>(s.E, m, om);
-  mm<N, N, N>(s.E, P, T1);
-  mm_nt<N, N, N>(T1, s.E, P);
-  BF_UNROLL for (int e = 0; e < N; ++e) m[e] = om[e] + s.g[e];
-  BF_UNROLL for (int e = 0; e < N * N; ++e) P[e] += s.L[e];
-  prs_symmetrise<N>(P);
-}
-
-// the filtered inputs of step t of trajectory b (the predictions only where the route reads them)
-template <int N, int KIND>
-__device__ __forceinline__ void prs_load_step(const RtsViews& v, long long b, long long t, float* m, float* P, float* mp,
-                                              float* Pp) {
-  auto ld = [&](const SView& s, int e) { return s.p[b * s.sB + t * s.sT + e * s.sE]; };
-  BF_UNROLL for (int i = 0; i < N; ++i) m[i] = ld(v.m, i);
-  BF_UNROLL for (int i = 0; i < N * N; ++i) P[i] = ld(v.P, i);
-  if constexpr (KIND != RTS_LIN_RECOMPUTE) {
-    BF_UNROLL for (int i = 0; i < N; ++i) mp[i] = ld(v.pm, i);
-    BF_UNROLL for (int i = 0; i < N * N; ++i) Pp[i] = ld(v.pP, i);
-  }
+  mv<N, N>(s.E(), m, om);
+  mm<N, N, N>(s.E(), P, T1);
+  mm_nt<N, N, N>(T1, s.E(), P);
+  BF_UNROLL for (int e = 0; e < N; ++e) m[e] = om[e] + s.g()[e];
+  BF_UNROLL for (int e = 0; e < N * N; ++e) P[e] += s.L()[e];
+  symmetrise<N>(P);
 }
 
 // The ordinary backward recursion of trajectory b over the steps t_hi ... t_lo from the smoothed state (ms, Ps) at t_hi + 1:
@@ -140,7 +103,7 @@ __device__ __forceinline__ void prs_walk(const RtsLin<N>& c, const RtsViews& v, 
   auto st = [&](const SView& s, long long t, int e, float x) { s.p[b * s.sB + t * s.sT + e * s.sE] = x; };
   for (long long t = t_hi; t >= t_lo; --t) {
     float m[N], P[NN], mp[N], Pp[NN], X[NN], C[NN];
-    prs_load_step<N, KIND>(v, b, t, m, P, mp, Pp);
+    pscan_load_step<N, KIND != RTS_LIN_RECOMPUTE>(v, b, t, m, P, mp, Pp);
     rts_linearize<N, KIND>(c, nullptr, t, 0.f, m, P, X, mp, Pp);
     rts_step<N>(X, P, m, mp, Pp, ms, Ps, C, STORE && want_c);
     if constexpr (STORE) {
@@ -178,146 +141,80 @@ template <int N, int KIND>
 __device__ __forceinline__ void prs_fold_body(const RtsLin<N>& c, const RtsViews& v, float* __restrict__ span, long long B,
                                               long long T, long long NB, int L) {
   constexpr int NN = N * N;
-  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = B * NB;
-  if (g >= stride) return;
-  const long long b = g / NB, k = g % NB;
+  long long g, b, k;
+  int j;
+  if (!pscan_lane(B, 1, NB, g, b, j, k)) return;
   if (k == 0) return;   // block 0 is only emitted
   const long long t0 = k * (long long)L;
   PrsSpan<N> s;
   if (k == NB - 1) {
     // the last block: the ordinary recursion from the call's end; its smoothed first-step state is the span (0, m^s, P^s)
-    const long long t_hi = prs_terminal<N, false>(v, b, T, s.g, s.L);
-    prs_walk<N, KIND, false>(c, v, b, t_hi, t0, false, s.g, s.L);
-    BF_UNROLL for (int e = 0; e < NN; ++e) s.E[e] = 0.f;
+    const long long t_hi = prs_terminal<N, false>(v, b, T, s.g(), s.L());
+    prs_walk<N, KIND, false>(c, v, b, t_hi, t0, false, s.g(), s.L());
+    BF_UNROLL for (int e = 0; e < NN; ++e) s.E()[e] = 0.f;
   } else {
     for (int q = L - 1; q >= 0; --q) {
       const long long t = t0 + q;
       // the element of step t: rts_step on the zero state leaves g_t, L_t in the carry and G_t^T in X
       PrsSpan<N> e;
       float m[N], P[NN], mp[N], Pp[NN], X[NN], C[NN];
-      prs_load_step<N, KIND>(v, b, t, m, P, mp, Pp);
+      pscan_load_step<N, KIND != RTS_LIN_RECOMPUTE>(v, b, t, m, P, mp, Pp);
       rts_linearize<N, KIND>(c, nullptr, t, 0.f, m, P, X, mp, Pp);
-      BF_UNROLL for (int i = 0; i < N; ++i) e.g[i] = 0.f;
-      BF_UNROLL for (int i = 0; i < NN; ++i) e.L[i] = 0.f;
-      rts_step<N>(X, P, m, mp, Pp, e.g, e.L, C, false);
-      prs_symmetrise<N>(e.L);
-      BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = 0; j < N; ++j) e.E[i * N + j] = X[j * N + i];
+      BF_UNROLL for (int i = 0; i < N; ++i) e.g()[i] = 0.f;
+      BF_UNROLL for (int i = 0; i < NN; ++i) e.L()[i] = 0.f;
+      rts_step<N>(X, P, m, mp, Pp, e.g(), e.L(), C, false);
+      symmetrise<N>(e.L());
+      BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = 0; j < N; ++j) e.E()[i * N + j] = X[j * N + i];
       if (q == L - 1) {
-        BF_UNROLL for (int i = 0; i < NN; ++i) { s.E[i] = e.E[i]; s.L[i] = e.L[i]; }
-        BF_UNROLL for (int i = 0; i < N; ++i) s.g[i] = e.g[i];
+        BF_UNROLL for (int i = 0; i < PrsSpan<N>::F; ++i) s.v[i] = e.v[i];
       } else {
         prs_combine<N>(e, s, s);
       }
     }
   }
-  prs_store_span<N>(span, stride, g, s);
+  pscan_col_store<PrsSpan<N>::F>(span, B * NB, g, s.v);
 }
 
-// ---- launch 2: scan -----------------------------------------------------------------------------------------------------
+// ---- launch 2: scan (pscan_common.hpp) -----------------------------------------------------------------------------------
+// Span NB-1 has E = 0 and maps any finite state to (g, L) exactly.  finish: the state is the smoothed (m, P) at the first step
+// of block k.
 template <int N>
-__device__ __forceinline__ void prs_shfl_up_span(const PrsSpan<N>& s, int off, PrsSpan<N>& o) {
-  BF_UNROLL for (int e = 0; e < N * N; ++e) {
-    o.E[e] = __shfl_up(s.E[e], off, 64);
-    o.L[e] = __shfl_up(s.L[e], off, 64);
+struct PrsScan {
+  using Span = PrsSpan<N>;
+  static constexpr int STATE = prs_state_floats(N);
+  static constexpr int DIM = N;
+  static constexpr bool SUFFIX = true;
+  struct Args {
+    const float* __restrict__ span;
+    float* __restrict__ start;
+    long long col0, stride;   // b NB and B NB
+  };
+  static __device__ __forceinline__ void load(const Args& a, long long k, Span& s) {
+    pscan_col_load<Span::F>(a.span, a.stride, a.col0 + k, s.v);
   }
-  BF_UNROLL for (int e = 0; e < N; ++e) o.g[e] = __shfl_up(s.g[e], off, 64);
-}
-
-// One workgroup (blockDim.x = 64 or 256) per trajectory.  lds: prs_scan_lds_floats<N>() floats (four wave totals, the running state).
-template <int N>
-constexpr int prs_scan_lds_floats() { return 4 * prs_span_floats(N) + prs_start_floats(N); }
-
-template <int N>
-__device__ __forceinline__ void prs_scan_body(const float* __restrict__ span, float* __restrict__ start, long long B, long long NB,
-                                              float* lds) {
-  constexpr int SPAN = prs_span_floats(N);
-  const long long b = blockIdx.x;
-  const long long stride = B * NB;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* tot = lds;              // [4][SPAN]: the waves' totals of this tile
-  float* run = lds + 4 * SPAN;   // the smoothed state at the first step of the previous tile's earliest block
-  const long long nspan = NB - 1;   // spans k = NB-1 ... 1 at the reversed indices r = NB-1-k = 0 ... NB-2
-  // after the first span there is no state; span NB-1 has E = 0 and maps any finite state to (g, L) exactly
-  float gm[N], gP[N * N];
-  BF_UNROLL for (int i = 0; i < N; ++i) gm[i] = 0.f;
-  BF_UNROLL for (int i = 0; i < N * N; ++i) gP[i] = 0.f;
-
-  for (long long base = 0; base < nspan; base += blockDim.x) {
-    const long long r = base + tid;
-    const bool valid = r < nspan;
-    const long long k = valid ? NB - 1 - r : 1;
-    PrsSpan<N> s;
-    prs_load_span<N>(span, stride, b * NB + k, s);
-    if (!valid) {   // the identity span
-      BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = 0; j < N; ++j) {
-        s.E[i * N + j] = (i == j) ? 1.f : 0.f;
-        s.L[i * N + j] = 0.f;
-      }
-      BF_UNROLL for (int i = 0; i < N; ++i) s.g[i] = 0.f;
-    }
-    // inclusive scan of the wave's 64 spans: thread r ends with span_k (+) span_{k+1} (+) ... up to the wave's first
-#pragma unroll 1
-    for (int off = 1; off < 64; off <<= 1) {
-      PrsSpan<N> p, q;
-      prs_shfl_up_span<N>(s, off, p);   // the spans of LATER blocks
-      prs_combine<N>(s, p, q);
-      const bool take = lane >= off;
-      BF_UNROLL for (int e = 0; e < N * N; ++e) {
-        s.E[e] = take ? q.E[e] : s.E[e];
-        s.L[e] = take ? q.L[e] : s.L[e];
-      }
-      BF_UNROLL for (int e = 0; e < N; ++e) s.g[e] = take ? q.g[e] : s.g[e];
-    }
-    if (lane == 63) prs_store_span<N>(tot + wave * SPAN, 1, 0, s);
-    __syncthreads();
-    // the smoothed state behind this wave: the running state through the totals of the waves before it
-    float m[N], P[N * N];
-    BF_UNROLL for (int i = 0; i < N; ++i) m[i] = gm[i];
-    BF_UNROLL for (int i = 0; i < N * N; ++i) P[i] = gP[i];
-#pragma unroll 1
-    for (int w = 0; w < wave; ++w) {
-      PrsSpan<N> tw;
-      prs_load_span<N>(tot + w * SPAN, 1, 0, tw);
-      prs_apply<N>(tw, m, P);
-    }
-    prs_apply<N>(s, m, P);   // smoothed (m, P) at the first step of block k
-    __syncthreads();
-    if (tid == (int)blockDim.x - 1) {
-      BF_UNROLL for (int i = 0; i < N; ++i) run[i] = m[i];
-      BF_UNROLL for (int i = 0; i < N * N; ++i) run[N + i] = P[i];
-    }
-    if (valid) {
-      float* p = start + b * NB + k;
-      BF_UNROLL for (int i = 0; i < N; ++i) p[(long long)i * stride] = m[i];
-      BF_UNROLL for (int i = 0; i < N * N; ++i) p[(long long)(N + i) * stride] = P[i];
-    }
-    __syncthreads();
-    BF_UNROLL for (int i = 0; i < N; ++i) gm[i] = run[i];
-    BF_UNROLL for (int i = 0; i < N * N; ++i) gP[i] = run[N + i];
+  static __device__ __forceinline__ void combine(const Span& i, const Span& j, Span& o) { prs_combine<N>(i, j, o); }
+  static __device__ __forceinline__ void apply(const Span& s, float* x) { prs_apply<N>(s, x); }
+  static __device__ __forceinline__ void finish(const Args& a, long long k, float* x) {
+    pscan_col_store<STATE>(a.start, a.stride, a.col0 + k, x);
   }
-}
+};
 
 // ---- launch 3: emit -----------------------------------------------------------------------------------------------------
 template <int N, int KIND>
 __device__ __forceinline__ void prs_emit_body(const RtsLin<N>& c, const RtsViews& v, const float* __restrict__ start, long long B,
                                               long long T, long long NB, int L) {
   constexpr int NN = N * N;
-  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = B * NB;
-  if (g >= stride) return;
-  const long long b = g / NB, k = g % NB;
+  long long g, b, k;
+  int j;
+  if (!pscan_lane(B, 1, NB, g, b, j, k)) return;
   const bool want_c = v.Cs.p != nullptr;
   const long long t0 = k * (long long)L;
-  float ms[N], Ps[NN];
+  float x[prs_state_floats(N)], *ms = x, *Ps = x + N;
   long long t_hi;
   if (k == NB - 1) {
     t_hi = prs_terminal<N, true>(v, b, T, ms, Ps);
   } else {
-    const float* p = start + g + 1;   // start[k + 1] of the same trajectory
-    BF_UNROLL for (int i = 0; i < N; ++i) ms[i] = p[(long long)i * stride];
-    BF_UNROLL for (int i = 0; i < NN; ++i) Ps[i] = p[(long long)(N + i) * stride];
+    pscan_col_load<prs_state_floats(N)>(start, B * NB, g + 1, x);   // start[k + 1] of the same trajectory
     t_hi = t0 + L - 1;
   }
   prs_walk<N, KIND, true>(c, v, b, t_hi, t0, want_c, ms, Ps);
@@ -332,10 +229,10 @@ __global__ void __launch_bounds__(64) rts_pscan_fold_kernel(RtsLin<N> c, RtsView
                                                             long long NB, int L) {
   prs_fold_body<N, KIND>(c, v, span, B, T, NB, L);
 }
-template <int N>
+template <int N>   // one workgroup per trajectory
 __global__ void __launch_bounds__(256) rts_pscan_scan_kernel(const float* span, float* start, long long B, long long NB) {
-  __shared__ float lds[prs_scan_lds_floats<N>()];
-  prs_scan_body<N>(span, start, B, NB, lds);
+  __shared__ float lds[pscan_lds_floats<PrsScan<N>>()];
+  pscan_scan<PrsScan<N>>({span, start, blockIdx.x * NB, B * NB}, NB, lds);
 }
 template <int N, int KIND>
 __global__ void __launch_bounds__(64) rts_pscan_emit_kernel(RtsLin<N> c, RtsViews v, const float* start, long long B, long long T,
@@ -347,17 +244,15 @@ __global__ void __launch_bounds__(64) rts_pscan_emit_kernel(RtsLin<N> c, RtsView
 template <int N, int KIND>
 static inline int launch_rts_pscan_n(const RtsLin<N>& c, const RtsViews& v, long long B, long long T, float* workspace, int L,
                                      hipStream_t stream) {
-  const long long NB = (T + L - 1) / L;
-  const long long lanes = B * NB;
+  const PscanGeom g = pscan_geom(B, 1, T, L);
   float* span = workspace;
-  float* start = workspace + lanes * prs_span_floats(N);
-  const unsigned grid = (unsigned)((lanes + 63) / 64);
-  if (NB > 1) {
-    hipLaunchKernelGGL((rts_pscan_fold_kernel<N, KIND>), dim3(grid), dim3(64), 0, stream, c, v, span, B, T, NB, L);
-    hipLaunchKernelGGL((rts_pscan_scan_kernel<N>), dim3((unsigned)B), dim3(NB - 1 <= 64 ? 64 : 256), 0, stream,
-                       (const float*)span, start, B, NB);
+  float* start = workspace + g.lanes * PrsSpan<N>::F;
+  if (g.NB > 1) {
+    hipLaunchKernelGGL((rts_pscan_fold_kernel<N, KIND>), dim3(g.grid), dim3(64), 0, stream, c, v, span, B, T, g.NB, L);
+    hipLaunchKernelGGL((rts_pscan_scan_kernel<N>), dim3((unsigned)B), dim3(g.scan_threads), 0, stream, (const float*)span, start,
+                       B, g.NB);
   }
-  hipLaunchKernelGGL((rts_pscan_emit_kernel<N, KIND>), dim3(grid), dim3(64), 0, stream, c, v, (const float*)start, B, T, NB, L);
+  hipLaunchKernelGGL((rts_pscan_emit_kernel<N, KIND>), dim3(g.grid), dim3(64), 0, stream, c, v, (const float*)start, B, T, g.NB, L);
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;
 }

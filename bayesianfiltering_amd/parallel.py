@@ -32,13 +32,17 @@ from .sampler import _sampler_front, _sampler_args
 from .smoother import _out_buffer, _smoothed_buffers, _smoothed_result
 
 
-def parallel_kalman_workspace_bytes(n: int, m: int, B: int, T: int, block=None) -> int:
-    """Bytes of device workspace a call with these sizes needs: ``4 B ceil(T / L) (4 n^2 + 3 n)``."""
-    lib = _lib.load()
-    need = lib.bf_kalman_pscan_workspace_bytes(n, m, B, T, int(block or 0))
+def _bytes(lib, family, *sizes, block=None) -> int:
+    """``bf_<family>_pscan_workspace_bytes(*sizes, block)``; a refusal raises with the library's text."""
+    need = getattr(lib, f"bf_{family}_pscan_workspace_bytes")(*sizes, int(block or 0))
     if need < 0:
         _lib.check(int(need))
     return int(need)
+
+
+def parallel_kalman_workspace_bytes(n: int, m: int, B: int, T: int, block=None) -> int:
+    """Bytes of device workspace a call with these sizes needs: ``4 B ceil(T / L) (4 n^2 + 3 n)``."""
+    return _bytes(_lib.load(), "kalman", n, m, B, T, block=block)
 
 
 def _workspace(workspace, need, dev):
@@ -50,6 +54,32 @@ def _workspace(workspace, need, dev):
             or not workspace.is_contiguous():
         raise ValueError(f"workspace must be a contiguous uint8 tensor on {dev}")
     return workspace
+
+
+def _run(lib, family, sizes, block, workspace, dev, options, option, call, stream=None, keep=()):
+    """The tail of a parallel call: the bytes these ``sizes`` need (refusals first), the workspace, ``option`` (the family's
+    block option) armed for this call only, ``call(pointer, bytes)``, and ``keep`` recorded on ``stream``."""
+    need = _bytes(lib, family, *sizes, block=block)
+    workspace = _workspace(workspace, need, dev)
+    _lib.arm_call_options(lib, {**(options or {}), option: int(block or 0)})   # tuning options for THIS call only (bf_set_call_option)
+    _lib.check(call(C.c_void_p(workspace.data_ptr()), workspace.numel()))
+    for t_ in keep:
+        t_.record_stream(stream)
+
+
+def _shared_workspace(params, emissions, kw, skw, other_bytes):
+    """The filter-then-backward wrappers' workspace, into ``skw``: ``workspace=``, or one allocation of the larger of the
+    filter's size and ``other_bytes(n, B, T, block)``.  Returns the filter's ``block`` and ``workspace`` keywords."""
+    torch = _torch()
+    block = kw.get("block")
+    if kw.get("workspace") is None:
+        shape = tuple(emissions.shape) if hasattr(emissions, "shape") else np.shape(emissions)
+        T, m = int(shape[-2]), int(shape[-1])
+        B = int(shape[0]) if len(shape) == 3 else 1
+        n = _param_dims(params)[0]
+        need = max(parallel_kalman_workspace_bytes(n, m, B, T, block), other_bytes(n, B, T, block))
+        skw["workspace"] = torch.empty(need, dtype=torch.uint8, device=kw.get("device", "cuda"))
+    return dict(block=block, workspace=skw["workspace"])
 
 
 def parallel_kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
@@ -65,30 +95,18 @@ def parallel_kalman_filter(params, emissions, *, initial_means=None, initial_cov
     when absent.  Its contents mean nothing before or after the call.
     Linear registry functions, constant Q and R, state dimension <= 6, emission dimension <= 4.
     """
-    torch = _torch()
     lib = _lib.require_gpu()
     k = _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
                      return_carry, device)
-    L = int(block or 0)
-    need = lib.bf_kalman_pscan_workspace_bytes(k.mdl.n, k.mdl.m, k.B, k.T, L)
-    if need < 0:
-        _lib.check(int(need))
-    workspace = _workspace(workspace, need, k.y.device)
-    opts = dict(options or {})
-    opts["pkf_block"] = L
-    _lib.arm_call_options(lib, opts)         # tuning options for THIS call only (bf_set_call_option)
-    _lib.check(lib.bf_kalman_filter_pscan_f32(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od),
-                                              C.c_void_p(workspace.data_ptr()), workspace.numel(), C.c_void_p(k.stream)))
+    _run(lib, "kalman", (k.mdl.n, k.mdl.m, k.B, k.T), block, workspace, k.y.device, options, "pkf_block",
+         lambda ws, size: lib.bf_kalman_filter_pscan_f32(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od),
+                                                         ws, size, C.c_void_p(k.stream)))
     return k.result()
 
 
 def parallel_rts_workspace_bytes(n: int, B: int, T: int, block=None) -> int:
     """Bytes of device workspace :func:`parallel_rts_smoother` needs at these sizes: ``4 B ceil(T / L) (3 n^2 + 2 n)``."""
-    lib = _lib.load()
-    need = lib.bf_rts_pscan_workspace_bytes(n, B, T, int(block or 0))
-    if need < 0:
-        _lib.check(int(need))
-    return int(need)
+    return _bytes(_lib.load(), "rts", n, B, T, block=block)
 
 
 def parallel_rts_smoother(params, posterior, *, carry=None, cross_covariances: bool = False, layout: str = "reference",
@@ -117,20 +135,10 @@ def parallel_rts_smoother(params, posterior, *, carry=None, cross_covariances: b
         raise ValueError("params.dynamics_function must be linear_dynamics for the parallel smoother")
     ms, Ps, Cs, sd, cr, keep, c_out = _smoothed_buffers(bw, out, carry, cross_covariances, layout, return_carry)
     mdl = _LinearDynamics(params, bw.f)
-    L = int(block or 0)
-    need = bw.lib.bf_rts_pscan_workspace_bytes(bw.n, bw.B, bw.T, L)
-    if need < 0:
-        _lib.check(int(need))
-    workspace = _workspace(workspace, need, bw.dev)
     cur = torch.cuda.current_stream(bw.dev)
-    opts = dict(options or {})
-    opts["prs_block"] = L
-    _lib.arm_call_options(bw.lib, opts)      # tuning options for THIS call only (bf_set_call_option)
-    _lib.check(bw.lib.bf_rts_smoother_pscan_f32(C.byref(mdl.c), C.byref(bw.fd), bw.B, bw.T, C.byref(cr), C.byref(sd),
-                                                C.c_void_p(workspace.data_ptr()), workspace.numel(),
-                                                C.c_void_p(cur.cuda_stream)))
-    for t_ in keep:
-        t_.record_stream(cur)
+    _run(bw.lib, "rts", (bw.n, bw.B, bw.T), block, workspace, bw.dev, options, "prs_block",
+         lambda ws, size: bw.lib.bf_rts_smoother_pscan_f32(C.byref(mdl.c), C.byref(bw.fd), bw.B, bw.T, C.byref(cr), C.byref(sd),
+                                                           ws, size, C.c_void_p(cur.cuda_stream)), cur, keep)
     return _smoothed_result(bw, ms, Ps, Cs, c_out, return_carry)
 
 
@@ -139,27 +147,14 @@ def parallel_kalman_smoother(params, emissions, **kw):
     path.  Keywords of the filter (``initial_means``, ``initial_covariances``, ``layout``, ``device``) go to the filter, the
     others to the smoother; ``block`` goes to both passes.  One workspace of the larger -- the filter's -- size is allocated
     once and handed to both (or ``workspace=`` is)."""
-    torch = _torch()
     fkw, skw = _wrapper_kw(params, kw, False)
-    block = kw.get("block")
-    if kw.get("workspace") is None:
-        shape = tuple(emissions.shape) if hasattr(emissions, "shape") else np.shape(emissions)
-        T, m = int(shape[-2]), int(shape[-1])
-        B = int(shape[0]) if len(shape) == 3 else 1
-        n = _param_dims(params)[0]
-        need = max(parallel_kalman_workspace_bytes(n, m, B, T, block), parallel_rts_workspace_bytes(n, B, T, block))
-        skw["workspace"] = torch.empty(need, dtype=torch.uint8, device=kw.get("device", "cuda"))
-    fkw["block"], fkw["workspace"] = block, skw["workspace"]
+    fkw.update(_shared_workspace(params, emissions, kw, skw, parallel_rts_workspace_bytes))
     return parallel_rts_smoother(params, parallel_kalman_filter(params, emissions, **fkw), **skw)
 
 
 def parallel_ffbs_workspace_bytes(n: int, B: int, T: int, S: int, block=None) -> int:
     """Bytes of device workspace :func:`parallel_posterior_sample` needs at these sizes: ``4 B ceil(T / L) (n^2 + 2 S n)``."""
-    lib = _lib.load()
-    need = lib.bf_ffbs_pscan_workspace_bytes(n, B, T, S, int(block or 0))
-    if need < 0:
-        _lib.check(int(need))
-    return int(need)
+    return _bytes(_lib.load(), "ffbs", n, B, T, S, block=block)
 
 
 def parallel_posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise=None, carry=None,
@@ -194,20 +189,10 @@ def parallel_posterior_sample(params, posterior, num_samples: int = 1, *, key=No
         raise ValueError(linear)
     xs, sd, cr, c_out, keep = _sampler_args(bw, S, key, noise, carry, return_carry, layout, out)
     mdl = _LinearDynamics(params, bw.f)
-    L = int(block or 0)
-    need = bw.lib.bf_ffbs_pscan_workspace_bytes(bw.n, bw.B, bw.T, S, L)
-    if need < 0:
-        _lib.check(int(need))
-    workspace = _workspace(workspace, need, bw.dev)
     cur = torch.cuda.current_stream(bw.dev)
-    opts = dict(options or {})
-    opts["pfs_block"] = L
-    _lib.arm_call_options(bw.lib, opts)      # tuning options for THIS call only (bf_set_call_option)
-    _lib.check(bw.lib.bf_ffbs_sample_pscan_f32(C.byref(mdl.c), C.byref(bw.fd), bw.B, bw.T, S, C.byref(cr), C.byref(sd),
-                                               C.c_void_p(workspace.data_ptr()), workspace.numel(),
-                                               C.c_void_p(cur.cuda_stream)))
-    for t_ in keep:
-        t_.record_stream(cur)
+    _run(bw.lib, "ffbs", (bw.n, bw.B, bw.T, S), block, workspace, bw.dev, options, "pfs_block",
+         lambda ws, size: bw.lib.bf_ffbs_sample_pscan_f32(C.byref(mdl.c), C.byref(bw.fd), bw.B, bw.T, S, C.byref(cr), C.byref(sd),
+                                                          ws, size, C.c_void_p(cur.cuda_stream)), cur, keep)
     res = xs[0] if bw.squeeze else xs
     return (res, c_out) if return_carry else res
 
@@ -217,16 +202,7 @@ def parallel_kalman_posterior_sample(params, emissions, num_samples, key, **kw):
     recompute path.  Keywords of the filter (``initial_means``, ``initial_covariances``, ``layout``, ``device``) go to the
     filter, the others to the sampler (``noise=`` among them: then ``key`` is None); ``block`` goes to both passes.  One
     workspace of the larger size is allocated once and handed to both (or ``workspace=`` is)."""
-    torch = _torch()
     fkw, skw = _wrapper_kw(params, kw, False)
-    block = kw.get("block")
-    if kw.get("workspace") is None:
-        shape = tuple(emissions.shape) if hasattr(emissions, "shape") else np.shape(emissions)
-        T, m = int(shape[-2]), int(shape[-1])
-        B = int(shape[0]) if len(shape) == 3 else 1
-        n = _param_dims(params)[0]
-        need = max(parallel_kalman_workspace_bytes(n, m, B, T, block),
-                   parallel_ffbs_workspace_bytes(n, B, T, int(num_samples), block))
-        skw["workspace"] = torch.empty(need, dtype=torch.uint8, device=kw.get("device", "cuda"))
-    fkw["block"], fkw["workspace"] = block, skw["workspace"]
+    fkw.update(_shared_workspace(params, emissions, kw, skw,
+                                 lambda n, B, T, block: parallel_ffbs_workspace_bytes(n, B, T, int(num_samples), block)))
     return parallel_posterior_sample(params, parallel_kalman_filter(params, emissions, **fkw), num_samples, key=key, **skw)

@@ -17,8 +17,8 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-5   # the project's standing fp32 tolerance
 MODELS = ["1x1", "2x2", "3x1", "4x2", "4x4", "bias", "5x2", "6x3"]   # every built n; 'bias': noise biases, dq = 2 < n = 4
 # (T, block): 301 blocks -- across a wave and a 256-thread tile, ragged last block of 3; 16 blocks inside one wave, ragged;
-# one block; one step
-SHAPES = [(1203, 4), (1000, 64), (37, 64), (1, 64)]
+# three blocks, one of them interior; two blocks, a scan over a single span; one block; one step
+SHAPES = [(1203, 4), (1000, 64), (12, 4), (8, 4), (37, 64), (1, 64)]
 B, TMAX = 3, 1203
 
 
