@@ -347,7 +347,7 @@ __device__ __forceinline__ void agsf_generic_body(const typename NODES::Model& p
       const float tot = block_tree_reduce<NW>(ew, red, [](float a, float c) { return a + c; });
       const float w = leaf_ok ? ew / tot : 0.f;
       // ---- jr.choice(PRNGKey(0), arange(M), (N0,), p = w) (:760), or utils.optimal_resampling (:1256)
-      const float cw = block_cumsum_assoc<NW>(w, red);
+      const float cw = block_cumsum_assoc<NW>(w, red + 16);
       scdf[l] = cw;
       lds_barrier();
       int idx = 0;

@@ -141,52 +141,9 @@ __device__ __forceinline__ void optimal_resampling_lanes(float w, int l, int MP,
 }
 
 
-// ---- the same building blocks for one trajectory per workgroup of NW waves (thread l = threadIdx.x holds element l of
-// MP = 64 NW; `red` is 64 floats of LDS scratch: [0, 16) reductions, [16, 32) scan totals, [32, 48) integer sums)
-template <int NW, class OP>
-__device__ __forceinline__ float block_tree_reduce(float v, float* red, OP op) {  // adjacent-pair tree over the 64 NW elements
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int off = 1; off < 64; off <<= 1) v = op(v, __shfl_xor(v, off, 64));
-  lds_barrier();
-  if (lane == 0) red[wave] = v;
-  lds_barrier();
-  float r = red[lane < NW ? lane : 0];
-  for (int off = 1; off < NW; off <<= 1) r = op(r, __shfl_xor(r, off, 64));
-  return __shfl(r, 0, 64);
-}
-// inclusive cumulative sum in lax.associative_scan order (Brent-Kung) over the 64 NW elements: wave up-sweep, scan of
-// the wave totals, wave down-sweep
-template <int NW>
-__device__ __forceinline__ float block_cumsum_assoc(float c, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  BF_UNROLL for (int d = 0; d < 6; ++d) {
-    const float o = __shfl_up(c, 1 << d, 64);
-    if (((lane + 1) & ((2 << d) - 1)) == 0) c += o;
-  }
-  lds_barrier();
-  if (lane == 63) red[16 + wave] = c;
-  lds_barrier();
-  float r = (lane < NW) ? red[16 + lane] : 0.f;
-  BF_UNROLL for (int d = 0; (1 << d) < NW; ++d) {
-    const float o = __shfl_up(r, 1 << d, 64);
-    if (lane < NW && ((lane + 1) & ((2 << d) - 1)) == 0) r += o;
-  }
-  BF_UNROLL for (int d = 4; d >= 1; --d) {
-    if ((1 << d) <= NW) {
-      const float o = __shfl_up(r, 1 << (d - 1), 64);
-      if (lane < NW && lane >= (1 << d) && ((lane + 1) & ((1 << d) - 1)) == (1 << (d - 1))) r += o;
-    }
-  }
-  const float mine = __shfl(r, wave, 64);
-  const float prev = __shfl(r, wave > 0 ? wave - 1 : 0, 64);
-  const float excl_wave = wave > 0 ? prev : 0.f;
-  if (lane == 63) c = mine;
-  BF_UNROLL for (int d = 6; d >= 1; --d) {
-    const float o = __shfl_up(c, 1 << (d - 1), 64);
-    if (((lane + 1) & ((1 << d) - 1)) == (1 << (d - 1))) c += (lane >= (1 << (d - 1))) ? o : excl_wave;
-  }
-  return c;
-}
+// ---- the same building blocks for one trajectory per workgroup of NW waves: block_tree_reduce and block_cumsum_assoc of
+// scan_common.hpp (thread l = threadIdx.x holds element l of MP = 64 NW; `red` is 64 floats of LDS scratch: [0, 16)
+// reductions, [16, 32) scan totals, [32, 48) integer sums)
 
 // optimal_resampling (utils.py:216-244) for M <= 64 NW weights held one per thread by a whole workgroup -- the reference's
 // own test runs augmented_gaussian_sum_filter_optimal on a [5, 5, 5] tree, 125 leaves (docs/tests/test_inference.py:89-92).
@@ -259,7 +216,7 @@ __device__ __forceinline__ void optimal_resampling_block(float w, int M, int N, 
   float rw = below ? sv : 0.f;
   const float tot = block_tree_reduce<NW>(rw, red, [](float a, float b) { return a + b; });
   rw = rw / tot;
-  const float c = block_cumsum_assoc<NW>(rw, red);
+  const float c = block_cumsum_assoc<NW>(rw, red + 16);
   s_b[l] = c;
   lds_barrier();
   const float ctot = s_b[M - 1];
@@ -337,8 +294,6 @@ agsf_scan_body(typename NODES::Arg mdl, CView y, UView uin, CarryView carry, Ags
   constexpr int REC = N + EP;  // one component record in LDS: mean, covariance
   constexpr int NT = NW == 1 ? 256 : 64 * NW;
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tpb = NT / MP;
   const int slot = tid / MP;       // trajectory slot in the workgroup
   const int l = tid % MP;          // leaf index
@@ -398,16 +353,10 @@ agsf_scan_body(typename NODES::Arg mdl, CView y, UView uin, CarryView carry, Ags
   auto seg_reduce = [&](float v, auto op) {  // over the MP leaves of the trajectory, adjacent-pair tree
     if constexpr (NW == 1) {
       for (int off = 1; off < MP; off <<= 1) v = op(v, __shfl_xor(v, off, 64));
+      return v;
     } else {
-      for (int off = 1; off < 64; off <<= 1) v = op(v, __shfl_xor(v, off, 64));
-      lds_barrier();
-      if (lane == 0) red[wave] = v;
-      lds_barrier();
-      float r = red[lane < NW ? lane : 0];
-      for (int off = 1; off < NW; off <<= 1) r = op(r, __shfl_xor(r, off, 64));
-      v = __shfl(r, 0, 64);
+      return block_tree_reduce<NW>(v, red, op);
     }
-    return v;
   };
 
   // observation and input of step t + 1 are fetched while step t runs (a load issued at the top of its own step would put
@@ -488,7 +437,7 @@ agsf_scan_body(typename NODES::Arg mdl, CView y, UView uin, CarryView carry, Ags
         }
       }
     } else {
-      c = block_cumsum_assoc<NW>(c, red);  // the same Brent-Kung order over 64 NW leaves
+      c = block_cumsum_assoc<NW>(c, red + 16);  // the same Brent-Kung order over 64 NW leaves
     }
     lds_barrier();  // previous step's readers of leafbuf / cdfbuf are done
     cdfbuf[tid] = c;

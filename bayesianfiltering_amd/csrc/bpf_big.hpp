@@ -7,13 +7,18 @@
 // resampling gather goes from one to the other); one 1024-thread workgroup per trajectory walks them
 // in chunks of 1024, so every reduction and the cumulative sum keep the binary-tree order of the small
 // kernel and of the oracle:
-//   * max / sum: adjacent-pair tree inside a chunk (xor butterfly, then across waves), then the same tree over
-//     the chunk results (N' = next_pow2 chunks, zero / -inf padded);
+//   * max / sum: adjacent-pair tree inside a chunk (block_tree_reduce of scan_common.hpp), then the same tree over
+//     the chunk results (chunks_reduce; N' = next_pow2 chunks, zero / -inf padded);
 //   * CDF = lax.associative_scan order (Brent-Kung) over N' elements: per chunk the up-sweep yields the chunk
-//     total; the totals are scanned by the same algorithm; then every chunk redoes its up-sweep and runs the
-//     down-sweep with the inclusive value at the end of the previous chunk as the element "before" it;
+//     total (block_total_assoc); the totals are scanned by the same algorithm; then every chunk redoes its up-sweep
+//     and runs the down-sweep with the inclusive value at the end of the previous chunk as the element "before" it
+//     (block_cumsum_assoc with a prefix);
 //   * inverse-CDF draw by binary search over the CDF in global memory, gather through global memory.
 // The workgroup of a trajectory is alone on its data: no grid-wide synchronisation, any batch size.
+//
+// The pieces that define a step's bits -- the collectives above, the particle at step 0, the ancestor draw, the key
+// chain, the reduction functors -- stand in front of the kernel; the workgroup-per-chunk kernels of bpf_wide.hpp are
+// written from the same ones.
 #pragma once
 #include "bpf_scan.hpp"
 
@@ -29,61 +34,85 @@ struct BigScratch {
 };
 
 constexpr int BIG_NT = 1024;       // threads per trajectory
+constexpr int BIG_NW = BIG_NT / 64;
 constexpr int BIG_MAXCH = 1024;    // chunks per trajectory (N <= 2^20)
 
-// Brent-Kung inclusive scan of one 1024-element chunk (thread tid holds v): `excl0` is the inclusive value at
-// the end of the previous chunk (the element "before" this one, 0 for the first chunk); when `fix_last`, the
-// chunk's last element is `incl_last` (the scanned chunk total).  red: 32 floats of LDS scratch.
-__device__ __forceinline__ float chunk_scan_bk(float v, float excl0, float incl_last, bool fix_last, float* red) {
+struct BpfAdd {
+  __device__ __forceinline__ float operator()(float a, float c) const { return a + c; }
+};
+struct BpfMax {
+  __device__ __forceinline__ float operator()(float a, float c) const { return nanmax(a, c); }
+};
+
+// the tree of block_tree_reduce continued over the chunk partials src[0 .. nchp) (LDS or global memory), nchp a power of
+// two <= 1024: one value per thread; the butterfly of the first nchp threads only pairs them among themselves.  The caller
+// orders the writers of src before the call.  red: 17 floats of LDS scratch.
+template <class OP>
+__device__ __forceinline__ float chunks_reduce(const float* src, int nchp, float* red, OP op) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  BF_UNROLL for (int d = 0; d < 6; ++d) {  // wave up-sweep
-    const float o = __shfl_up(v, 1 << d, 64);
-    if (((lane + 1) & ((2 << d) - 1)) == 0) v += o;
+  float v = src[tid < nchp ? tid : 0];
+  for (int off = 1; off < nchp && off < 64; off <<= 1) v = op(v, __shfl_xor(v, off, 64));
+  if (nchp > 64) {
+    lds_barrier();
+    if (lane == 0) red[wave] = v;
+    lds_barrier();
+    const int nw = nchp / 64;
+    float r = red[lane < nw ? lane : 0];
+    for (int off = 1; off < nw; off <<= 1) r = op(r, __shfl_xor(r, off, 64));
+    v = __shfl(r, 0, 64);
+  } else {
+    lds_barrier();
+    if (tid == 0) red[16] = v;
+    lds_barrier();
+    v = red[16];
   }
-  lds_barrier();
-  if (lane == 63) red[wave] = v;
-  lds_barrier();
-  float r = (lane < 16) ? red[lane] : 0.f;
-  BF_UNROLL for (int d = 0; d < 4; ++d) {  // up-sweep over the 16 wave totals
-    const float o = __shfl_up(r, 1 << d, 64);
-    if (lane < 16 && ((lane + 1) & ((2 << d) - 1)) == 0) r += o;
-  }
-  const float total = __shfl(r, 15, 64);  // chunk total (before any prefix)
-  if (fix_last && lane == 15) r = incl_last;
-  BF_UNROLL for (int d = 4; d >= 1; --d) {  // down-sweep over the wave totals; the node before wave 0 is excl0
-    const float o = __shfl_up(r, 1 << (d - 1), 64);
-    if (lane < 16 && ((lane + 1) & ((1 << d) - 1)) == (1 << (d - 1))) r += (lane >= (1 << d)) ? o : excl0;
-  }
-  const float mine = __shfl(r, wave, 64);
-  const float prev = __shfl(r, wave > 0 ? wave - 1 : 0, 64);
-  const float excl_wave = wave > 0 ? prev : excl0;
-  if (lane == 63) v = mine;
-  BF_UNROLL for (int d = 6; d >= 1; --d) {  // wave down-sweep (virtual lane -1 = excl_wave)
-    const float o = __shfl_up(v, 1 << (d - 1), 64);
-    if (((lane + 1) & ((1 << d) - 1)) == (1 << (d - 1))) v += (lane >= (1 << (d - 1))) ? o : excl_wave;
-  }
-  (void)total;
   return v;
 }
 
-// total of one chunk in the same up-sweep order (== the chunk's last scan element without prefix)
-__device__ __forceinline__ float chunk_total_bk(float v, float* red) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  BF_UNROLL for (int d = 0; d < 6; ++d) {
-    const float o = __shfl_up(v, 1 << d, 64);
-    if (((lane + 1) & ((2 << d) - 1)) == 0) v += o;
+// the key a trajectory starts from: its carried key, else the launch key
+__device__ __forceinline__ U32x2 bpf_start_key(const BpfCarry& carry, long long b, uint32_t key0, uint32_t key1) {
+  if (carry.key_in) return U32x2{carry.key_in[b * 2], carry.key_in[b * 2 + 1]};
+  return U32x2{key0, key1};
+}
+
+// particle i of trajectory b at step 0 and its weight: carried in, or drawn from the prior with key i + 1 of
+// split(k, NP + 1) (whose key 0 the caller then goes on with)
+template <int N, int DQ, int M>
+__device__ __forceinline__ void initial_particle(const BpfModel<N, DQ, M>* __restrict__ mdlp, const BpfCarry& carry, long long b, int i, int NP,
+                                                 U32x2 k, float* x, float* w) {
+  if (carry.x_in) {
+    BF_UNROLL for (int d = 0; d < N; ++d) x[d] = carry.x_in[(b * NP + i) * N + d];
+    *w = carry.w_in[b * NP + i];
+  } else {
+    draw_initial_particle<N, DQ, M>(mdlp, k.x, k.y, (uint32_t)i, (uint32_t)NP, x);
+    *w = 1.0f / (float)NP;
   }
-  lds_barrier();
-  if (lane == 63) red[wave] = v;
-  lds_barrier();
-  float r = (lane < 16) ? red[lane] : 0.f;
-  BF_UNROLL for (int d = 0; d < 4; ++d) {
-    const float o = __shfl_up(r, 1 << d, 64);
-    if (lane < 16 && ((lane + 1) & ((2 << d) - 1)) == 0) r += o;
+}
+
+// keys of a step that starts with key k: key 0 of split(k, NP + 1) (the particles' noise takes keys 1 .. NP), which a
+// step that resamples splits once more into the key of the ancestor draw and the next step's
+struct StepKeys {
+  U32x2 draw, next;
+};
+__device__ __forceinline__ StepKeys bpf_step_keys(uint32_t k0, uint32_t k1, int NP, bool do_resample) {
+  const U32x2 nk = threefry_split(k0, k1, 0u, (uint32_t)NP + 1u);
+  if (!do_resample) return StepKeys{nk, nk};
+  return StepKeys{threefry_split(nk.x, nk.y, 0u, 2u), threefry_split(nk.x, nk.y, 1u, 2u)};
+}
+
+// ancestor of particle i: systematic (resampler == 1) or multinomial position in [0, total], total = gc[NP - 1]; the first
+// index whose CDF value reaches it (searchsorted side='left' over gc[0 .. NP) in global memory), clamped to NP - 1
+__device__ __forceinline__ int draw_ancestor(U32x2 kc, int resampler, float total, const float* gc, int NP, int i) {
+  float r;
+  if (resampler == 1) r = (((float)i + bits_to_unit(threefry_bits(kc.x, kc.y, 0u, 1u))) / (float)NP) * total;
+  else r = total * (1.0f - bits_to_unit(threefry_bits(kc.x, kc.y, (uint32_t)i, (uint32_t)NP)));
+  int lo = 0, hi = NP;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (gc[mid] < r) lo = mid + 1; else hi = mid;
   }
-  return __shfl(r, 15, 64);
+  return lo < NP - 1 ? lo : NP - 1;
 }
 
 // one particle through the dynamics with its own noise draw (inference.py:1342-1345: q = q0 + chol(Q) z from the
@@ -104,14 +133,13 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
              BpfCarry carry, BpfOut out, BigScratch sc, long long B, long long T, int NP, float ess_threshold, int resampler,
              uint32_t key0, uint32_t key1) {
   const BpfModel<N, DQ, M>& mdl = *mdlp;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = threadIdx.x;
   const long long b = blockIdx.x;
   const int nch = (NP + BIG_NT - 1) / BIG_NT;
   int nchp = 1;
   while (nchp < nch) nchp <<= 1;
 
-  __shared__ float red[64];
+  __shared__ float red[64];           // [0, 16) scan totals, [32, 49) reductions
   __shared__ float cpart[BIG_MAXCH];  // per-chunk partial results (max / sums / CDF totals)
   float* xa = sc.xa + b * (long long)NP * N;
   float* xb = sc.xb + b * (long long)NP * N;
@@ -120,76 +148,16 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
   float* gc = sc.cdf + b * (long long)NP;
   int* ganc = sc.anc + b * (long long)NP;
 
-  auto block_reduce = [&](float v, auto op) {  // adjacent-pair tree over the 1024 values of a chunk
-    BF_UNROLL for (int off = 1; off < 64; off <<= 1) v = op(v, __shfl_xor(v, off, 64));
-    lds_barrier();
-    if (lane == 0) red[32 + wave] = v;
-    lds_barrier();
-    float r = red[32 + (lane < 16 ? lane : 0)];
-    BF_UNROLL for (int off = 1; off < 16; off <<= 1) r = op(r, __shfl_xor(r, off, 64));
-    return __shfl(r, 0, 64);
-  };
-  // the same tree continued over the chunk partials cpart[0 .. nchp), nchp a power of two <= 1024: one value per
-  // thread; the butterfly of the first nchp threads only pairs them among themselves
-  auto chunks_reduce = [&](auto op) {
-    lds_barrier();
-    float v = cpart[tid < nchp ? tid : 0];
-    for (int off = 1; off < nchp && off < 64; off <<= 1) v = op(v, __shfl_xor(v, off, 64));
-    if (nchp > 64) {
-      lds_barrier();
-      if (lane == 0) red[32 + wave] = v;
-      lds_barrier();
-      const int nw = nchp / 64;
-      float r = red[32 + (lane < nw ? lane : 0)];
-      for (int off = 1; off < nw; off <<= 1) r = op(r, __shfl_xor(r, off, 64));
-      v = __shfl(r, 0, 64);
-    } else {
-      lds_barrier();
-      if (tid == 0) red[48] = v;
-      lds_barrier();
-      v = red[48];
-    }
-    return v;
-  };
-  auto fadd = [](float a, float c) { return a + c; };
-
-  uint32_t k0, k1;
-  if (carry.key_in) {
-    k0 = carry.key_in[b * 2];
-    k1 = carry.key_in[b * 2 + 1];
-  } else {
-    k0 = key0;
-    k1 = key1;
-  }
   // ---- initial particles
-  if (carry.x_in) {
-    for (int i = tid; i < NP; i += BIG_NT) {
-      BF_UNROLL for (int d = 0; d < N; ++d) xa[(long long)i * N + d] = carry.x_in[(b * NP + i) * N + d];
-      gw[i] = carry.w_in[b * NP + i];
-    }
-  } else {
-    for (int i = tid; i < NP; i += BIG_NT) {
-      const U32x2 ki = threefry_split(k0, k1, (uint32_t)i + 1u, (uint32_t)NP + 1u);
-      float z[N];
-      BF_UNROLL for (int d = 0; d < N; ++d) z[d] = bits_to_normal(threefry_bits(ki.x, ki.y, (uint32_t)d, (uint32_t)N));
-      BF_UNROLL for (int d = 0; d < N; ++d) {
-        float s = 0.f;
-        BF_UNROLL for (int c = 0; c <= d; ++c) s = fmaf(mdl.L0[d * N + c], z[c], s);
-        xa[(long long)i * N + d] = mdl.m0[d] + s;
-      }
-      gw[i] = 1.0f / (float)NP;
-    }
-    const U32x2 nk = threefry_split(k0, k1, 0u, (uint32_t)NP + 1u);
-    k0 = nk.x;
-    k1 = nk.y;
-  }
+  U32x2 k = bpf_start_key(carry, b, key0, key1);
+  for (int i = tid; i < NP; i += BIG_NT) initial_particle<N, DQ, M>(mdlp, carry, b, i, NP, k, xa + (long long)i * N, gw + i);
+  if (!carry.x_in) k = threefry_split(k.x, k.y, 0u, (uint32_t)NP + 1u);
   __syncthreads();  // global-memory state written by other threads is read below
 
   for (long long t = 0; t < T; ++t) {
     float yv[M];
     BF_UNROLL for (int a = 0; a < M; ++a) yv[a] = y.p[b * y.sB + t * y.sT + a * y.sE];
     const float u0 = uptr ? uptr[b * u_sB + t * u_sT] : 0.f;
-    const U32x2 nk = threefry_split(k0, k1, 0u, (uint32_t)NP + 1u);
 
     // ---- pass 1: propagate, log-weight, chunk maxima
     for (int c = 0; c < nch; ++c) {
@@ -197,15 +165,16 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
       const bool valid = i < NP;
       float ll = -__builtin_inff();
       if (valid) {
-        const U32x2 ki = threefry_split(k0, k1, (uint32_t)i + 1u, (uint32_t)NP + 1u);
+        const U32x2 ki = threefry_split(k.x, k.y, (uint32_t)i + 1u, (uint32_t)NP + 1u);
         ll = propagate_particle<N, DQ, M, SP>(mdl, ki, xa + (long long)i * N, u0, yv);
         gl[i] = ll;
       }
-      const float cm = block_reduce(ll, nanmax);
+      const float cm = block_tree_reduce<BIG_NW>(ll, red + 32, BpfMax());
       if (tid == 0) cpart[c] = cm;
     }
     for (int c = nch + tid; c < nchp; c += BIG_NT) cpart[c] = -__builtin_inff();
-    const float mx = chunks_reduce(nanmax);
+    lds_barrier();
+    const float mx = chunks_reduce(cpart, nchp, red + 32, BpfMax());
 
     // ---- pass 2: unnormalised weights and their sum
     for (int c = 0; c < nch; ++c) {
@@ -216,12 +185,13 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
         e = canon_exp(gl[i] - mx) * gw[i];
         gl[i] = e;
       }
-      const float cs = block_reduce(e, fadd);
+      const float cs = block_tree_reduce<BIG_NW>(e, red + 32, BpfAdd());
       lds_barrier();
       if (tid == 0) cpart[c] = cs;
     }
     for (int c = nch + tid; c < nchp; c += BIG_NT) cpart[c] = 0.f;
-    const float tot = chunks_reduce(fadd);
+    lds_barrier();
+    const float tot = chunks_reduce(cpart, nchp, red + 32, BpfAdd());
 
     // ---- pass 3: normalise, effective sample size
     for (int c = 0; c < nch; ++c) {
@@ -233,22 +203,22 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
         gl[i] = wn;
         w2 = wn * wn;
       }
-      const float cs = block_reduce(w2, fadd);
+      const float cs = block_tree_reduce<BIG_NW>(w2, red + 32, BpfAdd());
       lds_barrier();
       if (tid == 0) cpart[c] = cs;
     }
     for (int c = nch + tid; c < nchp; c += BIG_NT) cpart[c] = 0.f;
-    const float ess = 1.0f / chunks_reduce(fadd);
+    lds_barrier();
+    const float ess = 1.0f / chunks_reduce(cpart, nchp, red + 32, BpfAdd());
     const bool do_resample = ess < ess_threshold * (float)NP;
+    const StepKeys sk = bpf_step_keys(k.x, k.y, NP, do_resample);
 
     float* xcur = xa;
     if (do_resample) {
-      const U32x2 kc = threefry_split(nk.x, nk.y, 0u, 2u);
-      const U32x2 kn = threefry_split(nk.x, nk.y, 1u, 2u);
       // ---- pass 4a: chunk totals of the normalised weights (up-sweep order)
       for (int c = 0; c < nch; ++c) {
         const int i = c * BIG_NT + tid;
-        const float ct = chunk_total_bk(i < NP ? gl[i] : 0.f, red);
+        const float ct = block_total_assoc<BIG_NW>(i < NP ? gl[i] : 0.f, red);
         lds_barrier();
         if (tid == 0) cpart[c] = ct;
       }
@@ -257,7 +227,7 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
       // scan of the chunk totals (nchp <= 1024 values, one per thread, same algorithm)
       {
         const float v = cpart[tid < nchp ? tid : 0];
-        const float sv = chunk_scan_bk(tid < nchp ? v : 0.f, 0.f, 0.f, false, red);
+        const float sv = block_cumsum_assoc<BIG_NW, true>(tid < nchp ? v : 0.f, red);
         lds_barrier();
         if (tid < nchp) cpart[tid] = sv;  // inclusive value at the end of chunk tid
         lds_barrier();
@@ -265,40 +235,27 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
       // ---- pass 4b: the CDF chunk by chunk, prefixed by the end of the previous chunk
       for (int c = 0; c < nch; ++c) {
         const int i = c * BIG_NT + tid;
-        const float excl0 = c > 0 ? cpart[c - 1] : 0.f;
-        const float cv = chunk_scan_bk(i < NP ? gl[i] : 0.f, excl0, cpart[c], true, red);
+        const float before = c > 0 ? cpart[c - 1] : 0.f;
+        const float cv = block_cumsum_assoc<BIG_NW, true>(i < NP ? gl[i] : 0.f, red, before, true, cpart[c]);
         if (i < NP) gc[i] = cv;
       }
       __syncthreads();  // the CDF is read by every thread below
-      // ---- pass 5: inverse-CDF draw (searchsorted side='left') and gather
+      // ---- pass 5: inverse-CDF draw and gather
       const float total = gc[NP - 1];
-      float u_sys = 0.f;
-      if (resampler == 1) u_sys = bits_to_unit(threefry_bits(kc.x, kc.y, 0u, 1u));
       for (int i = tid; i < NP; i += BIG_NT) {
-        float r;
-        if (resampler == 1) r = (((float)i + u_sys) / (float)NP) * total;
-        else r = total * (1.0f - bits_to_unit(threefry_bits(kc.x, kc.y, (uint32_t)i, (uint32_t)NP)));
-        int lo = 0, hi = NP;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (gc[mid] < r) lo = mid + 1; else hi = mid;
-        }
-        const int a = lo < NP - 1 ? lo : NP - 1;
+        const int a = draw_ancestor(sk.draw, resampler, total, gc, NP, i);
         ganc[i] = a;
         BF_UNROLL for (int d = 0; d < N; ++d) xb[(long long)i * N + d] = xa[(long long)a * N + d];
         gw[i] = 1.0f / (float)NP;
       }
       xcur = xb;
-      k0 = kn.x;
-      k1 = kn.y;
     } else {
       for (int i = tid; i < NP; i += BIG_NT) {
         gw[i] = gl[i];
         ganc[i] = i;
       }
-      k0 = nk.x;
-      k1 = nk.y;
     }
+    k = sk.next;
     __syncthreads();
 
     // ---- emit
@@ -316,7 +273,7 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
       for (int i = tid; i < NP; i += BIG_NT)
         BF_UNROLL for (int d = 0; d < N; ++d) part[d] = fmaf(gw[i], xcur[(long long)i * N + d], part[d]);
       BF_UNROLL for (int d = 0; d < N; ++d) {
-        const float s = block_reduce(part[d], fadd);
+        const float s = block_tree_reduce<BIG_NW>(part[d], red + 32, BpfAdd());
         if (tid == 0) out.mean[(b * T + t) * N + d] = s;
       }
     }
@@ -338,8 +295,8 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
     if (carry.w_out) carry.w_out[b * NP + i] = gw[i];
   }
   if (tid == 0 && carry.key_out) {
-    carry.key_out[b * 2] = k0;
-    carry.key_out[b * 2 + 1] = k1;
+    carry.key_out[b * 2] = k.x;
+    carry.key_out[b * 2 + 1] = k.y;
   }
 }
 
@@ -352,21 +309,34 @@ bpf_big_kernel(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float
 }
 
 #ifndef BF_JIT
-// launch preparation, shared with the kernel built at run time (bpf_scan.hip): the capacity check and the stream-ordered
-// scratch of a launch, carved from one allocation (*buf: the caller frees it on the stream after the launch)
-static inline int prepare_bpf_big(int n, long long B, int NP, hipStream_t stream, BigScratch& sc, float** buf) {
+// launch preparation of every particles-in-HBM kernel, the one built at run time (bpf_scan.hip) included: the capacity check
+// and the stream-ordered scratch of a launch, carved from one allocation (*buf: the caller frees it on the stream after the
+// launch) with `tail_bytes` left behind the BigScratch fields (*tail) for what a launcher adds
+static inline int prepare_bpf_big(int n, long long B, int NP, hipStream_t stream, BigScratch& sc, float** buf, size_t tail_bytes = 0,
+                                  void** tail = nullptr) {
   if (NP > BIG_NT * BIG_MAXCH)
     return set_error(BF_EUNSUPPORTED, "bootstrap particle filter: %d particles exceed the capacity of %d per trajectory", NP,
                      BIG_NT * BIG_MAXCH);
   const size_t per = (size_t)B * NP;
-  BF_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(buf), sizeof(float) * per * (2 * (size_t)n + 3) + sizeof(int) * per, stream));
+  BF_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(buf), sizeof(float) * per * (2 * (size_t)n + 3) + sizeof(int) * per + tail_bytes, stream));
   sc.xa = *buf;
   sc.xb = sc.xa + per * n;
   sc.w = sc.xb + per * n;
   sc.ll = sc.w + per;
   sc.cdf = sc.ll + per;
   sc.anc = reinterpret_cast<int*>(sc.cdf + per);
+  if (tail) *tail = sc.anc + per;
   return BF_OK;
+}
+
+// the observation and input arguments of the kernels, from the caller's descriptors (`u` NULL or u->ptr NULL: no inputs)
+struct BpfInputs {
+  CView y;
+  const float* u;
+  long long u_sB, u_sT;
+};
+static inline BpfInputs bpf_inputs(const bf_cstream* y, const bf_cstream* u) {
+  return BpfInputs{CView{y->ptr, y->sB, y->sT, y->sE}, (u && u->ptr) ? u->ptr : nullptr, u ? u->sB : 0, u ? u->sT : 0};
 }
 
 template <int N, int DQ, int M>
@@ -377,9 +347,9 @@ static inline int launch_bpf_big_dims(const BpfModel<N, DQ, M>* d_mdl, const bf_
   float* buf = nullptr;
   const int rc = prepare_bpf_big(N, B, NP, stream, sc, &buf);
   if (rc != BF_OK) return rc;
-  CView yv{y->ptr, y->sB, y->sT, y->sE};
-  hipLaunchKernelGGL((bpf_big_kernel<N, DQ, M>), dim3((unsigned)B), dim3(BIG_NT), 0, stream, d_mdl, yv, (u && u->ptr) ? u->ptr : nullptr,
-                     u ? u->sB : 0, u ? u->sT : 0, cr, out, sc, B, T, NP, ess, resampler, key[0], key[1]);
+  const BpfInputs in = bpf_inputs(y, u);
+  hipLaunchKernelGGL((bpf_big_kernel<N, DQ, M>), dim3((unsigned)B), dim3(BIG_NT), 0, stream, d_mdl, in.y, in.u, in.u_sB, in.u_sT, cr, out,
+                     sc, B, T, NP, ess, resampler, key[0], key[1]);
   const hipError_t le = hipGetLastError();
   const hipError_t fe = hipFreeAsync(buf, stream);
   BF_HIP_CHECK(le);

@@ -71,13 +71,11 @@ static int launch_bpf_jit(const bf_user_model* um, const bf_bpf_model* bp, const
     BigScratch sc;
     float* buf = nullptr;
     if ((rc = prepare_bpf_big(N, B, NP, stream, sc, &buf)) != BF_OK) return rc;
-    CView yv{y->ptr, y->sB, y->sT, y->sE};
-    const float* uptr = (u && u->ptr) ? u->ptr : nullptr;
-    long long u_sB = u ? u->sB : 0, u_sT = u ? u->sT : 0;
+    BpfInputs in = bpf_inputs(y, u);
     BpfCarry crv = cr;
     BpfOut ov = out;
     uint32_t k0 = key[0], k1 = key[1];
-    void* args[] = {&L.d_mdl, &yv, &uptr, &u_sB, &u_sT, &crv, &ov, &sc, &B, &T, &NP, &ess, &resampler, &k0, &k1};
+    void* args[] = {&L.d_mdl, &in.y, &in.u, &in.u_sB, &in.u_sT, &crv, &ov, &sc, &B, &T, &NP, &ess, &resampler, &k0, &k1};
     const hipError_t le = hipModuleLaunchKernel(fn, (unsigned)B, 1, 1, BIG_NT, 1, 1, 0, stream, args, nullptr);
     const hipError_t fe = hipFreeAsync(buf, stream);
     BF_HIP_CHECK(le);

@@ -1,6 +1,6 @@
-// Building blocks shared by the scan kernels (Kalman / Gaussian-sum): per-lane constant
-// selection, wave-level LDS ordering, LDS-DMA loads with counted waits, and the LDS tile that
-// transposes time for the reference output layout.
+// Building blocks shared by the scan kernels (Kalman / Gaussian-sum / particle): per-lane constant
+// selection, wave-level LDS ordering, LDS-DMA loads with counted waits, the workgroup-wide tree
+// reduction and Brent-Kung scan, and the LDS tile that transposes time for the reference output layout.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -71,6 +71,78 @@ __device__ __forceinline__ void wait_vm(int n) {
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
   }
 #undef BF_VMCASE
+}
+
+// ---------------------------------------------------------------------------------------
+// Workgroup-wide collectives over 64 NW elements, element l held by thread l = threadIdx.x: the adjacent-pair tree and the
+// lax.associative_scan (Brent-Kung) order that the particles-in-HBM particle filters (bpf_big.hpp, bpf_wide.hpp; NW = 16) and
+// the augmented Gaussian-sum filters (agsf_scan.hpp, agsf_generic_device.hpp) share, so one text defines the bits of all of
+// them.  Every thread of the workgroup calls them.  `red`: NW floats of LDS scratch; a collective writes it only behind a
+// barrier of its own, after every read of the one before, so consecutive collectives may use the same slot.
+template <int NW, class OP>
+__device__ __forceinline__ float block_tree_reduce(float v, float* red, OP op) {  // adjacent-pair tree over the 64 NW elements
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int off = 1; off < 64; off <<= 1) v = op(v, __shfl_xor(v, off, 64));
+  lds_barrier();
+  if (lane == 0) red[wave] = v;
+  lds_barrier();
+  float r = red[lane < NW ? lane : 0];
+  for (int off = 1; off < NW; off <<= 1) r = op(r, __shfl_xor(r, off, 64));
+  return __shfl(r, 0, 64);
+}
+// Brent-Kung up-sweep: the 64 elements of the wave (in place, in c), then the NW wave totals, which lane q < NW of every
+// wave returns up-swept (lane NW - 1: the block total)
+template <int NW>
+__device__ __forceinline__ float block_upsweep(float& c, float* red) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  BF_UNROLL for (int d = 0; d < 6; ++d) {
+    const float o = __shfl_up(c, 1 << d, 64);
+    if (((lane + 1) & ((2 << d) - 1)) == 0) c += o;
+  }
+  lds_barrier();
+  if (lane == 63) red[wave] = c;
+  lds_barrier();
+  float r = (lane < NW) ? red[lane] : 0.f;
+  BF_UNROLL for (int d = 0; (1 << d) < NW; ++d) {
+    const float o = __shfl_up(r, 1 << d, 64);
+    if (lane < NW && ((lane + 1) & ((2 << d) - 1)) == 0) r += o;
+  }
+  return r;
+}
+// total of the 64 NW elements in up-sweep order (== the last element of their inclusive scan)
+template <int NW>
+__device__ __forceinline__ float block_total_assoc(float c, float* red) {
+  return __shfl(block_upsweep<NW>(c, red), NW - 1, 64);
+}
+// inclusive cumulative sum in lax.associative_scan order (Brent-Kung) over the 64 NW elements: up-sweep, down-sweep over the
+// wave totals, wave down-sweep.  PREFIX: the block continues a longer scan -- `before` is the inclusive value of the element
+// in front of it (the node the down-sweep adds where the block has none) and, when `fix_last`, the block's last element is
+// `last` (its place in the scan of the block totals, known to the caller) instead of its own total.
+template <int NW, bool PREFIX = false>
+__device__ __forceinline__ float block_cumsum_assoc(float c, float* red, float before = 0.f, bool fix_last = false, float last = 0.f) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  float r = block_upsweep<NW>(c, red);
+  if (PREFIX && fix_last && lane == NW - 1) r = last;
+  BF_UNROLL for (int d = 4; d >= 1; --d) {
+    if ((1 << d) <= NW) {
+      const float o = __shfl_up(r, 1 << (d - 1), 64);
+      const bool node = lane < NW && ((lane + 1) & ((1 << d) - 1)) == (1 << (d - 1));
+      if constexpr (PREFIX) {
+        if (node) r += (lane >= (1 << d)) ? o : before;
+      } else {
+        if (node && lane >= (1 << d)) r += o;
+      }
+    }
+  }
+  const float mine = __shfl(r, wave, 64);
+  const float prev = __shfl(r, wave > 0 ? wave - 1 : 0, 64);
+  const float excl_wave = wave > 0 ? prev : (PREFIX ? before : 0.f);
+  if (lane == 63) c = mine;
+  BF_UNROLL for (int d = 6; d >= 1; --d) {  // (virtual lane -1 = excl_wave)
+    const float o = __shfl_up(c, 1 << (d - 1), 64);
+    if (((lane + 1) & ((1 << d) - 1)) == (1 << (d - 1))) c += (lane >= (1 << (d - 1))) ? o : excl_wave;
+  }
+  return c;
 }
 
 // ---------------------------------------------------------------------------------------

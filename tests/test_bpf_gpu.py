@@ -332,23 +332,12 @@ def test_particles_in_hbm_path(N, resampler):
     assert bool(np.isfinite(out["mean"].cpu().numpy()).all())
 
 
-@pytest.mark.parametrize("N,resampler,B", [(20000, "multinomial", 1), (17000, "systematic", 3), (70000, "multinomial", 2)])
-def test_workgroup_per_chunk_equals_workgroup_per_trajectory(N, resampler, B):
-    """The two particles-in-HBM kernels (bpf_big.hpp: a workgroup per trajectory; bpf_wide.hpp: a workgroup per
-    1024-particle chunk, six launches per step) keep the same reduction / scan trees: identical weights, particles,
-    ancestors, ESS and evidence over steps that do and do not resample, chunked runs through the carry included."""
+def _hbm_modes_agree(pp, ys, N, resampler, B):
+    """Both particles-in-HBM kernels (bpf_hbm_mode 1: a workgroup per trajectory, 2: a workgroup per chunk) on T = 6
+    observations `ys`, and the per-chunk one in two pieces through the carry: the streams that must be identical are.
+    Returns the per-trajectory kernel's output."""
     import bayesianfiltering_amd as bfa
     from bayesianfiltering_amd import _lib
-    nl = bfa.nonlinearities
-    T = 6
-    h = nl.linear_emission(np.eye(3, dtype=F32))
-    pp = bfa.ParamsBPF(np.array([0.0, 1.0, 1.05], F32), np.eye(3, dtype=F32), nl.lorenz63(), np.zeros(3, F32),
-                       0.1 * np.eye(3, dtype=F32), h, np.zeros(3, F32), 4.0 * np.eye(3, dtype=F32),
-                       nl.gaussian_log_prob(h, 4.0 * np.eye(3, dtype=F32)))
-    rng = np.random.default_rng(N)
-    ys = (np.array([0.0, 1.0, 1.05], F32) + rng.normal(size=(B, T, 3))).astype(F32)
-    if B == 1:
-        ys = ys[0]
     lib = _lib.load()
     outs = []
     try:
@@ -375,6 +364,59 @@ def test_workgroup_per_chunk_equals_workgroup_per_trajectory(N, resampler, B):
     assert np.array_equal(joined, b_["weights"])
     joined = np.concatenate([first["particles"].cpu().numpy(), second["particles"].cpu().numpy()], axis=t_axis if B == 1 else t_axis)
     assert np.array_equal(joined, b_["particles"])
+    return a
+
+
+@pytest.mark.parametrize("N,resampler,B", [(20000, "multinomial", 1), (17000, "systematic", 3), (70000, "multinomial", 2)])
+def test_workgroup_per_chunk_equals_workgroup_per_trajectory(N, resampler, B):
+    """The two particles-in-HBM kernels (bpf_big.hpp: a workgroup per trajectory; bpf_wide.hpp: a workgroup per
+    1024-particle chunk, six launches per step) keep the same reduction / scan trees: identical weights, particles,
+    ancestors, ESS and evidence over steps that do and do not resample, chunked runs through the carry included."""
+    import bayesianfiltering_amd as bfa
+    nl = bfa.nonlinearities
+    T = 6
+    h = nl.linear_emission(np.eye(3, dtype=F32))
+    pp = bfa.ParamsBPF(np.array([0.0, 1.0, 1.05], F32), np.eye(3, dtype=F32), nl.lorenz63(), np.zeros(3, F32),
+                       0.1 * np.eye(3, dtype=F32), h, np.zeros(3, F32), 4.0 * np.eye(3, dtype=F32),
+                       nl.gaussian_log_prob(h, 4.0 * np.eye(3, dtype=F32)))
+    rng = np.random.default_rng(N)
+    ys = (np.array([0.0, 1.0, 1.05], F32) + rng.normal(size=(B, T, 3))).astype(F32)
+    if B == 1:
+        ys = ys[0]
+    _hbm_modes_agree(pp, ys, N, resampler, B)
+
+
+@pytest.mark.parametrize("resampler,B", [("multinomial", 1), ("systematic", 3)])
+def test_workgroup_per_chunk_equals_workgroup_per_trajectory_four_particles_in_the_last_chunk(resampler, B):
+    """The same on the smallest shape that has every seam of the two kernels: N = 4100 particles are five chunks, padded
+    to eight for the trees, the last one with four live particles.  Lorenz-96 with n = dq = 6 observed through three
+    of its states (the compiled (6, 6, 3) instance; at n > 4 the in-register kernels end at 4096 particles, so mode 1 is
+    the per-trajectory kernel).  The observations come from the model itself, from seeds for which the oracle resamples
+    at some steps and not at others; the per-trajectory kernel's ancestors, weights, particles and ESS are the oracle's
+    bits (arith="canonical") as in test_particles_in_hbm_path."""
+    import bayesianfiltering_amd as bfa
+    nl = bfa.nonlinearities
+    N, T = 4100, 6
+    H = np.zeros((3, 6), F32)
+    H[0, 0] = H[1, 2] = H[2, 4] = 1.0
+    R, Q = 4.0 * np.eye(3, dtype=F32), 0.1 * np.eye(6, dtype=F32)
+    po = go.ParamsBPF(8 * np.ones(6, F32), np.eye(6, dtype=F32), om.Lorenz96(6), np.zeros(6, F32), Q, om.Linear(H),
+                      np.zeros(3, F32), R, go.GaussianEmissionLogProb(om.Linear(H), R))
+    h = nl.linear_emission(H)
+    pp = bfa.ParamsBPF(8 * np.ones(6, F32), np.eye(6, dtype=F32), nl.lorenz96(6), np.zeros(6, F32), Q, h,
+                       np.zeros(3, F32), R, nl.gaussian_log_prob(h, R))
+    ys = np.stack([go.sample_ssm(go.ParamsNLSSM(*po[:8]), otf.PRNGKey(3 + b), T)[1] for b in range(B)]).astype(F32)
+    a = _hbm_modes_agree(pp, ys if B > 1 else ys[0], N, resampler, B)
+    for b in range(B):
+        ref, dbg = go.bootstrap_particle_filter(po, ys[b], N, key=otf.PRNGKey(5), ess_threshold=0.6, resampler=resampler, debug=True,
+                                                arith="canonical")
+        got = {k: (v[b] if B > 1 else v) for k, v in a.items()}
+        res = np.asarray(dbg["resampled"])
+        assert 0 < res.sum() < res.size, res
+        assert np.array_equal(got["resampled"] > 0.5, res)
+        assert np.array_equal(got["ancestors"].T, np.asarray(dbg["ancestors"]))
+        assert _bits_equal(got["weights"], ref["weights"]) and _bits_equal(got["particles"], ref["particles"])
+        assert _bits_equal(got["ess"], np.asarray(dbg["ess"]))
 
 
 @pytest.mark.parametrize("N,n", [(64, 3), (300, 2), (5000, 3)])
