@@ -678,6 +678,42 @@ def systematic_indices(weights, u0):
     return np.minimum(np.searchsorted(cdf, pos.astype(F32), side="left"), N - 1).astype(np.int32)
 
 
+def draw_positions(weights, key, resampler):
+    """What a resampling step looks up: the canonical CDF of ``weights`` and the N positions r_i in it, from the key the
+    step resamples with (multinomial: c[-1] (1 - u_i); systematic: (i + u0) / N c[-1])."""
+    weights = np.asarray(weights, dtype=F32)
+    N = weights.shape[0]
+    k0 = tf.split(key, 2)[0]
+    cdf = tf.cumsum_assoc(weights)
+    if resampler == "multinomial":
+        r = (cdf[-1] * (F32(1.0) - tf.uniform(k0, N).astype(F32))).astype(F32)
+    else:
+        r = (((np.arange(N, dtype=F32) + F32(tf.uniform(k0, 1)[0])) / F32(N)).astype(F32) * cdf[-1]).astype(F32)
+    return cdf, r
+
+
+def ambiguous_draws(cdf, r):
+    """Mask of the positions whose ancestor the CDF alone does not define.  The fp32 CDF in associative-scan order is NOT
+    monotone (neighbouring prefixes are different roundings; weights below an ulp of the prefix leave inversions), and a
+    searchsorted over it returns the first index with c >= r only where {i: c_i < r} is a prefix: there every bisection agrees.
+    Where it is not, the answer depends on the probe sequence (NumPy's here, bpf_big.hpp and bpf_wide.hpp the same; the
+    in-register kernels probe power-of-two strides) -- all of them valid inverses within the CDF's rounding."""
+    cdf = np.asarray(cdf, dtype=F32)
+    first_ge = np.searchsorted(np.maximum.accumulate(cdf), r, side="left")
+    after_last_lt = np.searchsorted(np.minimum.accumulate(cdf[::-1])[::-1], r, side="left")
+    return first_ge != after_last_lt
+
+
+def _logz_f64(lls, weights):
+    """log sum_i w_i exp(ll_i) in float64 (log-sum-exp) of the fp32 log-densities and the previous step's weights."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        a = np.asarray(lls, dtype=np.float64) + np.log(np.asarray(weights, dtype=np.float64))
+        mx = np.max(a)
+        if not np.isfinite(mx):
+            return mx
+        return mx + np.log(np.sum(np.exp(a - mx)))
+
+
 def _bpf_canonical(params, emissions, num_particles, key, inputs, ess_threshold, resampler, debug):
     """inference.py:1302-1380 on the canonical fp32 arithmetic of oracle/fp32.py, vectorised over the particles: the
     operation sequence of the HIP engine's particle kernels, so that weights -- and with them every ancestor index of
@@ -703,7 +739,8 @@ def _bpf_canonical(params, emissions, num_particles, key, inputs, ess_threshold,
     out_w = np.empty((T, N), F32)
     out_x = np.empty((T, N, n), F32)
     dbg = {"resampled": np.zeros(T, bool), "ancestors": np.tile(np.arange(N, dtype=np.int32), (T, 1)),
-           "ess": np.zeros(T, F32), "pre_weights": np.empty((T, N), F32)}
+           "ess": np.zeros(T, F32), "pre_weights": np.empty((T, N), F32),
+           "logz": np.zeros(T, F32), "logz64": np.zeros(T), "mean64": np.zeros((T, n)), "ambiguous": np.zeros((T, N), bool)}
     for t in range(T):
         u, y = inputs[t], emissions[t]
         keys = tf.split(next_key, N + 1)                          # :1342
@@ -714,11 +751,16 @@ def _bpf_canonical(params, emissions, num_particles, key, inputs, ess_threshold,
         lls = lp.logprob_c(new_particles, y, u)                   # :1348-1349
         with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
             e = (fp32.canon_exp((lls - np.max(lls)).astype(F32)) * weights).astype(F32)   # :1350-1352
-            new_weights = (e / sum_f32(e)).astype(F32)            # :1353
+            tot = sum_f32(e)
+            new_weights = (e / tot).astype(F32)                   # :1353
             ess = F32(1.0) / sum_f32((new_weights * new_weights).astype(F32))
+            # the step's log-evidence log sum_i w_{t-1,i} p(y_t | x_i): the kernels' mx + canon_log(tot), defined to the bit
+            dbg["logz"][t] = F32(np.max(lls) + fp32.canon_log(tot)[0])
+            dbg["logz64"][t] = _logz_f64(lls, weights)
         dbg["ess"][t] = ess
         dbg["pre_weights"][t] = new_weights
         if ess < F32(ess_threshold) * F32(N):                    # :1356
+            dbg["ambiguous"][t] = ambiguous_draws(*draw_positions(new_weights, next_key, resampler))
             if resampler == "multinomial":
                 weights, new_particles, next_key, idx = _resample(new_weights, new_particles, next_key)
             else:
@@ -734,6 +776,7 @@ def _bpf_canonical(params, emissions, num_particles, key, inputs, ess_threshold,
         particles = new_particles
         out_w[t] = weights
         out_x[t] = particles
+        dbg["mean64"][t] = weights.astype(np.float64) @ particles.astype(np.float64)
     out = {"weights": out_w.swapaxes(0, 1).copy(), "particles": out_x.swapaxes(0, 1).copy()}
     return (out, dbg) if debug else out
 
@@ -742,7 +785,13 @@ def bootstrap_particle_filter(params, emissions, num_particles, key=None, inputs
                               ess_threshold=0.5, resampler="multinomial", debug=False, arith="libm"):
     """inference.py:1302-1380.  ``arith``: "libm" = NumPy's float32 functions and BLAS products (the reference leaves the
     rounding of exp / log1p / matrix products to XLA: any faithful choice is as good); "canonical" = the ONE definition of
-    oracle/fp32.py that the HIP engine also implements -- bit-exact ancestry (:func:`_bpf_canonical`)."""
+    oracle/fp32.py that the HIP engine also implements -- bit-exact ancestry (:func:`_bpf_canonical`).
+
+    ``debug=True`` also returns per step: ``resampled``, ``ancestors``, ``ess``, ``pre_weights`` (before the resampling
+    decision); ``logz`` (T,) fp32, the log-evidence log sum_i w_{t-1,i} p(y_t | x_i) as the kernels emit it (max + log of the
+    sum the weights are divided by: defined to the bit with arith="canonical"); ``logz64``, the float64 log-sum-exp of the same
+    fp32 log-densities; ``mean64`` (T, n), the float64 weighted mean of the emitted (post-resampling) particles; ``ambiguous``
+    (T, N), the draws of a resampling step that fall inside an inversion of the CDF (:func:`ambiguous_draws`)."""
     key = tf.PRNGKey(0) if key is None else np.asarray(key, dtype=np.uint32)
     if arith == "canonical":
         return _bpf_canonical(params, emissions, num_particles, key, inputs, ess_threshold, resampler, debug)
@@ -762,7 +811,8 @@ def bootstrap_particle_filter(params, emissions, num_particles, key=None, inputs
     out_w = np.empty((T, N), F32)
     out_x = np.empty((T, N, n), F32)
     dbg = {"resampled": np.zeros(T, bool), "ancestors": np.tile(np.arange(N, dtype=np.int32), (T, 1)),
-           "ess": np.zeros(T, F32), "pre_weights": np.empty((T, N), F32)}
+           "ess": np.zeros(T, F32), "pre_weights": np.empty((T, N), F32),
+           "logz": np.zeros(T, F32), "logz64": np.zeros(T), "mean64": np.zeros((T, n)), "ambiguous": np.zeros((T, N), bool)}
 
     for t in range(T):
         Qt = np.asarray(_get_params(params.dynamics_noise_covariance, 2, t), dtype=F32)
@@ -776,11 +826,15 @@ def bootstrap_particle_filter(params, emissions, num_particles, key=None, inputs
         lls = np.array([params.emission_distribution_log_prob(new_particles[i], y, u) for i in range(N)],
                        dtype=F32)                                 # :1348-1349
         new_weights = reweight(lls, weights)                     # :1350-1353
-        with np.errstate(invalid="ignore", divide="ignore"):
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
             ess = F32(1.0) / sum_f32((new_weights * new_weights).astype(F32))
+            mx = np.max(lls)
+            dbg["logz"][t] = F32(mx + np.log(sum_f32((np.exp((lls - mx).astype(F32)).astype(F32) * weights).astype(F32))))
+            dbg["logz64"][t] = _logz_f64(lls, weights)
         dbg["ess"][t] = ess
         dbg["pre_weights"][t] = new_weights
         if ess < F32(ess_threshold) * F32(N):                    # :1356
+            dbg["ambiguous"][t] = ambiguous_draws(*draw_positions(new_weights, next_key, resampler))
             if resampler == "multinomial":
                 weights, new_particles, next_key, idx = _resample(new_weights, new_particles, next_key)
             else:
@@ -796,6 +850,7 @@ def bootstrap_particle_filter(params, emissions, num_particles, key=None, inputs
         particles = new_particles
         out_w[t] = weights
         out_x[t] = particles
+        dbg["mean64"][t] = weights.astype(np.float64) @ particles.astype(np.float64)
 
     out = {"weights": out_w.swapaxes(0, 1).copy(), "particles": out_x.swapaxes(0, 1).copy()}
     return (out, dbg) if debug else out

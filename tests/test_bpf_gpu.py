@@ -53,6 +53,13 @@ def _bits_equal(a, b):
     return np.array_equal(np.ascontiguousarray(a, F32).view(np.uint32), np.ascontiguousarray(b, F32).view(np.uint32))
 
 
+def _route_options(N):
+    """Per-call options under which a call with few trajectories is run: as dispatched, and -- beyond 2048 particles, where
+    the default for B <= 32 is the workgroup-per-chunk kernels (bpf_scan.hpp: spread) -- also with bpf_hbm_mode = 1, the
+    workgroup-per-trajectory instance of the capacity."""
+    return [None, {"bpf_hbm_mode": 1}] if N > 2048 else [None]
+
+
 @pytest.mark.parametrize("op", [0, 1, 2])
 def test_device_canonical_arithmetic_equals_oracle_bit_for_bit(op):
     """canon_log / canon_exp / the bits -> normal map evaluated ON THE DEVICE (bf_canon_eval_f32) against oracle/fp32.py."""
@@ -105,7 +112,9 @@ def test_golden_lorenz63_fixture(golden_dir):
                                            (1024, "multinomial", 6), (4096, "multinomial", 30), (4096, "systematic", 6)])
 def test_lorenz96_ancestry_bit_exact(N, resampler, T):
     """n = 8, m = 4 Lorenz-96 with the g96lp log-density (gaussfiltax/nonlinearities.py:37-52), B = 2: the WHOLE ancestry
-    (inference.py:1350-1357, utils.py:207-214), every weight and every particle of every step equal to the oracle's bits."""
+    (inference.py:1350-1357, utils.py:207-214), every weight and every particle of every step equal to the oracle's bits.
+    N = 4096 with B = 2 goes to the workgroup-per-chunk kernels by default (bpf_scan.hpp: spread) and to the in-register 4x16
+    instance with options={"bpf_hbm_mode": 1}: both are run."""
     bfa, nl = _bfa()
     R = 0.5 * np.eye(4, dtype=F32)
     Q = 1e-1 * np.eye(8, dtype=F32)
@@ -116,15 +125,20 @@ def test_lorenz96_ancestry_bit_exact(N, resampler, T):
                        np.zeros(4, F32), R, nl.gaussian_log_prob(g96, R))
     ys = np.stack([go.sample_ssm(go.ParamsNLSSM(*po[:8]), otf.PRNGKey(b), T)[1] for b in range(2)])
     key = np.array([0, 11], np.uint32)
-    out = bfa.bootstrap_particle_filter(pp, ys, N, key, resampler=resampler, return_ancestors=True, output="both")
+    outs = [bfa.bootstrap_particle_filter(pp, ys, N, key, resampler=resampler, return_ancestors=True, output="both", options=o)
+            for o in _route_options(N)]
+    out = outs[0]
     for b in range(2):
         ref, dbg = go.bootstrap_particle_filter(po, ys[b], N, key=key, resampler=resampler, debug=True, arith="canonical")
         assert dbg["resampled"].any()
-        assert np.array_equal(out["resampled"][b].cpu().numpy() > 0.5, dbg["resampled"])
-        assert np.array_equal(out["ancestors"][b].cpu().numpy().T, dbg["ancestors"])
-        assert _bits_equal(out["weights"][b].cpu().numpy(), ref["weights"])
-        assert _bits_equal(out["particles"][b].cpu().numpy(), ref["particles"])
-        assert _bits_equal(out["ess"][b].cpu().numpy(), dbg["ess"])
+        for o in outs:
+            assert np.array_equal(o["resampled"][b].cpu().numpy() > 0.5, dbg["resampled"])
+            assert np.array_equal(o["ancestors"][b].cpu().numpy().T, dbg["ancestors"])
+            assert _bits_equal(o["weights"][b].cpu().numpy(), ref["weights"])
+            assert _bits_equal(o["particles"][b].cpu().numpy(), ref["particles"])
+            assert _bits_equal(o["ess"][b].cpu().numpy(), dbg["ess"])
+            assert _bits_equal(o["logz"][b].cpu().numpy(), dbg["logz"])
+            assert cm.rel_err(o["mean"][b].cpu().numpy(), dbg["mean64"]) < 1e-5
         # ... and the libm-arithmetic oracle (the reference leaves exp / log1p to XLA) agrees to rounding until a draw
         # of ITS run lands within an ulp of a CDF step
         ref0, dbg0 = go.bootstrap_particle_filter(po, ys[b], N, key=key, resampler=resampler, debug=True)
@@ -233,12 +247,16 @@ def test_bot_model_ancestry_bit_exact(N, resampler):
     key = np.array([0, 5], np.uint32)
     ref, dbg = go.bootstrap_particle_filter(po, ys, N, key=key, inputs=inputs.reshape(T, 1), resampler=resampler, debug=True,
                                             arith="canonical")
-    out = bfa.bootstrap_particle_filter(pp, ys, N, key, inputs, resampler=resampler, return_ancestors=True, output="both")
     assert dbg["resampled"].any()
-    assert np.array_equal(out["resampled"].cpu().numpy() > 0.5, dbg["resampled"])
-    assert np.array_equal(out["ancestors"].cpu().numpy().T, dbg["ancestors"])
-    assert _bits_equal(out["weights"].cpu().numpy(), ref["weights"])
-    assert _bits_equal(out["particles"].cpu().numpy(), ref["particles"])
+    for o in _route_options(N):      # (N = 4096: the workgroup-per-chunk kernels as dispatched, the in-register 4x16 instance with mode 1)
+        out = bfa.bootstrap_particle_filter(pp, ys, N, key, inputs, resampler=resampler, return_ancestors=True, output="both", options=o)
+        assert np.array_equal(out["resampled"].cpu().numpy() > 0.5, dbg["resampled"])
+        assert np.array_equal(out["ancestors"].cpu().numpy().T, dbg["ancestors"])
+        assert _bits_equal(out["weights"].cpu().numpy(), ref["weights"])
+        assert _bits_equal(out["particles"].cpu().numpy(), ref["particles"])
+        assert _bits_equal(out["ess"].cpu().numpy(), dbg["ess"])
+        assert _bits_equal(out["logz"].cpu().numpy(), dbg["logz"])
+        assert cm.rel_err(out["mean"].cpu().numpy(), dbg["mean64"]) < 1e-5
     # the libm-arithmetic oracle agrees to rounding
     ref0 = go.bootstrap_particle_filter(po, ys, N, key=key, inputs=inputs.reshape(T, 1), resampler=resampler)
     assert np.max(np.abs(out["weights"].cpu().numpy()[:, 0] - ref0["weights"][:, 0])) < 1e-6
@@ -259,7 +277,8 @@ def test_bpf_errors():
 
 def test_sixteen_thousand_particles_for_small_states():
     """N = 10 000 (the particle count of the reference's BOTExperiment notebook) on the manoeuvring-target
-    model: 16 particles per thread; weights, particles and ancestry against the oracle."""
+    model: weights, particles and ancestry against the oracle, on the workgroup-per-chunk kernels (one trajectory as
+    dispatched) and on the instance with 16 particles per thread (options={"bpf_hbm_mode": 1})."""
     import bayesianfiltering_amd as bfa
     nl = bfa.nonlinearities
     T, N = 6, 10000
@@ -301,6 +320,12 @@ def test_sixteen_thousand_particles_for_small_states():
     refc, dbgc = go.bootstrap_particle_filter(po, ys, N, key=key, inputs=inputs.reshape(T, 1), debug=True, arith="canonical")
     assert np.array_equal(anc, np.asarray(dbgc["ancestors"]).T)
     assert _bits_equal(out["weights"].cpu().numpy(), refc["weights"]) and _bits_equal(out["particles"].cpu().numpy(), refc["particles"])
+    reg = bfa.bootstrap_particle_filter(pp, ys, N, key, inputs, return_ancestors=True, output="both", options={"bpf_hbm_mode": 1})
+    assert np.array_equal(reg["ancestors"].cpu().numpy(), anc)
+    assert _bits_equal(reg["weights"].cpu().numpy(), refc["weights"]) and _bits_equal(reg["particles"].cpu().numpy(), refc["particles"])
+    assert np.array_equal(reg["resampled"].cpu().numpy() > 0.5, dbgc["resampled"])
+    assert _bits_equal(reg["ess"].cpu().numpy(), dbgc["ess"]) and _bits_equal(reg["logz"].cpu().numpy(), dbgc["logz"])
+    assert cm.rel_err(reg["mean"].cpu().numpy(), dbgc["mean64"]) < 1e-5
 
 
 @pytest.mark.parametrize("N,resampler", [(20000, "multinomial"), (17000, "systematic"), (70000, "multinomial")])
@@ -364,6 +389,9 @@ def _hbm_modes_agree(pp, ys, N, resampler, B):
     assert np.array_equal(joined, b_["weights"])
     joined = np.concatenate([first["particles"].cpu().numpy(), second["particles"].cpu().numpy()], axis=t_axis if B == 1 else t_axis)
     assert np.array_equal(joined, b_["particles"])
+    for k in ("mean", "ess", "logz", "resampled"):           # ... and the summaries' bits (time is their first axis after the batch's)
+        joined = np.concatenate([first[k].cpu().numpy(), second[k].cpu().numpy()], axis=0 if B == 1 else 1)
+        assert _bits_equal(joined, b_[k]), k
     return a
 
 
@@ -499,13 +527,16 @@ def test_compile_time_model_instance_equals_the_run_time_one(n, N):
     pp = bfa.ParamsBPF(8 * np.ones(n, F32), np.eye(n, dtype=F32), nl.lorenz96(n), q0, Q, g, r0, R, nl.gaussian_log_prob(g, R, r0))
     ys = cm.device_observations(bfa.ParamsNLSSM(*pp[:8]), (n, n, m, m), B, T, seed=n).cpu().numpy()
     key = np.array([3, 7], np.uint32)
+    # (beyond 2048 particles three trajectories would go to the workgroup-per-chunk kernels, which have the run-time structure
+    # only: bpf_hbm_mode = 1 keeps the call on the in-register instance that this test is about)
+    opts = {"bpf_hbm_mode": 1} if N > 2048 else None
     res = {}
     for spec in (1, 0):
         _lib.check(lib.bf_set_option(b"bpf_spec", spec))
         try:
-            res[spec] = bfa.bootstrap_particle_filter(pp, ys, N, key, output="both", return_ancestors=True, return_carry=True)
-            h1, c1 = bfa.bootstrap_particle_filter(pp, ys[:, :4], N, key, output="both", return_carry=True)
-            h2, c2 = bfa.bootstrap_particle_filter(pp, ys[:, 4:], N, None, output="both", carry=c1, return_carry=True)
+            res[spec] = bfa.bootstrap_particle_filter(pp, ys, N, key, output="both", return_ancestors=True, return_carry=True, options=opts)
+            h1, c1 = bfa.bootstrap_particle_filter(pp, ys[:, :4], N, key, output="both", return_carry=True, options=opts)
+            h2, c2 = bfa.bootstrap_particle_filter(pp, ys[:, 4:], N, None, output="both", carry=c1, return_carry=True, options=opts)
             for k in ("weights", "particles", "mean", "ess", "logz", "resampled"):
                 tdim = 2 if k in ("weights", "particles") else 1
                 assert torch.equal(torch.cat([h1[k], h2[k]], dim=tdim), res[spec][0][k]), (spec, k)     # chunked == one-shot

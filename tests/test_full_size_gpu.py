@@ -289,10 +289,13 @@ def test_cfg1_single_trajectory_T1000():
 
 
 def test_cfg4_instance_n16_N4096_against_oracle():
-    """configs[3]'s kernel instance itself -- bpf_scan_kernel<16,16,8,4,16>: Lorenz-96 n = 16, m = 8, N = 4 096 particles
-    (inference.py:1330-1377) -- against oracle.bootstrap_particle_filter on B = 2 trajectories, T = 12: resampling decisions,
-    ancestors, weights, particles and the ESS BIT FOR BIT (canonical arithmetic, oracle/fp32.py), and the libm-arithmetic
-    oracle to rounding on the first steps."""
+    """configs[3]'s kernel instance itself -- bpf_scan_kernel<16,16,8,4,16> with the model structure at compile time, which
+    B = 2 trajectories reach only with options={"bpf_hbm_mode": 1} -- and what the default dispatch runs for so few
+    trajectories, the workgroup-per-chunk kernels of bpf_wide.hpp: Lorenz-96 n = 16, m = 8, N = 4 096 particles
+    (inference.py:1330-1377) against oracle.bootstrap_particle_filter, T = 12: resampling decisions, ancestors, weights,
+    particles, the ESS and the log-evidence BIT FOR BIT (canonical arithmetic, oracle/fp32.py), the mean to 1e-5 of the
+    oracle's float64 mean, and the libm-arithmetic oracle to rounding on the first steps.  The two routes sum the mean in
+    different orders: its bits differ, which is the one sign of the route in the outputs."""
     import bayesianfiltering_amd as bfa
     from oracle import threefry as otf
     nl = bfa.nonlinearities
@@ -306,20 +309,25 @@ def test_cfg4_instance_n16_N4096_against_oracle():
                        nl.gaussian_log_prob(g, R))
     ys = np.stack([go.sample_ssm(go.ParamsNLSSM(*po[:8]), otf.PRNGKey(40 + b), T)[1] for b in range(2)])
     key = np.array([0, 1], np.uint32)
-    out = bfa.bootstrap_particle_filter(pp, ys, N, key, output="both", return_ancestors=True)
+    outs = {mode: bfa.bootstrap_particle_filter(pp, ys, N, key, output="both", return_ancestors=True, options=opts)
+            for mode, opts in (("in-register", {"bpf_hbm_mode": 1}), ("default", None))}
+    bits = lambda v: np.ascontiguousarray(v, F32).view(np.uint32)
     for b in range(2):
         ref, dbg = go.bootstrap_particle_filter(po, ys[b], N, key=key, debug=True, arith="canonical")
-        assert np.array_equal(out["resampled"][b].cpu().numpy() > 0.5, dbg["resampled"])
         assert dbg["resampled"].any()
-        assert np.array_equal(out["ancestors"][b].cpu().numpy().T, dbg["ancestors"])          # bit-exact ancestry, all steps
-        bits = lambda v: np.ascontiguousarray(v, F32).view(np.uint32)
-        assert np.array_equal(bits(out["weights"][b].cpu().numpy()), bits(ref["weights"]))
-        assert np.array_equal(bits(out["particles"][b].cpu().numpy()), bits(ref["particles"]))
-        assert np.array_equal(bits(out["ess"][b].cpu().numpy()), bits(dbg["ess"]))
-        if b == 0:      # the libm-arithmetic oracle on the first steps: weights 1e-6, particles 1e-5
-            ref0 = go.bootstrap_particle_filter(po, ys[b, :2], N, key=key)
-            assert cm.rel_err(out["particles"][b].cpu().numpy()[:, :2], ref0["particles"]) < 1e-5
-            assert np.max(np.abs(out["weights"][b].cpu().numpy()[:, :2] - ref0["weights"])) < 1e-6
+        ref0 = go.bootstrap_particle_filter(po, ys[b, :2], N, key=key) if b == 0 else None
+        for mode, out in outs.items():
+            assert np.array_equal(out["resampled"][b].cpu().numpy() > 0.5, dbg["resampled"]), mode
+            assert np.array_equal(out["ancestors"][b].cpu().numpy().T, dbg["ancestors"]), mode    # bit-exact ancestry, all steps
+            assert np.array_equal(bits(out["weights"][b].cpu().numpy()), bits(ref["weights"])), mode
+            assert np.array_equal(bits(out["particles"][b].cpu().numpy()), bits(ref["particles"])), mode
+            assert np.array_equal(bits(out["ess"][b].cpu().numpy()), bits(dbg["ess"])), mode
+            assert np.array_equal(bits(out["logz"][b].cpu().numpy()), bits(dbg["logz"])), mode
+            assert cm.rel_err(out["mean"][b].cpu().numpy(), dbg["mean64"]) < 1e-5, mode
+            if b == 0:      # the libm-arithmetic oracle on the first steps: weights 1e-6, particles 1e-5
+                assert cm.rel_err(out["particles"][b].cpu().numpy()[:, :2], ref0["particles"]) < 1e-5
+                assert np.max(np.abs(out["weights"][b].cpu().numpy()[:, :2] - ref0["weights"])) < 1e-6
+    assert not np.array_equal(bits(outs["default"]["mean"].cpu().numpy()), bits(outs["in-register"]["mean"].cpu().numpy()))
 
 
 def test_cfg5_two_trajectories_T2000_against_oracle():
