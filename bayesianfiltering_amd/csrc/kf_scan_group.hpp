@@ -49,6 +49,8 @@ struct KFConst {
   float Dr0[M];      // H_r r0
 };
 
+// (tests/test_kalman_staged_cpu.py restates the tile geometry below -- and Tile's TS / CH / POW2 in scan_common.hpp -- and
+// pins these lines as text: a change here goes with a change of _group_cfg and of the table in tests/kalman_staged_cases.py)
 template <int NS, int M, int NL>
 struct GroupCfg {
   static_assert((NL & (NL - 1)) == 0 && NL >= 1 && NL <= 64, "lanes per trajectory must be a power of two");

@@ -1,6 +1,10 @@
 """Every compiled (state_dim, obs_dim) instance of the Kalman and Gaussian-sum kernels against the oracle, at ragged
 sizes: odd batch, T not a multiple of the time tile, non-square noise maps, biases.  (The other test files go deep on a
-few shapes; this one makes sure no instance of the dispatch tables is left unexercised.)  Tolerance 1e-5 relative."""
+few shapes; this one makes sure no instance of the dispatch tables is left unexercised.)  Tolerance 1e-5 relative.
+
+The Kalman batches here (B = 7 + n) are smaller than one wave of every instance, and launch_nml sends fewer than CPW
+trajectories to the strided kernel: this file exercises the STRIDED kernel of every instance.  The LDS-staged emitter of every
+instance, the route any batch of a wave or more takes, is covered by tests/test_kalman_staged_gpu.py."""
 import numpy as np
 import pytest
 

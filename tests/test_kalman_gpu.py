@@ -84,18 +84,21 @@ def test_chunked_carry_equals_one_shot():
 
 
 def test_time_varying_covariances():
-    a = cm.cv_model_arrays()
-    B, T = 8, 32
-    ys = cm.simulate_batch(a, B, T, seed=9)
-    rng = np.random.default_rng(0)
-    a = dict(a)
-    a["Q"] = (a["Q"][None] * (1 + rng.random((T, 1, 1)))).astype(np.float32)
-    a["R"] = (a["R"][None] * (1 + rng.random((T, 1, 1)))).astype(np.float32)
-    init = np.tile(a["m0"], (B, 1))
-    ref = cm.oracle_kalman_batch(a, ys, init)
-    post = _run(a, ys, init, "reference")
-    for k in FIELDS:
-        assert cm.rel_err(getattr(post, k).cpu().numpy(), ref[k]) < TOL, k
+    """B = 8 is less than a wave (32 trajectories at two lanes each): the strided kernel reads the per-step tables.  B = 70 is
+    two whole waves for the LDS-staged kernel (forced: a layout it cannot take would be refused) and a tail of 6."""
+    T = 32
+    for B, mode in ((8, -1), (70, 2)):
+        a = cm.cv_model_arrays()
+        ys = cm.simulate_batch(a, B, T, seed=9)
+        rng = np.random.default_rng(0)
+        a = dict(a)
+        a["Q"] = (a["Q"][None] * (1 + rng.random((T, 1, 1)))).astype(np.float32)
+        a["R"] = (a["R"][None] * (1 + rng.random((T, 1, 1)))).astype(np.float32)
+        init = np.tile(a["m0"], (B, 1))
+        ref = cm.oracle_kalman_batch(a, ys, init)
+        post = _run(a, ys, init, "reference", mode)
+        for k in FIELDS:
+            assert cm.rel_err(getattr(post, k).cpu().numpy(), ref[k]) < TOL, (B, k)
 
 
 def test_errors_are_loud():
