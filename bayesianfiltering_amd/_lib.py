@@ -160,6 +160,8 @@ SYMBOLS = {
     "bf_random_split": (C.c_int, [C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_uint32)]),
     "bf_kalman_filter_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
                                        C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
+    "bf_kalman_filter_missing_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
+                                               C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
     "bf_kalman_pscan_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
     "bf_kalman_filter_pscan_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
                                              C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p, C.c_int64, C.c_void_p]),

@@ -26,6 +26,10 @@ int set_error(int code, const char* fmt, ...) {
 int launch_kf_group(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
                     const bf_out_desc* out, hipStream_t stream, int force_mode, int lanes);
 
+int kf_missing_default_lanes(int n, int m);  // kf_scan_group.hip: 0 = the pair has no missing-observation instance
+int launch_kf_missing_group(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
+                            const bf_out_desc* out, hipStream_t stream, int force_mode, int lanes);
+
 int launch_kf_mfma(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
                    const bf_out_desc* out, hipStream_t stream, int K, bool multi, int dyn_kind, const float* dth);
 int launch_kf_bf32(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry, const bf_out_desc* out,
@@ -235,6 +239,29 @@ int bf_kalman_filter_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, 
     return bf::with_generic_fallback(bf::launch_kf_mfma(model, y, B, T, carry, out, hs, 1, false, 0, nullptr), generic);
   return bf::with_generic_fallback(
       bf::launch_kf_group(model, y, B, T, carry, out, hs, bf::g_kf_emit_mode.load(), bf::g_kf_lanes.load()), generic);
+}
+
+int bf_kalman_filter_missing_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T, const bf_carry* carry,
+                                 const bf_out_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  if (!model || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
+  if (out->coll_mean.ptr || out->coll_cov.ptr)
+    return bf::set_error(BF_EUNSUPPORTED, "kalman filter with missing observations: collapsed streams are not produced (with one component they equal means / covs)");
+  if (int rc; (rc = bf::check_lgssm(model)) || (rc = bf::check_streams(y, carry))) return rc;
+  // the register kernels only: no matrix-core or run-time-dimension instance takes gaps
+  if (model->n > 8 || model->m > 4)
+    return bf::set_error(BF_EUNSUPPORTED, "kalman filter with missing observations: n <= 8 and m <= 4 only (n=%d, m=%d)", (int)model->n,
+                         (int)model->m);
+  const int lanes = bf::g_kf_lanes.load();
+  const int have = bf::kf_missing_default_lanes(model->n, model->m);
+  if (have == 0)
+    return bf::set_error(BF_EUNSUPPORTED, "kalman filter with missing observations: (n=%d, m=%d) is not compiled in (n = 1..8 with m = 1..min(n,4))",
+                         (int)model->n, (int)model->m);
+  if (lanes != 0 && lanes != have)
+    return bf::set_error(BF_EUNSUPPORTED, "kalman filter with missing observations: kf_lanes=%d has no instance at (n=%d, m=%d); the compiled one is %d (or 0)",
+                         lanes, (int)model->n, (int)model->m, have);
+  return bf::launch_kf_missing_group(model, y, B, T, carry, out, static_cast<hipStream_t>(stream), bf::g_kf_emit_mode.load(), lanes);
 }
 
 int64_t bf_kalman_pscan_workspace_bytes(int32_t n, int32_t m, int64_t B, int64_t T, int32_t block) {

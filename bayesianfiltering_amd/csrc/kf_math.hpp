@@ -173,6 +173,100 @@ __device__ __forceinline__ float condition_on(const float* Hx, const float* HrRH
   return mvn_logpdf_chol<M>(S, v);
 }
 
+// ---- Missing observations: the update on the sub-model of the observed components o (obs[a] true), embedded in the full
+// M x M system so that every loop keeps its compile-time bounds and lanes with different patterns stay convergent.
+// The caller hands in the EMBEDDED quantities: v[a] = 0 and row a of the right-hand sides = 0 for a missing a, and S with
+// row and column a overwritten by e_a.  That matrix is a permutation of blockdiag(S_oo, I): partial pivoting meets zeros
+// below and beside a missing diagonal 1 and picks the pivots of the reduced system in the observed block, every elimination
+// against a missing row has multiplier 0, and the Cholesky factor's missing rows are e_a (d = 1) -- the reduced model's
+// arithmetic plus exact zeros.
+
+// Solve for X with entry (i, j) of the matrix = S + 1e-6 where both components are observed and the embedded S (1 on the
+// diagonal, 0 off it) elsewhere.
+template <int M, int C>
+__device__ __forceinline__ void psd_solve_masked(const float* S /* embedded */, float* X /* in: Bm, out: X */, const bool* obs,
+                                                 float jitter = 1e-6f) {
+  float a[M * M];
+  BF_UNROLL for (int i = 0; i < M; ++i) BF_UNROLL for (int j = 0; j < M; ++j)
+      a[i * M + j] = (obs[i] && obs[j]) ? S[i * M + j] + jitter : S[i * M + j];
+  psd_solve<M, C>(a, X, 0.0f);
+}
+
+// log N(v_o; 0, S_oo) from the embedded S and v: mvn_logpdf_chol with |o| in the log 2 pi term (the missing rows add
+// z = 0 to the quadratic form and d = 1 to the determinant).  |o| = 0 gives 0.
+template <int M>
+__device__ __forceinline__ float mvn_logpdf_chol_masked(const float* S /* embedded */, const float* v, const bool* obs) {
+  float L[M * M];
+  float rd[M];
+  float dprod = 1.0f;
+  BF_UNROLL for (int j = 0; j < M; ++j) {
+    float d = S[j * M + j];
+    BF_UNROLL for (int k = 0; k < j; ++k) d = fmaf(-L[j * M + k], L[j * M + k], d);
+    d = fast_sqrt(d);
+    L[j * M + j] = d;
+    dprod *= d;
+    const float inv = fast_rcp(d);
+    rd[j] = inv;
+    BF_UNROLL for (int i = j + 1; i < M; ++i) {
+      float s = S[i * M + j];
+      BF_UNROLL for (int k = 0; k < j; ++k) s = fmaf(-L[i * M + k], L[j * M + k], s);
+      L[i * M + j] = s * inv;
+    }
+  }
+  float quad = 0.f;
+  float z[M];
+  float cnt = 0.f;
+  BF_UNROLL for (int i = 0; i < M; ++i) {
+    float s = v[i];
+    BF_UNROLL for (int j = 0; j < i; ++j) s = fmaf(-L[i * M + j], z[j], s);
+    z[i] = s * rd[i];
+    quad = fmaf(z[i], z[i], quad);
+    cnt += obs[i] ? 1.0f : 0.0f;
+  }
+  constexpr float kLog2Pi = 1.8378770664093453f;
+  return -0.5f * quad - 0.5f * cnt * kLog2Pi - fast_log(dprod);
+}
+
+// condition_on with missing components: y[a] NaN = not observed.  mu = h(m) (the predicted observation); an observed
+// component that is not finite poisons as in condition_on.  Nothing observed: m and P unchanged, log-likelihood 0.
+template <int N, int M>
+__device__ __forceinline__ float condition_on_masked(const float* Hx, const float* HrRHr, const float* y, const float* mu,
+                                                     float* m, float* P) {
+  bool obs[M];
+  float v[M];
+  BF_UNROLL for (int a = 0; a < M; ++a) {
+    obs[a] = (y[a] == y[a]);
+    v[a] = obs[a] ? y[a] - mu[a] : 0.f;
+  }
+  float HP[M * N];
+  mm<M, N, N>(Hx, P, HP);
+  BF_UNROLL for (int a = 0; a < M; ++a) BF_UNROLL for (int i = 0; i < N; ++i) HP[a * N + i] = obs[a] ? HP[a * N + i] : 0.f;
+  float S[M * M];
+  mm_nt<M, N, M>(HP, Hx, S);
+  BF_UNROLL for (int a = 0; a < M; ++a) BF_UNROLL for (int b = 0; b < M; ++b)
+      S[a * M + b] = (obs[a] && obs[b]) ? HrRHr[a * M + b] + S[a * M + b] : (a == b ? 1.f : 0.f);
+  float X[M * N];
+  BF_UNROLL for (int i = 0; i < M * N; ++i) X[i] = HP[i];
+  psd_solve_masked<M, N>(S, X, obs);
+  float KS[N * M];
+  BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int b = 0; b < M; ++b) {
+    float s = X[i] * S[b];
+    BF_UNROLL for (int a = 1; a < M; ++a) s = fmaf(X[a * N + i], S[a * M + b], s);
+    KS[i * M + b] = s;
+  }
+  BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int j = 0; j < N; ++j) {
+    float s = KS[i * M] * X[j];
+    BF_UNROLL for (int b = 1; b < M; ++b) s = fmaf(KS[i * M + b], X[b * N + j], s);
+    P[i * N + j] -= s;
+  }
+  BF_UNROLL for (int i = 0; i < N; ++i) {
+    float s = X[i] * v[0];
+    BF_UNROLL for (int a = 1; a < M; ++a) s = fmaf(X[a * N + i], v[a], s);
+    m[i] += s;
+  }
+  return mvn_logpdf_chol_masked<M>(S, v, obs);
+}
+
 // Covariance part of _predict (inference.py:69): P <- F_x P F_x^T + FqQFq.
 template <int N>
 __device__ __forceinline__ void predict_cov(const float* Fx, const float* FqQFq, float* P) {

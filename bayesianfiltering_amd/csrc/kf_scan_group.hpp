@@ -87,7 +87,10 @@ struct GroupCfg {
   static constexpr bool STAGED_OK = TP::GOK && TM::GOK && TW::GOK;
 };
 
-template <int NS, int M, int NL, int MODE, bool TV>
+// MISSING (bf_kalman_filter_missing_f32): a NaN entry of y is a component that was not observed at that step.  The update runs
+// on the sub-model of the observed components, embedded in the M x M system (kf_math.hpp: psd_solve_masked) so that the step
+// stays branch-free; loads, emitters and predict are the same code.
+template <int NS, int M, int NL, int MODE, bool TV, bool MISSING = false>
 __global__ void __launch_bounds__(256, (NL >= 4 ? 4 : NL))
 kf_scan_group_kernel(KFConst<NS, M> c, const float* __restrict__ gqg_t, const float* __restrict__ drd_t, CView y,
                      CarryView carry, OutViews out, long long B, long long T, int lds_per_wave, int vm_younger, int wscalar) {
@@ -199,10 +202,13 @@ kf_scan_group_kernel(KFConst<NS, M> c, const float* __restrict__ gqg_t, const fl
     // ================= _condition_on (inference.py:72-105) =================
     // innovation v = y - (H m + H_r r0): group all-reduce over the state index
     float v[M];
+    [[maybe_unused]] bool obs[M];
+    if constexpr (MISSING) BF_UNROLL for (int a = 0; a < M; ++a) obs[a] = (yv[a] == yv[a]);
     BF_UNROLL for (int a = 0; a < M; ++a) {
       float s = Hcol[0][a] * mj[0];
       BF_UNROLL for (int cc = 1; cc < CPL; ++cc) s = fmaf(Hcol[cc][a], mj[cc], s);
       v[a] = yv[a] - (group_sum<NL>(s) + c.Dr0[a]);
+      if constexpr (MISSING) v[a] = obs[a] ? v[a] : 0.f;
     }
     // owned columns of H_x P, laid out [a][cc] (the right-hand sides of the gain solve)
     float X[M * CPL];
@@ -210,6 +216,7 @@ kf_scan_group_kernel(KFConst<NS, M> c, const float* __restrict__ gqg_t, const fl
       float s = c.H[a * NS] * Pc[cc][0];
       BF_UNROLL for (int i = 1; i < NS; ++i) s = fmaf(c.H[a * NS + i], Pc[cc][i], s);
       X[a * CPL + cc] = s;
+      if constexpr (MISSING) X[a * CPL + cc] = obs[a] ? s : 0.f;  // a missing row of H_x P: zero right-hand sides
     }
     // S = H_r R H_r^T + (H_x P) H_x^T
     float S[M * M];
@@ -217,9 +224,12 @@ kf_scan_group_kernel(KFConst<NS, M> c, const float* __restrict__ gqg_t, const fl
       float s = X[a * CPL] * Hcol[0][bb];
       BF_UNROLL for (int cc = 1; cc < CPL; ++cc) s = fmaf(X[a * CPL + cc], Hcol[cc][bb], s);
       S[a * M + bb] = DRD[a * M + bb] + group_sum<NL>(s);
+      // a missing component's row and column of S become e_a: S is a permutation of blockdiag(S_oo, I)
+      if constexpr (MISSING) S[a * M + bb] = (obs[a] && obs[bb]) ? S[a * M + bb] : (a == bb ? 1.f : 0.f);
     }
     // K[col][:] = column col of solve(S + 1e-6, H_x P)       X[a][cc] = K[col(cc)][a]
-    psd_solve<M, CPL>(S, X);
+    if constexpr (MISSING) psd_solve_masked<M, CPL>(S, X, obs);
+    else psd_solve<M, CPL>(S, X);
     // (K S)[col][:]
     float KS[CPL][M];
     BF_UNROLL for (int cc = 0; cc < CPL; ++cc) BF_UNROLL for (int bb = 0; bb < M; ++bb) {
@@ -244,7 +254,9 @@ kf_scan_group_kernel(KFConst<NS, M> c, const float* __restrict__ gqg_t, const fl
       BF_UNROLL for (int a = 1; a < M; ++a) s = fmaf(X[a * CPL + cc], v[a], s);
       mj[cc] += s;
     }
-    const float ll = mvn_logpdf_chol<M>(S, v);
+    float ll;
+    if constexpr (MISSING) ll = mvn_logpdf_chol_masked<M>(S, v, obs);
+    else ll = mvn_logpdf_chol<M>(S, v);
 
     // ================= reweight, K = 1 (inference.py:347-350) =================
     w = reweight_single(ll, w);
@@ -426,7 +438,7 @@ static inline bool stream_is_reference(const bf_stream& s, long long E, long lon
          (s.sE == 1 && s.sT == E && s.sB == T * E && (reinterpret_cast<uintptr_t>(s.ptr) % 16 == 0));
 }
 
-template <int N, int M, int NL>
+template <int N, int M, int NL, bool MISSING = false>
 static inline int launch_nml(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
                       const bf_out_desc* out, hipStream_t stream, int force_mode) {
   using Cfg = GroupCfg<N, M, NL>;
@@ -530,7 +542,7 @@ static inline int launch_nml(const bf_lgssm* p, const bf_cstream* y, long long B
     dim3 block(256);
     dim3 grid((unsigned)((waves + 3) / 4));
 #define BF_LAUNCH(MODE_, TV_)                                                                                  \
-  hipLaunchKernelGGL((kf_scan_group_kernel<N, M, NL, MODE_, TV_>), grid, block, lds_bytes, stream, c, d_gqg,   \
+  hipLaunchKernelGGL((kf_scan_group_kernel<N, M, NL, MODE_, TV_, MISSING>), grid, block, lds_bytes, stream, c, d_gqg,   \
                      d_drd, yv2, cv2, ov2, b_count, T, lds_per_wave, vm_younger, (int)wscalar)
     if (tv) {
       if (mode_ == EMIT_SCALAR) BF_LAUNCH(EMIT_SCALAR, true);

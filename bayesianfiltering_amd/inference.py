@@ -313,9 +313,51 @@ def _kalman_call(params, emissions, initial_means, initial_covariances, carry, f
                         layout, out, return_loglik, return_carry, device, reshape_weights=True)
 
 
+def _observed_mask(observed, shape, m):
+    """``observed`` as a host bool array shaped like emissions of ``shape`` ((T, m) or (B, T, m)) after broadcasting: a mask
+    (T,), (T, m), (B, T) or (B, T, m), read in that order where two coincide (the batched forms only with batched
+    emissions).  Host work only: a mask that does not fit is refused before the device is touched."""
+    torch = _torch()
+    if isinstance(observed, torch.Tensor):
+        observed = observed.detach().cpu().numpy()
+    mask = np.asarray(observed)
+    if mask.dtype != np.bool_:
+        raise ValueError(f"observed must be a bool mask; got dtype {mask.dtype}")
+    shape = tuple(int(v) for v in shape)
+    if len(shape) not in (2, 3) or shape[-1] != m:
+        raise ValueError(f"emissions must be (T,{m}) or (B,T,{m}); got {shape}")
+    T, got = shape[-2], tuple(mask.shape)
+    if got == (T,):
+        mask = mask.reshape(T, 1)
+    elif got == (T, m):
+        pass
+    elif len(shape) == 3 and got == shape[:2]:
+        mask = mask.reshape(shape[0], T, 1)
+    elif got != shape:
+        forms = f"({T},), ({T},{m})" + (f", ({shape[0]},{T}) or ({shape[0]},{T},{m})" if len(shape) == 3 else "")
+        raise ValueError(f"observed must have shape {forms}; got {got}")
+    return np.array(np.broadcast_to(mask, shape))   # a writable, contiguous copy
+
+
+def _masked_emissions(emissions, mask, device):
+    """A float32 copy of ``emissions`` on ``device`` with NaN where ``mask`` (from :func:`_observed_mask`) is false.  Always a
+    new tensor: the caller's array or tensor is never written."""
+    torch = _torch()
+    y = _dev_f32(emissions, device)
+    return torch.where(torch.as_tensor(mask, device=y.device), y, torch.full((), float("nan"), dtype=torch.float32, device=y.device))
+
+
+def _missing_route(missing, observed):
+    """Whether the call takes the missing-observation entry point: ``missing="nan"``, or any ``observed=`` mask."""
+    if missing not in (None, "nan"):
+        raise ValueError(f"missing must be None or 'nan'; got {missing!r}")
+    return missing == "nan" or observed is not None
+
+
 def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
                   fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
-                  return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None):
+                  return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None,
+                  missing=None, observed=None):
     """Batched Kalman filter == ``gaussian_sum_filter(params, y, num_components=1)`` of the
     reference for linear ``f(x,q,u) = A x + G q``, ``h(x,r,u) = H x + D r`` with the initial
     component mean given explicitly (the reference samples it from N(m0, P0) with PRNGKey(0),
@@ -325,13 +367,23 @@ def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=
     (1, T, ...) or (B, 1, T, ...); ``layout='batch_inner'`` returns the same logical shapes as
     strided views of a [K][T][E][B] buffer (the fastest store pattern).  ``out`` may hold a
     previously returned posterior whose buffers are reused.
+
+    ``missing="nan"``: a NaN entry of ``emissions`` is a component that was not observed at that step
+    (``bf_kalman_filter_missing_f32``: the update conditions on the observed rows only, a step with none is predict-only with
+    log-likelihood 0; n <= 8 and m <= 4).  Without it a NaN poisons its trajectory from that step on, as ever.  +-Inf is never
+    "missing".  ``observed``: a bool mask of shape (T,), (B, T), (T, m) or (B, T, m), true where the entry was observed; it
+    implies ``missing="nan"`` and the filter runs on a device copy of the emissions with NaN where the mask is false.
     """
+    gaps = _missing_route(missing, observed)
+    mask = None if observed is None else _observed_mask(observed, np.shape(emissions), _Lgssm(params).m)
     lib = _lib.require_gpu()
+    if mask is not None:
+        emissions = _masked_emissions(emissions, mask, device)
     k = _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
                      return_carry, device)
     _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
-    _lib.check(lib.bf_kalman_filter_f32(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od),
-                                        C.c_void_p(k.stream)))
+    entry = lib.bf_kalman_filter_missing_f32 if gaps else lib.bf_kalman_filter_f32
+    _lib.check(entry(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od), C.c_void_p(k.stream)))
     return k.result()
 
 

@@ -136,9 +136,11 @@ def posterior_sample(params, posterior, num_samples: int = 1, *, key=None, noise
 def kalman_posterior_sample(params, emissions, num_samples, key, **kw):
     """``kalman_filter`` emitting the filtered fields only, then :func:`posterior_sample` on the recompute path.
     Keywords of :func:`kalman_filter` (``initial_means``, ``initial_covariances``, ``layout``, ``device``) go to the
-    filter, the others to :func:`posterior_sample`."""
+    filter, the others to :func:`posterior_sample`.  ``missing`` / ``observed`` are :func:`kalman_filter`'s: the backward pass
+    reads no observations, so it runs on the gapped posterior as it is."""
+    gaps = {k: kw.pop(k) for k in ("missing", "observed") if k in kw}
     fkw, skw = _wrapper_kw(params, kw, False)
-    return posterior_sample(params, kalman_filter(params, emissions, **fkw), num_samples, key=key, **skw)
+    return posterior_sample(params, kalman_filter(params, emissions, **fkw, **gaps), num_samples, key=key, **skw)
 
 
 def extended_kalman_posterior_sample(params, emissions, num_samples, key, inputs=None, **kw):

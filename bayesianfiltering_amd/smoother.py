@@ -127,9 +127,11 @@ def kalman_smoother(params, emissions, **kw):
     """``kalman_filter`` emitting the filtered fields only, then :func:`rts_smoother` on the recompute path (the
     predictions are formed again inside the backward pass: 80 instead of 160 bytes read per step at n = 4).
     Keywords of :func:`kalman_filter` (``initial_means``, ``initial_covariances``, ``layout``, ``device``) go to the
-    filter, the others to :func:`rts_smoother`."""
+    filter, the others to :func:`rts_smoother`.  ``missing`` / ``observed`` are :func:`kalman_filter`'s: the backward pass reads
+    no observations, so it runs on the gapped posterior as it is."""
+    gaps = {k: kw.pop(k) for k in ("missing", "observed") if k in kw}
     fkw, skw = _wrapper_kw(params, kw, False)
-    return rts_smoother(params, kalman_filter(params, emissions, **fkw), **skw)
+    return rts_smoother(params, kalman_filter(params, emissions, **fkw, **gaps), **skw)
 
 
 def extended_kalman_smoother(params, emissions, inputs=None, **kw):

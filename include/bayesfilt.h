@@ -165,7 +165,7 @@ int bf_device_count(void);
  *                   and serves particle counts up to 4 096 with registry functions.
  * bf_set_option changes the PROCESS-WIDE default.  A library or a thread that must not disturb -- or be disturbed by -- other
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
- * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
+ * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_missing_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
  * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_rts_smoother_pscan_f32, bf_eks_smoother_f32,
  * bf_ffbs_sample_f32, bf_ffbs_sample_pscan_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_gs_smoother_f32, bf_gs_sample_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
@@ -178,6 +178,25 @@ int bf_set_call_option(const char* name, int value);
  * y: observations, element (b, t, e) at y->ptr[b*sB + t*sT + e*sE], E = m. */
 int bf_kalman_filter_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T,
                          const bf_carry* carry, const bf_out_desc* out, void* stream);
+
+/* bf_kalman_filter_f32 for series with gaps: the same arguments and streams, and a NaN entry of y means "component a of
+ * trajectory b was not observed at step t" (the convention of statsmodels / pykalman; no second input stream).  With o the
+ * components of a step that are not NaN, the update is _condition_on on the sub-model of those rows -- H[o,:], (D r0)[o],
+ * (D R D^T)[o,o], the reference's 1e-6 on every entry of the reduced S_oo in the gain solve -- and the step's log-likelihood
+ * is log N(v_o; 0, S_oo) with |o| in the log 2 pi term.  o empty: m+ = m-, P+ = P- exactly, log-likelihood 0, weight
+ * reweight(0, w); the predict step runs as always, so trailing unobserved steps are a forecast.  +-Inf is NOT missing: a
+ * non-finite innovation of an observed component poisons the trajectory as in bf_kalman_filter_f32 (which keeps treating NaN
+ * that way: this entry point is opt-in).  The step is the reduced model's arithmetic embedded in the m x m system (missing
+ * rows and columns of S replaced by those of the identity, exact zeros elsewhere), so lanes with different patterns stay
+ * convergent and a trajectory's bits do not depend on its neighbours' gaps.  The smoothers and samplers read no observations:
+ * they run on these streams as they are.
+ * Register kernels only, each (n, m) pair at its default lanes per trajectory; honours "kf_emit_mode" ("force_generic" and
+ * "kf_small_mode" do not apply: there is no other kernel to fall back to).
+ * BF_EUNSUPPORTED: n > 8 or m > 4 (the message names the limit), m > n, a "kf_lanes" other than 0 or the pair's default,
+ * collapsed streams.  BF_EINVAL: NULL arguments, B or T <= 0, what bf_kalman_filter_f32 refuses of the model and the carry.
+ * Every check precedes the first HIP call.  With this one, this header declares 46 entry points. */
+int bf_kalman_filter_missing_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T,
+                                 const bf_carry* carry, const bf_out_desc* out, void* stream);
 
 /* Parallel-in-time Kalman filter for few long trajectories: the model, streams, carry and log-likelihood of
  * bf_kalman_filter_f32, with time cut into blocks of L steps that run on separate lanes (the associative filtering elements
