@@ -138,5 +138,7 @@ def _wrapper_kw(params, kw, nonlinear):
     skw = {k: v for k, v in kw.items() if k not in ("initial_means", "initial_covariances")}
     if nonlinear and "initial_means" not in fkw:
         fkw["initial_means"] = _host_f32(params.initial_mean).reshape(1, -1)
+    if nonlinear:   # ``missing`` / ``observed`` are the Gaussian-sum filters': a backward pass reads no observations
+        fkw.update({k: skw.pop(k) for k in ("missing", "observed") if k in skw})
     fkw["fields"] = _FULL5_PRED if nonlinear else ("means", "covariances")
     return fkw, skw

@@ -135,6 +135,10 @@ SYMBOLS = {
                                  C.c_int32, C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
     "bf_ugsf_ukf_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_ukf_params), C.POINTER(bf_cstream), C.POINTER(bf_cstream),
                                   C.c_int64, C.c_int64, C.c_int32, C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
+    "bf_gsf_ekf_missing_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
+                                         C.c_int32, C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
+    "bf_ugsf_ukf_missing_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_ukf_params), C.POINTER(bf_cstream), C.POINTER(bf_cstream),
+                                          C.c_int64, C.c_int64, C.c_int32, C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
     "bf_agsf_ekf_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
                                   C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _FP, C.POINTER(bf_carry),
                                   C.POINTER(bf_out_desc), C.c_void_p, C.c_int32, C.c_void_p]),

@@ -45,6 +45,14 @@ int launch_gsf_ekf(const bf_model* p, const bf_cstream* y, const bf_cstream* u, 
 
 int launch_ugsf_ukf(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
                     long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream);
+// the MISSING = true instances (gsf_scan.hip, ugsf_scan.hip)
+int gsf_default_lanes(int n);
+int launch_gsf_ekf_missing(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
+                           const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, int force_mode, int lanes);
+int launch_gsf_user_regs_missing_impl(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
+                                      const bf_carry* carry, const bf_out_desc* out, hipStream_t stream);
+int launch_ugsf_ukf_missing(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
+                            long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream);
 int launch_agsf_ekf(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, const int32_t nc[3],
                     const uint32_t key[2], const float opt[2], const bf_carry* carry, const bf_out_desc* out, int* d_leaf_idx,
                     int variant, hipStream_t stream);
@@ -325,6 +333,66 @@ int bf_ugsf_ukf_f32(const bf_model* model, const bf_ukf_params* uparams, const b
   if (B <= 0 || T <= 0 || K <= 0) return bf::set_error(BF_EINVAL, "B, T and K must be positive");
   if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_streams(y, carry)) || (rc = bf::check_alpha(uparams))) return rc;
   return bf::launch_ugsf_ukf(model, uparams, y, u, B, T, K, carry, out, static_cast<hipStream_t>(stream));
+}
+
+// Missing observations (NaN entries of y) on the register kernels of the two Gaussian-sum filters.  Both entry points refuse,
+// before their first HIP call, whatever the plain route would hand to a kernel that reads a NaN as poison: there is no fallback.
+int bf_gsf_ekf_missing_f32(const bf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t K,
+                           const bf_carry* carry, const bf_out_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  static const char* const who = "gaussian-sum filter with missing observations";
+  if (!model || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (B <= 0 || T <= 0 || K <= 0) return bf::set_error(BF_EINVAL, "B, T and K must be positive");
+  if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_streams(y, carry))) return rc;
+  if (model->flags != 0) return bf::set_error(BF_EUNSUPPORTED, "%s: the legacy classes (flags != 0) are not served", who);
+  if (bf::g_force_generic.load())
+    return bf::set_error(BF_EUNSUPPORTED, "%s: force_generic is set, and the run-time-dimension kernel takes no gaps", who);
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  if (model->user) {   // functions from source: the register kernel built at run time, or nothing
+    if (model->n > 8 || model->dq > 8 || model->m > 8 || model->dr > 8)
+      return bf::set_error(BF_EUNSUPPORTED, "%s: models from source need every dimension <= 8 (n=%d, dq=%d, m=%d, dr=%d)", who,
+                           (int)model->n, (int)model->dq, (int)model->m, (int)model->dr);
+    if (K > 256) return bf::set_error(BF_EUNSUPPORTED, "%s: models from source take at most 256 components (K=%d)", who, (int)K);
+    if (out->coll_mean.ptr || out->coll_cov.ptr)
+      return bf::set_error(BF_EUNSUPPORTED, "%s: models from source produce no collapsed streams", who);
+    if (!bf::gsf_user_regs_eligible(model, K, out))
+      return bf::set_error(BF_EUNSUPPORTED, "%s: this model from source is not eligible for the register kernel (a log-density, or a "
+                                            "nonlinear registry function beside one from source)", who);
+    return bf::launch_gsf_user_regs_missing_impl(model, y, u, B, T, K, carry, out, hs);
+  }
+  if (model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER)
+    return bf::set_error(BF_EINVAL, "dyn_id / emi_id = BF_FN_USER needs bf_model.user (bf_user_model_create)");
+  // the register kernels only: no matrix-core or run-time-dimension instance takes gaps
+  if (model->n > 8 || model->m > 4)
+    return bf::set_error(BF_EUNSUPPORTED, "%s: n <= 8 and m <= 4 only (n=%d, m=%d)", who, (int)model->n, (int)model->m);
+  const int lanes = bf::g_kf_lanes.load();
+  if (lanes != 0 && lanes != bf::gsf_default_lanes(model->n))
+    return bf::set_error(BF_EUNSUPPORTED, "%s: kf_lanes=%d is not served at n=%d; the compiled default is %d (or 0)", who, lanes,
+                         (int)model->n, bf::gsf_default_lanes(model->n));
+  return bf::launch_gsf_ekf_missing(model, y, u, B, T, K, carry, out, hs, bf::g_kf_emit_mode.load(), lanes);
+}
+
+int bf_ugsf_ukf_missing_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* y, const bf_cstream* u,
+                            int64_t B, int64_t T, int32_t K, const bf_carry* carry, const bf_out_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  static const char* const who = "unscented gaussian-sum filter with missing observations";
+  if (!model || !uparams || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (B <= 0 || T <= 0 || K <= 0) return bf::set_error(BF_EINVAL, "B, T and K must be positive");
+  if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_streams(y, carry)) || (rc = bf::check_alpha(uparams))) return rc;
+  if (model->flags != 0) return bf::set_error(BF_EUNSUPPORTED, "%s: the legacy classes (flags != 0) are not served", who);
+  if (bf::g_ugsf_force_generic.load())
+    return bf::set_error(BF_EUNSUPPORTED, "%s: ugsf_force_generic is set, and the run-time-dimension kernel takes no gaps", who);
+  if (model->n > 8 || model->dq > 8 || model->m > 8 || model->dr > 8)
+    return bf::set_error(BF_EUNSUPPORTED, "%s: every dimension <= 8 only (n=%d, dq=%d, m=%d, dr=%d)", who, (int)model->n,
+                         (int)model->dq, (int)model->m, (int)model->dr);
+  if (K > 256) return bf::set_error(BF_EUNSUPPORTED, "%s: at most 256 components (K=%d)", who, (int)K);
+  if (out->coll_mean.ptr || out->coll_cov.ptr)
+    return bf::set_error(BF_EUNSUPPORTED, "%s: collapsed streams are produced by bf_gsf_ekf_missing_f32 only", who);
+  if (!model->user && (model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER))
+    return bf::set_error(BF_EINVAL, "dyn_id / emi_id = BF_FN_USER needs bf_model.user (bf_user_model_create)");
+  if (model->user && model->user->has_lp)
+    return bf::set_error(BF_EINVAL, "a log-density from source belongs to the particle filter, not to the unscented filter");
+  return bf::launch_ugsf_ukf_missing(model, uparams, y, u, B, T, K, carry, out, static_cast<hipStream_t>(stream));
 }
 
 int bf_agsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T,

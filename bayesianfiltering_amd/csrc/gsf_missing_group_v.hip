@@ -1,0 +1,20 @@
+// Missing-observation instance (MISSING = true) of the unscented Gaussian-sum filter kernel (ugsf_scan.hpp) for the largest
+// shape ugsf_scan.hip compiles ahead of time; a translation unit of its own, since it alone builds as long as the other eight.
+#include "ugsf_scan.hpp"
+
+namespace bf {
+
+int launch_ugsf_missing_group_v(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
+        long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, bool* matched) {
+#define BF_MISSING_CASE(N_, DQ_, M_, DR_)                                                            \
+  if (p->n == N_ && p->dq == DQ_ && p->m == M_ && p->dr == DR_) {                                    \
+    *matched = true;                                                                                 \
+    return launch_ugsf<N_, DQ_, M_, DR_, true>(p, up, y, u, B, T, K, carry, out, stream);            \
+  }
+  BF_MISSING_CASE(8, 8, 4, 4);   // Lorenz-96 with the even-state emission
+#undef BF_MISSING_CASE
+  *matched = false;
+  return BF_OK;
+}
+
+}  // namespace bf

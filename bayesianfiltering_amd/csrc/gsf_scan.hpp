@@ -79,7 +79,11 @@ constexpr int wrap_mod(int i) {
 
 // EXT = true adds the optional features -- COLLAPSED outputs and per-step (time-varying) noise covariances --
 // as their own instances (strided stores only), so that the plain instances keep their register budget.
-template <int NS, int M, int NL, int MODE, int SPEC, bool EXT = false>
+// MISSING = true: a NaN y[b, t, a] is a component that was not observed at that step.  Every component of the bank conditions
+// on the observed rows only, through the embedding of kf_math.hpp (psd_solve_masked / mvn_logpdf_chol_masked); what the model
+// computes for a missing row is discarded by selects, so a NaN or Inf it produces there never reaches the state.  Its own
+// instances (gsf_missing_group_*.hip); nothing else in the step changes.
+template <int NS, int M, int NL, int MODE, int SPEC, bool EXT = false, bool MISSING = false>
 #ifndef BF_GSF_NONE_WAVES
 #define BF_GSF_NONE_WAVES 2
 #endif
@@ -319,6 +323,9 @@ gsf_scan_kernel(EkfModel<NS, M> mdl, CView y, UView uin, CarryView carry, OutVie
     float yv[M];
     BF_UNROLL for (int a = 0; a < M; ++a) yv[a] = y.p[b * y.sB + t * y.sT + a * y.sE];
     const float u0 = uin.p ? uin.p[b * uin.sB + t * uin.sT] : 0.f;
+    // (the pattern is taken here, into scalar masks: yv itself then lives no longer than in the plain instances)
+    [[maybe_unused]] bool obs[M];
+    if constexpr (MISSING) BF_UNROLL for (int a = 0; a < M; ++a) obs[a] = (yv[a] == yv[a]);
 
     // ================= _condition_on (inference.py:72-105), linearised at the predicted mean
     float v[M], X[M * CPL], S[M * M];
@@ -362,7 +369,16 @@ gsf_scan_kernel(EkfModel<NS, M> mdl, CView y, UView uin, CarryView carry, OutVie
         S[a * M + bb] = HrRHr[a * M + bb] + group_sum<NL>(s);
       }
     }
-    psd_solve<M, CPL>(S, X, mdl.jitter);
+    if constexpr (MISSING) {
+      BF_UNROLL for (int a = 0; a < M; ++a) {
+        v[a] = obs[a] ? v[a] : 0.f;
+        BF_UNROLL for (int cc = 0; cc < CPL; ++cc) X[a * CPL + cc] = obs[a] ? X[a * CPL + cc] : 0.f;
+        BF_UNROLL for (int bb = 0; bb < M; ++bb) S[a * M + bb] = (obs[a] && obs[bb]) ? S[a * M + bb] : (a == bb ? 1.f : 0.f);
+      }
+      psd_solve_masked<M, CPL>(S, X, obs, mdl.jitter);
+    } else {
+      psd_solve<M, CPL>(S, X, mdl.jitter);
+    }
     float KS[CPL][M];
     BF_UNROLL for (int cc = 0; cc < CPL; ++cc) BF_UNROLL for (int bb = 0; bb < M; ++bb) {
       float s = X[cc] * S[bb];
@@ -388,7 +404,9 @@ gsf_scan_kernel(EkfModel<NS, M> mdl, CView y, UView uin, CarryView carry, OutVie
       BF_UNROLL for (int a = 1; a < M; ++a) s = fmaf(X[a * CPL + cc], v[a], s);
       mj[cc] += s;
     }
-    const float ll = mvn_logpdf_chol<M>(S, v);
+    float ll;
+    if constexpr (MISSING) ll = mvn_logpdf_chol_masked<M>(S, v, obs);
+    else ll = mvn_logpdf_chol<M>(S, v);
 
     // ================= reweight (inference.py:347-350): lls -= max; w = exp(lls) * w; w /= sum(w)
     {
@@ -699,7 +717,7 @@ static inline bool gsf_is_l96_pick(const bf_model* p) {
   return true;
 }
 
-template <int N, int M, int NL, int SPEC = SPEC_GENERIC>
+template <int N, int M, int NL, int SPEC = SPEC_GENERIC, bool MISSING = false>
 static inline int launch_gsf(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
                       const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, int force_mode) {
   using Cfg = GsfCfg<N, M, NL>;
@@ -766,17 +784,17 @@ static inline int launch_gsf(const bf_model* p, const bf_cstream* y, const bf_cs
   const bool no_streams = !out->weights.ptr && !out->means.ptr && !out->covs.ptr && !out->pred_means.ptr && !out->pred_covs.ptr &&
                           !out->loglik.ptr;
   if (ext && no_streams) {  // collapsed-only: the per-component store code is not even compiled in
-    hipLaunchKernelGGL((gsf_scan_kernel<N, M, NL, EMIT_NONE, SPEC, true>), grid, block, lds_bytes, stream, e, yv, uv, cv, ov, B,
+    hipLaunchKernelGGL((gsf_scan_kernel<N, M, NL, EMIT_NONE, SPEC, true, MISSING>), grid, block, lds_bytes, stream, e, yv, uv, cv, ov, B,
                        T, K, KP, lds_per_wave, d_tvq, d_tvr, (int)wscalar);
   } else if (ext) {
-    hipLaunchKernelGGL((gsf_scan_kernel<N, M, NL, EMIT_SCALAR, SPEC, true>), grid, block, lds_bytes, stream, e, yv, uv, cv, ov, B,
+    hipLaunchKernelGGL((gsf_scan_kernel<N, M, NL, EMIT_SCALAR, SPEC, true, MISSING>), grid, block, lds_bytes, stream, e, yv, uv, cv, ov, B,
                        T, K, KP, lds_per_wave, d_tvq, d_tvr, (int)wscalar);
   } else if (mode == EMIT_SCALAR) {
-    hipLaunchKernelGGL((gsf_scan_kernel<N, M, NL, EMIT_SCALAR, SPEC>), grid, block, lds_bytes, stream, e, yv, uv, cv, ov, B, T, K,
+    hipLaunchKernelGGL((gsf_scan_kernel<N, M, NL, EMIT_SCALAR, SPEC, false, MISSING>), grid, block, lds_bytes, stream, e, yv, uv, cv, ov, B, T, K,
                        KP, lds_per_wave, d_tvq, d_tvr, (int)wscalar);
   } else {
     if constexpr (Cfg::STAGED_OK)
-      hipLaunchKernelGGL((gsf_scan_kernel<N, M, NL, EMIT_STAGED, SPEC>), grid, block, lds_bytes, stream, e, yv, uv, cv, ov, B, T, K,
+      hipLaunchKernelGGL((gsf_scan_kernel<N, M, NL, EMIT_STAGED, SPEC, false, MISSING>), grid, block, lds_bytes, stream, e, yv, uv, cv, ov, B, T, K,
                          KP, lds_per_wave, d_tvq, d_tvr, (int)wscalar);
   }
   BF_HIP_CHECK(hipGetLastError());

@@ -10,11 +10,12 @@ extern Option g_ugsf_force_generic;   // ugsf_generic.hip
 
 // ugsf_scan_body built around the handle's functions: `kind` JIT_UGSF (sigma points through f and h) or JIT_GSF_REGS
 // (extended-Kalman operations, Jacobians by dual numbers; user_flags bit 2: the covariances themselves, not their roots)
+// missing: the kernel's MISSING = true twin (its own module of the handle: variant 1)
 static int launch_ugsf_jit(int kind, const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
-                           long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
+                           long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, bool missing = false) {
   const bf_user_model* um = p->user;
   hipFunction_t fn = nullptr;
-  int rc = user_kernel(um, kind, 0, 0, JIT_SPEC_USER, &fn);
+  int rc = user_kernel(um, kind, missing ? 1 : 0, 0, JIT_SPEC_USER, &fn);
   if (rc != BF_OK) return rc;
   UgsfLaunch L;
   rc = prepare_ugsf(p, up, (um->user_flags() & 3) | (kind == JIT_GSF_REGS ? 4 : 0), y, u, B, T, K, carry, out, stream, L);
@@ -82,6 +83,41 @@ int launch_ugsf_ukf(const bf_model* p, const bf_ukf_params* up, const bf_cstream
   jit.user = registry_jit_handle(p, false);
   if (!jit.user) return set_error(BF_ENOGPU, "no current device");
   return launch_ugsf_user_impl(&jit, up, y, u, B, T, K, carry, out, stream);
+}
+
+// ---- missing observations (NaN entries): the MISSING = true twins of the register kernels above.  Nothing else takes gaps, so
+// whatever the plain route would send to a run-time-dimension kernel is refused here (bf_api.hip checks before any HIP call).
+int launch_ugsf_missing_group_u(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
+        long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, bool* matched);
+int launch_ugsf_missing_group_v(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
+        long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, bool* matched);
+
+int launch_gsf_user_regs_missing_impl(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
+                                      const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
+  const int rc = check_user_model(p->user, p);
+  if (rc != BF_OK) return rc;
+  return launch_ugsf_jit(JIT_GSF_REGS, p, nullptr, y, u, B, T, K, carry, out, stream, true);
+}
+
+int launch_ugsf_ukf_missing(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
+                            long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
+  if (p->user) {
+    const int rc = check_user_model(p->user, p);
+    if (rc != BF_OK) return rc;
+    return launch_ugsf_jit(JIT_UGSF, p, up, y, u, B, T, K, carry, out, stream, true);
+  }
+  bool matched = false;
+  int rc = launch_ugsf_missing_group_u(p, up, y, u, B, T, K, carry, out, stream, &matched);
+  if (matched) return rc;
+  rc = launch_ugsf_missing_group_v(p, up, y, u, B, T, K, carry, out, stream, &matched);
+  if (matched) return rc;
+  // no compiled instance for these dimensions: the same kernel, compiled now (needs hiprtc; dimensions up to 8)
+  bf_model jit = *p;
+  jit.user = registry_jit_handle(p, false);
+  if (!jit.user) return set_error(BF_ENOGPU, "no current device");
+  const int rc2 = check_user_model(jit.user, &jit);
+  if (rc2 != BF_OK) return rc2;
+  return launch_ugsf_jit(JIT_UGSF, &jit, up, y, u, B, T, K, carry, out, stream, true);
 }
 
 }  // namespace bf

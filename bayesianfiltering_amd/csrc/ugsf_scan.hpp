@@ -160,7 +160,10 @@ __device__ __forceinline__ void ukf_emi(const UkfModel<N, DQ, M, DR>& p, const f
 // _ukf_condition_on_nonadditive (inference.py:198-224): m, P <- posterior; returns the log-likelihood.
 // sR: sqrtm of this step's emission noise covariance (mdl.sR, or row t of the per-step table when R is (T, dr, dr):
 // inference.py:416 picks R_t before the step, :206-209 take the square root of blockdiag(P, R_t))
-template <class SP = SpecRuntime, int N, int DQ, int M, int DR>
+// MISSING: a NaN yv[a] is a component that was not observed.  The sigma points are those of the full augmented state (dropping
+// output rows changes neither them nor the weights); mu, S and C are restricted to the observed rows by selects, embedded in
+// the M x M system (kf_math.hpp), so what h yields in a missing row -- a NaN included -- is discarded.
+template <class SP = SpecRuntime, bool MISSING = false, int N, int DQ, int M, int DR>
 __device__ __forceinline__ float ukf_condition_on(const UkfModel<N, DQ, M, DR>& mdl, float* m, float* P, const float* yv, float u0,
                                                   const float* sR) {
 #pragma clang fp contract(fast)
@@ -231,7 +234,17 @@ __device__ __forceinline__ float ukf_condition_on(const UkfModel<N, DQ, M, DR>& 
       S[a * M + c2] = S[a * M + c2] * mdl.ws_u + mdl.wc_u * (d0[a] * d0[c2]);
   BF_UNROLL for (int i = 0; i < M * N; ++i) C[i] *= mdl.ws_u;
   // K = psd_solve(S, C)^T;  P+ = P - K S K^T;  m+ = m + K (y - mu);  ll = MVN(mu, S).log_prob(y)
-  psd_solve<M, N>(S, C);  // C <- (S + 1e-6)^-1 C = K^T
+  [[maybe_unused]] bool obs[M];
+  if constexpr (MISSING) {
+    BF_UNROLL for (int a = 0; a < M; ++a) obs[a] = (yv[a] == yv[a]);
+    BF_UNROLL for (int a = 0; a < M; ++a) {
+      BF_UNROLL for (int i = 0; i < N; ++i) C[a * N + i] = obs[a] ? C[a * N + i] : 0.f;
+      BF_UNROLL for (int c2 = 0; c2 < M; ++c2) S[a * M + c2] = (obs[a] && obs[c2]) ? S[a * M + c2] : (a == c2 ? 1.f : 0.f);
+    }
+    psd_solve_masked<M, N>(S, C, obs);
+  } else {
+    psd_solve<M, N>(S, C);  // C <- (S + 1e-6)^-1 C = K^T
+  }
   float KS[N * M];
   BF_UNROLL for (int i = 0; i < N; ++i) BF_UNROLL for (int c2 = 0; c2 < M; ++c2) {
     float s = C[i] * S[c2];
@@ -245,12 +258,14 @@ __device__ __forceinline__ float ukf_condition_on(const UkfModel<N, DQ, M, DR>& 
   }
   float v[M];
   BF_UNROLL for (int a = 0; a < M; ++a) v[a] = yv[a] - mu[a];
+  if constexpr (MISSING) BF_UNROLL for (int a = 0; a < M; ++a) v[a] = obs[a] ? v[a] : 0.f;
   BF_UNROLL for (int i = 0; i < N; ++i) {
     float s = C[i] * v[0];
     BF_UNROLL for (int a = 1; a < M; ++a) s = fmaf(C[a * N + i], v[a], s);
     m[i] += s;
   }
-  ll = mvn_logpdf_chol<M>(S, v);
+  if constexpr (MISSING) ll = mvn_logpdf_chol_masked<M>(S, v, obs);
+  else ll = mvn_logpdf_chol<M>(S, v);
   return ll;
 }
 
@@ -373,6 +388,8 @@ struct UserEkfNodes {
     predict_cov<N>(F, FqQFq, P);  // F P F^T + F_q Q F_q^T
     BF_UNROLL for (int i = 0; i < N; ++i) m[i] = fx[i];
   }
+  // MISSING: a NaN yv[a] is a component that was not observed (condition_on_masked: rows o of H_x, h and H_r R H_r^T)
+  template <bool MISSING = false>
   static __device__ __forceinline__ float condition(Arg mdl, float* m, float* P, const float* yv, float u0, const float* tr) {
     float H[M * N], Hr[M * DR], hx[M], HrRHr[M * M], v[M];
 #ifdef BF_USER_EMI
@@ -402,6 +419,7 @@ struct UserEkfNodes {
       }
     }
     congruence<M, DR, M>(Hr, tr ? tr : mdl->sR, HrRHr);
+    if constexpr (MISSING) return condition_on_masked<N, M>(H, HrRHr, yv, hx, m, P);
     BF_UNROLL for (int a = 0; a < M; ++a) v[a] = yv[a] - hx[a];
     return condition_on<N, M>(H, HrRHr, v, m, P);
   }
@@ -411,7 +429,9 @@ struct UserEkfNodes {
 // NODES = void: the unscented operations above (sQ / sR: square roots).  Any other NODES (UserEkfNodes): its condition / predict
 // pair on the same lane-per-(trajectory, component) scan -- the Gaussian-sum filter of inference.py:333-371 with the caller's
 // functions in registers (sQ / sR: the covariances themselves).
-template <int N, int DQ, int M, int DR, class SP = SpecRuntime, class NODES = void>
+// MISSING = true: NaN entries of y are components that were not observed (see ukf_condition_on / UserEkfNodes::condition); a
+// step with none leaves means and covariances untouched with log-likelihood 0, the weights only pass through the reweight.
+template <int N, int DQ, int M, int DR, class SP = SpecRuntime, class NODES = void, bool MISSING = false>
 __device__ __forceinline__ void ugsf_scan_body(const UkfModel<N, DQ, M, DR>* __restrict__ mdlp, CView y, const float* __restrict__ uptr, long long u_sB,
                  long long u_sT, CarryView carry, OutViews out, long long B, long long T, int K, int KP,
                  const float* __restrict__ tvsq, const float* __restrict__ tvsr) {
@@ -468,8 +488,8 @@ __device__ __forceinline__ void ugsf_scan_body(const UkfModel<N, DQ, M, DR>* __r
     float ll;
 
     // ================= _ukf_condition_on_nonadditive (inference.py:198-224)
-    if constexpr (std::is_void<NODES>::value) ll = ukf_condition_on<SP>(mdl, m, P, yv, u0, tvsr ? tvsr + t * (DR * DR) : mdl.sR);
-    else ll = NODES::condition(mdlp, m, P, yv, u0, tvsr ? tvsr + t * (DR * DR) : nullptr);
+    if constexpr (std::is_void<NODES>::value) ll = ukf_condition_on<SP, MISSING>(mdl, m, P, yv, u0, tvsr ? tvsr + t * (DR * DR) : mdl.sR);
+    else ll = NODES::template condition<MISSING>(mdlp, m, P, yv, u0, tvsr ? tvsr + t * (DR * DR) : nullptr);
 
     // ================= reweight (inference.py:424-427)
     {
@@ -502,12 +522,12 @@ __device__ __forceinline__ void ugsf_scan_body(const UkfModel<N, DQ, M, DR>* __r
   }
 }
 
-template <int N, int DQ, int M, int DR>
+template <int N, int DQ, int M, int DR, bool MISSING = false>
 __global__ void __launch_bounds__(256)
 ugsf_scan_kernel(const UkfModel<N, DQ, M, DR>* __restrict__ mdlp, CView y, const float* __restrict__ uptr, long long u_sB,
                  long long u_sT, CarryView carry, OutViews out, long long B, long long T, int K, int KP,
                  const float* __restrict__ tvsq, const float* __restrict__ tvsr) {
-  ugsf_scan_body<N, DQ, M, DR, SpecRuntime>(mdlp, y, uptr, u_sB, u_sT, carry, out, B, T, K, KP, tvsq, tvsr);
+  ugsf_scan_body<N, DQ, M, DR, SpecRuntime, void, MISSING>(mdlp, y, uptr, u_sB, u_sT, carry, out, B, T, K, KP, tvsq, tvsr);
 }
 
 #ifndef BF_JIT   // host side
@@ -745,14 +765,14 @@ static inline int prepare_ugsf(const bf_model* p, const bf_ukf_params* up, int u
   return BF_OK;
 }
 
-template <int N, int DQ, int M, int DR>
+template <int N, int DQ, int M, int DR, bool MISSING = false>
 static inline int launch_ugsf(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
                               long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
   static_assert(sizeof(UkfModel<N, DQ, M, DR>) == 4 * ukf_model_words(N, DQ, M, DR), "UkfModel: 4-byte members in declaration order, no padding");
   UgsfLaunch L;
   const int rc = prepare_ugsf(p, up, 0, y, u, B, T, K, carry, out, stream, L);
   if (rc != BF_OK) return rc;
-  hipLaunchKernelGGL((ugsf_scan_kernel<N, DQ, M, DR>), dim3(L.grid), dim3(256), 0, stream, static_cast<const UkfModel<N, DQ, M, DR>*>(L.d_mdl),
+  hipLaunchKernelGGL((ugsf_scan_kernel<N, DQ, M, DR, MISSING>), dim3(L.grid), dim3(256), 0, stream, static_cast<const UkfModel<N, DQ, M, DR>*>(L.d_mdl),
                      L.y, L.uptr, L.u_sB, L.u_sT, L.carry, L.out, B, T, K, L.KP, L.d_tvq, L.d_tvr);
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;

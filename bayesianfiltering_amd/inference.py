@@ -474,7 +474,7 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
                         initial_means=None, initial_covariances=None, carry=None,
                         fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
                         return_loglik: bool = False, return_carry: bool = False, return_collapsed: bool = False,
-                        device="cuda", options=None, _uparams=None):
+                        device="cuda", options=None, _uparams=None, missing=None, observed=None):
     """Gaussian-sum filter (bank of K extended Kalman filters + weight update),
     gaussfiltax/inference.py:303-377, on the HIP engine.
 
@@ -488,12 +488,29 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
     Gaussian of the filtered mixture at every step (utils.collapse, utils.py:10-18; the point estimate of
     BOT_Experiment_script.py:101), formed inside the scan: with ``fields=()`` a K-component run then
     returns 4(n + n^2) bytes per step instead of the K-fold streams (COLLAPSED mode).
+
+    ``missing="nan"``: a NaN entry of ``emissions`` is a component that was not observed at that step
+    (``bf_gsf_ekf_missing_f32``, DESIGN.md 4b'): every component of the bank conditions on the observed rows only, a step with
+    none leaves means and covariances untouched with log-likelihood 0 (the weights are renormalised only), trailing gaps are a
+    forecast.  Register kernels only: registry models with n <= 8 and m <= 4, models from source with every dimension <= 8.
+    Without it a NaN poisons its trajectory, as ever; +-Inf is never "missing".  ``observed``: a bool mask of shape (T,),
+    (B, T), (T, m) or (B, T, m), true where the entry was observed; it implies ``missing="nan"`` (see :func:`kalman_filter`).
     """
     torch = _torch()
-    lib = _lib.require_gpu()
+    gaps = _missing_route(missing, observed)
     K = int(num_components)
     if K < 1:
         raise ValueError("num_components must be >= 1")
+    mask = None
+    if observed is not None:   # (m from the model dimensions; host work only: a mask that does not fit never reaches the device)
+        h = params.emission_function
+        if not isinstance(h, DeviceFunction):   # a plain Python function: recorded on the host, as _Model does
+            n0, _, dr0 = _param_dims(params)
+            h = require_device_function(h, "emission", "params.emission_function", n0, dr0)
+        mask = _observed_mask(observed, np.shape(emissions), int(h.out_dim))
+    lib = _lib.require_gpu()
+    if mask is not None:
+        emissions = _masked_emissions(emissions, mask, device)
     k = _filter_call(_Model(params), emissions, K, "K",
                      (lambda: sample_initial_component_means(params, K)) if initial_means is None else initial_means,
                      params.initial_covariance if initial_covariances is None else initial_covariances, carry, inputs, fields,
@@ -507,7 +524,10 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
         od.coll_cov.ptr, od.coll_cov.sB, od.coll_cov.sK, od.coll_cov.sT, od.coll_cov.sE = coll[1].data_ptr(), T * n * n, 0, n * n, 1
         coll = (tuple(k.unwrap(v) for v in coll),)
     # (_uparams: the unscented bank -- same carry / streams, sigma-point moment matching instead of Jacobians)
-    fn, head = (lib.bf_gsf_ekf_f32, ()) if _uparams is None else (lib.bf_ugsf_ukf_f32, (C.byref(_uparams),))
+    if _uparams is None:
+        fn, head = (lib.bf_gsf_ekf_missing_f32 if gaps else lib.bf_gsf_ekf_f32), ()
+    else:
+        fn, head = (lib.bf_ugsf_ukf_missing_f32 if gaps else lib.bf_ugsf_ukf_f32), (C.byref(_uparams),)
     _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
     _lib.check(fn(C.byref(k.mdl.c), *head, C.byref(k.yd), C.byref(k.ud), B, T, K, C.byref(k.cr), C.byref(od),
                   C.c_void_p(k.stream)))
@@ -517,7 +537,8 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
 def unscented_gaussian_sum_filter(params, uparams, emissions, num_components: int = 1, num_iter: int = 1, inputs=None, *,
                                   initial_means=None, initial_covariances=None, carry=None,
                                   fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
-                                  return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None):
+                                  return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None,
+                                  missing=None, observed=None):
     """Unscented Gaussian-sum filter (bank of K unscented Kalman filters with non-additive noise +
     weight update), gaussfiltax/inference.py:379-456, on the HIP engine.
 
@@ -529,11 +550,14 @@ def unscented_gaussian_sum_filter(params, uparams, emissions, num_components: in
     State, noise and observation dimensions up to 8 run with the state in registers (at most 256 components); anything larger
     runs on the run-time-dimension kernel (state in LDS, any number of components, bounded by 160 KiB of LDS: about n = 70 with
     n / 2 observations).  ``options={"ugsf_force_generic": 1}`` sends a small model through that kernel too.
+
+    ``missing`` / ``observed``: NaN entries as gaps, as in :func:`gaussian_sum_filter` (``bf_ugsf_ukf_missing_f32``: the sigma
+    points are those of the full augmented state, the update reads the observed rows only; every dimension <= 8).
     """
     return gaussian_sum_filter(params, emissions, num_components, num_iter, inputs, initial_means=initial_means,
                                initial_covariances=initial_covariances, carry=carry, fields=fields, layout=layout, out=out,
                                return_loglik=return_loglik, return_carry=return_carry, device=device, options=options,
-                               _uparams=_ukf_params(uparams))
+                               _uparams=_ukf_params(uparams), missing=missing, observed=observed)
 
 
 def speedy_augmented_gaussian_sum_filter(params, emissions, num_components, rng_key=None, num_iter: int = 1,

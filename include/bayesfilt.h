@@ -165,7 +165,7 @@ int bf_device_count(void);
  *                   and serves particle counts up to 4 096 with registry functions.
  * bf_set_option changes the PROCESS-WIDE default.  A library or a thread that must not disturb -- or be disturbed by -- other
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
- * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_missing_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
+ * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_missing_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_gsf_ekf_missing_f32, bf_ugsf_ukf_missing_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
  * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_rts_smoother_pscan_f32, bf_eks_smoother_f32,
  * bf_ffbs_sample_f32, bf_ffbs_sample_pscan_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_gs_smoother_f32, bf_gs_sample_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
@@ -315,6 +315,29 @@ int bf_gsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream*
  * BF_EUNSUPPORTED with the byte count when a workgroup's 160 KiB of LDS do not hold the model (n = 68 with n / 2 observations fits). */
 int bf_ugsf_ukf_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* y, const bf_cstream* u,
                     int64_t B, int64_t T, int32_t K, const bf_carry* carry, const bf_out_desc* out, void* stream);
+
+/* The two Gaussian-sum filters on series with gaps: a NaN y(b, t, a) means "component a was not observed at step t" (the
+ * convention of bf_kalman_filter_missing_f32, per component of the bank).  Arguments of their plain twins.  With o the
+ * components of the step that are not NaN, every component k conditions on the rows o only -- extended nodes: H_x[o, :],
+ * h(x)[o], (H_r R H_r^T)[o, o], state-dependent H_r included, the jitter on every entry of the reduced S_oo; unscented nodes:
+ * the sigma points of the full augmented state with mu, S and C restricted to the rows o -- and ll_k = log N(v_o; 0, S_oo)
+ * with |o| in the log 2 pi term.  The weights go through the unchanged reweight with those ll_k.  o empty: every ll_k is 0,
+ * means and covariances are untouched exactly, the weights are renormalised only (K = 1: exactly 1); the predict always runs,
+ * so trailing unobserved steps are a forecast.  Only a NaN in y means missing: what the model computes for a missing row is
+ * discarded by selects, so a NaN or Inf produced there does not leak; +-Inf in y, or a non-finite innovation of an observed
+ * component, poisons as in the plain entry points (which keep reading a NaN as poison: these two are opt-in).  Collapsed
+ * streams and per-step Q / R tables work as on the plain route where its register kernels produce them.
+ * Register kernels only, and no fallback.  BF_EUNSUPPORTED, with a message that names the limit: flags != 0 (legacy classes);
+ * registry models with n > 8 or m > 4 (bf_gsf_ekf_missing_f32: the matrix-core and run-time-dimension kernels take no gaps) or
+ * m > n; models from source that the register kernel does not take (a log-density, a dimension above 8, K > 256, collapsed
+ * streams); unscented models with a dimension above 8 or K > 256; "force_generic" / "ugsf_force_generic" set; a "kf_lanes"
+ * other than 0 or the compiled default for n.  BF_EINVAL: NULL arguments, non-positive sizes, what the plain twins refuse of
+ * the model and the carry.  "kf_emit_mode" and "gsf_structured" are honoured.  Every check precedes the first HIP call.
+ * With these two, this header declares 48 entry points. */
+int bf_gsf_ekf_missing_f32(const bf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t K,
+                           const bf_carry* carry, const bf_out_desc* out, void* stream);
+int bf_ugsf_ukf_missing_f32(const bf_model* model, const bf_ukf_params* uparams, const bf_cstream* y, const bf_cstream* u,
+                            int64_t B, int64_t T, int32_t K, const bf_carry* carry, const bf_out_desc* out, void* stream);
 
 /* Batched "speedy" augmented Gaussian-sum filter: replaces the lax.scan of
  * speedy_augmented_gaussian_sum_filter (inference.py:621-812).  num_components = (N0, N1, N2): every
