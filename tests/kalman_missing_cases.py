@@ -43,14 +43,15 @@ def row_reduced(a, keep):
     return r
 
 
-def observed_mask(B, T, m, seed=11):
+def observed_mask(B, T, m, seed=11, wholly_missing_at=None):
     """(B, T, m) bool, true = observed.  Every trajectory but the fixed ones: about 30 % of the entries missing
-    independently, step 0 missing, one wholly missing step (T // 2), the last FORECAST steps missing.  Trajectory FULL is
-    fully observed, NONE has nothing observed, NO_COMP1 lacks component 1 and nothing else (at m = 1: component 0, which leaves nothing)."""
+    independently, step 0 missing, one wholly missing step (``wholly_missing_at``, default T // 2), the last FORECAST steps
+    missing.  Trajectory FULL is fully observed, NONE has nothing observed, NO_COMP1 lacks component 1 and nothing else (at
+    m = 1: component 0, which leaves nothing)."""
     rng = np.random.default_rng(seed)
     mask = rng.random((B, T, m)) >= 0.3
     mask[:, 0] = False
-    mask[:, T // 2] = False
+    mask[:, T // 2 if wholly_missing_at is None else wholly_missing_at] = False
     mask[:, T - FORECAST:] = False
     if B > FULL:
         mask[FULL] = True
