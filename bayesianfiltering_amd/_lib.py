@@ -152,6 +152,9 @@ SYMBOLS = {
     "bf_bpf_f32": (C.c_int, [C.POINTER(bf_bpf_model), C.POINTER(bf_cstream), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
                              C.c_int32, C.POINTER(C.c_uint32), C.c_float, C.c_int32, C.POINTER(bf_bpf_carry),
                              C.POINTER(bf_bpf_out), C.c_void_p]),
+    "bf_bpf_missing_f32": (C.c_int, [C.POINTER(bf_bpf_model), C.POINTER(bf_cstream), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
+                                     C.c_int32, C.POINTER(C.c_uint32), C.c_float, C.c_int32, C.POINTER(bf_bpf_carry),
+                                     C.POINTER(bf_bpf_out), C.c_void_p]),
     "bf_sample_ssm_f32": (C.c_int, [C.POINTER(bf_bpf_model), C.c_void_p, C.POINTER(bf_cstream), C.c_int64, C.c_int64,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_resample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

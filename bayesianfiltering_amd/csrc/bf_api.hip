@@ -63,7 +63,7 @@ int launch_optimal_resample(const float* d_w, const uint32_t key[2], long long B
                             hipStream_t stream);
 int launch_bpf(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP,
                float ess, int resampler, const uint32_t key[2], const bf_bpf_carry* carry, const bf_bpf_out* o,
-               hipStream_t stream);
+               hipStream_t stream, bool missing);   // missing: the MISSING = true kernels (NaN observations are gaps)
 int launch_sample_ssm(const bf_bpf_model* bp, const uint32_t* d_keys, const bf_cstream* u, long long B, long long T,
                       float* d_states, float* d_emis, hipStream_t stream);
 int launch_resample(const float* d_w, const uint32_t* d_keys, long long B, int NP, int resampler, int* d_idx,
@@ -443,17 +443,33 @@ int bf_collapse_f32(const bf_stream* weights, const bf_stream* means, const bf_s
   return bf::launch_collapse(weights, means, covs, B, T, K, n, mean_out, cov_out, static_cast<hipStream_t>(stream));
 }
 
-int bf_bpf_f32(const bf_bpf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t N,
-               const uint32_t key[2], float ess_threshold, int32_t resampler, const bf_bpf_carry* carry,
-               const bf_bpf_out* out, void* stream) {
-  bf::CallOptionScope call_option_scope;
+// the argument checks of the two particle-filter entry points, before any HIP call
+static int check_bpf_call(const bf_bpf_model* model, const bf_cstream* y, int64_t B, int64_t T, int32_t N, const uint32_t key[2],
+                          int32_t resampler, const bf_bpf_carry* carry, const bf_bpf_out* out) {
   if (!model || !y || !out || !key) return bf::set_error(BF_EINVAL, "NULL argument");
   if (B <= 0 || T <= 0 || N <= 0) return bf::set_error(BF_EINVAL, "B, T and N must be positive");
   if (!y->ptr) return bf::set_error(BF_EINVAL, "observations pointer is NULL");
   if (!model->ssm.Q || !model->m0 || !model->P0 || !model->lp_cov) return bf::set_error(BF_EINVAL, "Q, m0, P0, lp_cov are required");
   if (resampler != 0 && resampler != 1) return bf::set_error(BF_EINVAL, "resampler must be 0 (multinomial) or 1 (systematic)");
   if (carry && carry->x_in && !carry->w_in) return bf::set_error(BF_EINVAL, "carry.x_in needs carry.w_in");
-  return bf::launch_bpf(model, y, u, B, T, N, ess_threshold, resampler, key, carry, out, static_cast<hipStream_t>(stream));
+  return BF_OK;
+}
+
+int bf_bpf_f32(const bf_bpf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t N,
+               const uint32_t key[2], float ess_threshold, int32_t resampler, const bf_bpf_carry* carry,
+               const bf_bpf_out* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  if (int rc = check_bpf_call(model, y, B, T, N, key, resampler, carry, out)) return rc;
+  return bf::launch_bpf(model, y, u, B, T, N, ess_threshold, resampler, key, carry, out, static_cast<hipStream_t>(stream), false);
+}
+
+// Missing observations (NaN entries of y) on every route of the particle filter: the same dispatch, the MISSING = true kernels.
+int bf_bpf_missing_f32(const bf_bpf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t N,
+                       const uint32_t key[2], float ess_threshold, int32_t resampler, const bf_bpf_carry* carry,
+                       const bf_bpf_out* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  if (int rc = check_bpf_call(model, y, B, T, N, key, resampler, carry, out)) return rc;
+  return bf::launch_bpf(model, y, u, B, T, N, ess_threshold, resampler, key, carry, out, static_cast<hipStream_t>(stream), true);
 }
 
 int bf_sample_ssm_f32(const bf_bpf_model* model, const uint32_t* d_keys, const bf_cstream* u, int64_t B, int64_t T,

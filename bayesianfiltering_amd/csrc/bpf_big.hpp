@@ -117,17 +117,36 @@ __device__ __forceinline__ int draw_ancestor(U32x2 kc, int resampler, float tota
 
 // one particle through the dynamics with its own noise draw (inference.py:1342-1345: q = q0 + chol(Q) z from the
 // particle's key), written back in place, and its emission log-density (:1348-1349)
-template <int N, int DQ, int M, class SP = SpecRuntime>
-__device__ __forceinline__ float propagate_particle(const BpfModel<N, DQ, M>& mdl, U32x2 ki, float* xp, float u0, const float* yv) {
+// (MISSING: the log-density of the observed components, from the step's pattern and step density: emission_loglik_missing)
+template <int N, int DQ, int M, class SP = SpecRuntime, bool MISSING = false>
+__device__ __forceinline__ float propagate_particle(const BpfModel<N, DQ, M>& mdl, U32x2 ki, float* xp, float u0, const float* yv,
+                                                    const float* sdens = nullptr, uint64_t obs = 0) {
   float x[N], q[DQ], xn[N];
   BF_UNROLL for (int d = 0; d < N; ++d) x[d] = xp[d];
   draw_dynamics_noise<N, DQ, M, SP>(mdl, ki, q);
   dyn_value<N, DQ, M, SP>(mdl, x, q, u0, xn);       // (SP::user_dyn / user_emi / user_lp: the caller's functions from source)
   BF_UNROLL for (int d = 0; d < N; ++d) xp[d] = xn[d];
-  return emission_loglik<N, DQ, M, SP>(mdl, xn, u0, yv);
+  if constexpr (MISSING) return emission_loglik_missing<N, DQ, M, SP>(mdl, sdens, obs, xn, u0, yv);
+  else return emission_loglik<N, DQ, M, SP>(mdl, xn, u0, yv);
 }
 
-template <int N, int DQ, int M, class SP = SpecRuntime>
+// MISSING kernels with the particles in HBM: the observation pattern of a step, and the step density of a partly observed
+// step of a Gaussian density from thread 0 into `sdens` (LDS).  Every thread of the workgroup calls it; the previous readers of
+// `sdens` are a barrier back.  Every thread read the same y, so the pattern is the same in every lane; the readfirstlane says so
+// to the compiler, and the barrier below stands in control flow that is convergent by construction.
+template <int N, int DQ, int M, class SP>
+__device__ __forceinline__ uint64_t bpf_step_pattern(const BpfModel<N, DQ, M>* mdlp, const float* yv, float* sdens) {
+  const uint64_t o = bpf_observed_bits<M>(yv);
+  const uint64_t obs = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)o) |
+                       ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o >> 32)) << 32);
+  if (!SP::user_lp && obs != 0ull && obs != bpf_all_observed<M>()) {
+    if (threadIdx.x == 0) bpf_step_density<M>(bpf_model_lp_cov(mdlp), obs, sdens);
+    lds_barrier();
+  }
+  return obs;
+}
+
+template <int N, int DQ, int M, class SP = SpecRuntime, bool MISSING = false>
 __device__ __forceinline__ void
 bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* __restrict__ uptr, long long u_sB, long long u_sT,
              BpfCarry carry, BpfOut out, BigScratch sc, long long B, long long T, int NP, float ess_threshold, int resampler,
@@ -141,6 +160,11 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
 
   __shared__ float red[64];           // [0, 16) scan totals, [32, 49) reductions
   __shared__ float cpart[BIG_MAXCH];  // per-chunk partial results (max / sums / CDF totals)
+  float* sdens = nullptr;             // MISSING: the step density of a partly observed step
+  if constexpr (MISSING) {
+    __shared__ float sdens_[bpf_density_words(M)];
+    sdens = sdens_;
+  }
   float* xa = sc.xa + b * (long long)NP * N;
   float* xb = sc.xb + b * (long long)NP * N;
   float* gw = sc.w + b * (long long)NP;
@@ -158,6 +182,8 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
     float yv[M];
     BF_UNROLL for (int a = 0; a < M; ++a) yv[a] = y.p[b * y.sB + t * y.sT + a * y.sE];
     const float u0 = uptr ? uptr[b * u_sB + t * u_sT] : 0.f;
+    uint64_t obs = 0;
+    if constexpr (MISSING) obs = bpf_step_pattern<N, DQ, M, SP>(mdlp, yv, sdens);
 
     // ---- pass 1: propagate, log-weight, chunk maxima
     for (int c = 0; c < nch; ++c) {
@@ -166,7 +192,7 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
       float ll = -__builtin_inff();
       if (valid) {
         const U32x2 ki = threefry_split(k.x, k.y, (uint32_t)i + 1u, (uint32_t)NP + 1u);
-        ll = propagate_particle<N, DQ, M, SP>(mdl, ki, xa + (long long)i * N, u0, yv);
+        ll = propagate_particle<N, DQ, M, SP, MISSING>(mdl, ki, xa + (long long)i * N, u0, yv, sdens, obs);
         gl[i] = ll;
       }
       const float cm = block_tree_reduce<BIG_NW>(ll, red + 32, BpfMax());
@@ -300,12 +326,12 @@ bpf_big_body(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* 
   }
 }
 
-template <int N, int DQ, int M>
+template <int N, int DQ, int M, bool MISSING = false>
 __global__ void __launch_bounds__(BIG_NT)
 bpf_big_kernel(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* __restrict__ uptr, long long u_sB, long long u_sT,
                BpfCarry carry, BpfOut out, BigScratch sc, long long B, long long T, int NP, float ess_threshold, int resampler,
                uint32_t key0, uint32_t key1) {
-  bpf_big_body<N, DQ, M, SpecRuntime>(mdlp, y, uptr, u_sB, u_sT, carry, out, sc, B, T, NP, ess_threshold, resampler, key0, key1);
+  bpf_big_body<N, DQ, M, SpecRuntime, MISSING>(mdlp, y, uptr, u_sB, u_sT, carry, out, sc, B, T, NP, ess_threshold, resampler, key0, key1);
 }
 
 #ifndef BF_JIT
@@ -339,7 +365,7 @@ static inline BpfInputs bpf_inputs(const bf_cstream* y, const bf_cstream* u) {
   return BpfInputs{CView{y->ptr, y->sB, y->sT, y->sE}, (u && u->ptr) ? u->ptr : nullptr, u ? u->sB : 0, u ? u->sT : 0};
 }
 
-template <int N, int DQ, int M>
+template <int N, int DQ, int M, bool MISSING = false>
 static inline int launch_bpf_big_dims(const BpfModel<N, DQ, M>* d_mdl, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
                                  int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out,
                                  hipStream_t stream) {
@@ -348,7 +374,7 @@ static inline int launch_bpf_big_dims(const BpfModel<N, DQ, M>* d_mdl, const bf_
   const int rc = prepare_bpf_big(N, B, NP, stream, sc, &buf);
   if (rc != BF_OK) return rc;
   const BpfInputs in = bpf_inputs(y, u);
-  hipLaunchKernelGGL((bpf_big_kernel<N, DQ, M>), dim3((unsigned)B), dim3(BIG_NT), 0, stream, d_mdl, in.y, in.u, in.u_sB, in.u_sT, cr, out,
+  hipLaunchKernelGGL((bpf_big_kernel<N, DQ, M, MISSING>), dim3((unsigned)B), dim3(BIG_NT), 0, stream, d_mdl, in.y, in.u, in.u_sB, in.u_sT, cr, out,
                      sc, B, T, NP, ess, resampler, key[0], key[1]);
   const hipError_t le = hipGetLastError();
   const hipError_t fe = hipFreeAsync(buf, stream);

@@ -47,26 +47,32 @@ int launch_resample(const float* d_w, const uint32_t* d_keys, long long B, int N
 BF_DECL(launch_bpf_group_a);
 BF_DECL(launch_bpf_group_b);
 BF_DECL(launch_bpf_group_c);
+BF_DECL(launch_bpf_missing_group_a);   // the MISSING = true instances of the same rows (bpf_missing_group_{a,b,c}.hip)
+BF_DECL(launch_bpf_missing_group_b);
+BF_DECL(launch_bpf_missing_group_c);
 #undef BF_DECL
 
 // The particle filter built at run time (user_model.hpp): around the functions of a handle from source (the caller's functions
 // see the CANONICAL arithmetic of the weight path, so a function written like its registry twin gives the registry twin's bits),
 // or -- an internal handle without sources -- around the registry's, for dimensions without a compiled instance and for
 // bf_set_option "bpf_arith" = 1.  State in registers at the compile-time dimensions of the handle, one kernel per particle
-// capacity; beyond the register capacities the particles live in HBM (bpf_big.hpp), up to 2^20 per trajectory.
+// capacity; beyond the register capacities the particles live in HBM (bpf_big.hpp), up to 2^20 per trajectory.  missing: the
+// MISSING = true twins (JIT_BPF_MISSING, JIT_BPF_BIG_MISSING: kernels of their own in the handle's map and in the on-disk cache).
 static int launch_bpf_jit(const bf_user_model* um, const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
-                          int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out, hipStream_t stream) {
+                          int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out, hipStream_t stream,
+                          bool missing) {
   int rc = check_user_model(um, &bp->ssm);
   if (rc != BF_OK || (rc = check_user_device(um)) != BF_OK) return rc;
   const int N = bp->ssm.n;
   BpfModelLaunch L;
-  if ((rc = prepare_bpf_model(bp, um->user_flags(), stream, L)) != BF_OK) return rc;
+  if ((rc = prepare_bpf_model(bp, um->user_flags(), stream, L, missing)) != BF_OK) return rc;
   // registry models (the hardware-arithmetic build): the model structure as a compile-time spec where bpf_scan.hpp has one
   const int spec = !um->hw_arith ? JIT_SPEC_USER : (L.l96_pick ? JIT_SPEC_L96_PICK : JIT_SPEC_RUNTIME);
   int ppt, nw;
   bpf_capacity(NP, N, &ppt, &nw);
   hipFunction_t fn = nullptr;
-  if ((rc = user_kernel(um, ppt == 0 ? JIT_BPF_BIG : JIT_BPF, ppt, ppt == 0 ? 0 : nw, spec, &fn)) != BF_OK) return rc;
+  const int kind = ppt == 0 ? (missing ? JIT_BPF_BIG_MISSING : JIT_BPF_BIG) : (missing ? JIT_BPF_MISSING : JIT_BPF);
+  if ((rc = user_kernel(um, kind, ppt, ppt == 0 ? 0 : nw, spec, &fn)) != BF_OK) return rc;
   if (ppt == 0) {
     BigScratch sc;
     float* buf = nullptr;
@@ -82,7 +88,7 @@ static int launch_bpf_jit(const bf_user_model* um, const bf_bpf_model* bp, const
     BF_HIP_CHECK(fe);
     return BF_OK;
   }
-  const size_t lds_bytes = bpf_lds_bytes(N, ppt, nw);
+  const size_t lds_bytes = bpf_lds_bytes(N, ppt, nw, missing ? bpf_density_words(bp->ssm.m) : 0);
   if (lds_bytes > 160 * 1024) return set_error(BF_EUNSUPPORTED, "particle tile exceeds the 160 KiB LDS");
   struct { const void* mdl; BpfArgs<1, 1, 1> a; } packed;   // the kernarg segment: the model pointer, then the struct
   packed.mdl = L.d_mdl;
@@ -95,27 +101,27 @@ static int launch_bpf_jit(const bf_user_model* um, const bf_bpf_model* bp, const
 
 int launch_bpf(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP,
                float ess, int resampler, const uint32_t key[2], const bf_bpf_carry* carry, const bf_bpf_out* o,
-               hipStream_t stream) {
+               hipStream_t stream, bool missing) {
   const BpfCarry cr = make_bpf_carry(carry);
   const BpfOut out = make_bpf_out(o);
   if (bp->ssm.user)   // functions from the caller's source: the kernel compiled at run time for this model
-    return launch_bpf_jit(bp->ssm.user, bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
+    return launch_bpf_jit(bp->ssm.user, bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, missing);
   if (bp->ssm.dyn_id == BF_FN_USER || bp->ssm.emi_id == BF_FN_USER)
     return set_error(BF_EINVAL, "dyn_id / emi_id = BF_FN_USER needs bf_model.user (bf_user_model_create)");
   bool matched = false;
   int rc = BF_OK;
   if (g_bpf_arith != 1) {   // (1: the same kernel with the hardware's transcendentals, compiled at run time)
-    rc = launch_bpf_group_a(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
+    rc = (missing ? launch_bpf_missing_group_a : launch_bpf_group_a)(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
     if (matched) return rc;
-    rc = launch_bpf_group_b(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
+    rc = (missing ? launch_bpf_missing_group_b : launch_bpf_group_b)(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
     if (matched) return rc;
-    rc = launch_bpf_group_c(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
+    rc = (missing ? launch_bpf_missing_group_c : launch_bpf_group_c)(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
     if (matched) return rc;
   }
   // hardware arithmetic, or no compiled instance for these dimensions: the same kernel, compiled now (needs hiprtc)
   const bf_user_model* um = registry_jit_handle(&bp->ssm, g_bpf_arith == 1);
   if (!um) return set_error(BF_ENOGPU, "no current device");
-  return launch_bpf_jit(um, bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
+  return launch_bpf_jit(um, bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, missing);
 }
 
 }  // namespace bf

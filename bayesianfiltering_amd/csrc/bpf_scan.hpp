@@ -253,7 +253,9 @@ struct BpfArgs {
 // The kernel proper, as a device function: every kernel entry that runs it -- bpf_scan_kernel below, the `extern "C"` entries
 // of a build compiled at run time with a caller's functions (jit_source.hip) -- has the parameter list
 // (const BpfModel*, BpfArgs by value), which is what the kernarg-segment reads below rely on.
-template <int N, int DQ, int M, int PPT, int NW, class SP = SpecRuntime>
+// MISSING: NaN entries of y are components that were not observed (bpf_missing.hpp; emission_loglik_missing); everything else
+// of a step -- the keys it consumes, the reweight, the resampling decision -- is the plain kernel's.
+template <int N, int DQ, int M, int PPT, int NW, class SP = SpecRuntime, bool MISSING = false>
 __device__ __forceinline__ void bpf_scan_body(const BpfModel<N, DQ, M>* __restrict__ mdlp) {
   // `ka[fresh()]`: the argument struct as it lies in the kernarg segment (behind the model pointer, which stays a
   // `__restrict__` parameter of its own: that is what lets the compiler read the model with scalar loads), behind an
@@ -284,6 +286,7 @@ __device__ __forceinline__ void bpf_scan_body(const BpfModel<N, DQ, M>* __restri
   float* red = lds + CW;            // cross-wave scratch: [0, 16) and [32, 48) the two slot groups of block_reduce, [16, 32) the CDF's wave totals
   float* mpart = lds + CW + 64;     // NW * N floats: per-wave partial sums of the weighted-mean summary
   float* tile = mpart + ((NW * N + 3) & ~3);   // CAP * DCH floats (gather tile)
+  float* sdens = tile + CAP * DCH;             // MISSING: bpf_density_words(M) floats, the step density of a partly observed step
 
   // ---- workgroup reductions in the oracle's adjacent-pair tree order
   auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
@@ -373,6 +376,18 @@ __device__ __forceinline__ void bpf_scan_body(const BpfModel<N, DQ, M>* __restri
       BF_UNROLL for (int a = 0; a < M; ++a) yv[a] = y.p[b * y.sB + t * y.sT + a * y.sE];
       u0 = a_.uptr ? a_.uptr[b * a_.u_sB + t * a_.u_sT] : 0.f;
     }
+    // MISSING: the step's observation pattern, the same in every lane.  A partly observed step of a Gaussian density gets its
+    // step density from thread 0 (its last readers, the previous step's particle loop, are the reductions' barriers back; a
+    // workgroup of one wave runs its LDS operations in order)
+    uint64_t obs = 0;
+    if constexpr (MISSING) {
+      const uint64_t o = bpf_observed_bits<M>(yv);
+      obs = (uint64_t)uniform_u((uint32_t)o) | ((uint64_t)uniform_u((uint32_t)(o >> 32)) << 32);
+      if (!SP::user_lp && obs != 0ull && obs != bpf_all_observed<M>()) {
+        if (tid == 0) bpf_step_density<M>(bpf_model_lp_cov(mdlp), obs, sdens);
+        lds_barrier();
+      }
+    }
 
     // ---- propagate (inference.py:1342-1345, models.py:82-84) and log-weight (:1348-1349)
     const U32x2 nk = threefry_split(k0, k1, 0u, (uint32_t)NP + 1u);  // next_key = keys[0]
@@ -420,20 +435,23 @@ __device__ __forceinline__ void bpf_scan_body(const BpfModel<N, DQ, M>* __restri
               __builtin_amdgcn_sched_barrier(0);
             }
           }
-          llp = emission_loglik<N, DQ, M, SP>(mdl, x[p], u0, yv);
+          if constexpr (MISSING) llp = emission_loglik_missing<N, DQ, M, SP>(mdl, sdens, obs, x[p], u0, yv);
+          else llp = emission_loglik<N, DQ, M, SP>(mdl, x[p], u0, yv);
         } else {
           float q[DQ];
           draw_dynamics_noise<N, DQ, M, SP>(mdl, ki, q);
           dyn_value<N, DQ, M, SP>(mdl, x[p], q, u0, xn);
           BF_UNROLL for (int d = 0; d < N; ++d) x[p][d] = xn[d];
-          llp = emission_loglik<N, DQ, M, SP>(mdl, xn, u0, yv);
+          if constexpr (MISSING) llp = emission_loglik_missing<N, DQ, M, SP>(mdl, sdens, obs, xn, u0, yv);
+          else llp = emission_loglik<N, DQ, M, SP>(mdl, xn, u0, yv);
         }
       } else {
         float q[DQ];
         draw_dynamics_noise<N, DQ, M, SP>(mdl, ki, q);
         dyn_value<N, DQ, M, SP>(mdl, x[p], q, u0, xn);
         BF_UNROLL for (int d = 0; d < N; ++d) x[p][d] = xn[d];
-        llp = emission_loglik<N, DQ, M, SP>(mdl, xn, u0, yv);
+        if constexpr (MISSING) llp = emission_loglik_missing<N, DQ, M, SP>(mdl, sdens, obs, xn, u0, yv);
+        else llp = emission_loglik<N, DQ, M, SP>(mdl, xn, u0, yv);
       }
       ll[p] = valid[p] ? llp : -__builtin_inff();
       // one particle at a time: interleaving the PPT independent Threefry / erfinv chains overruns the
@@ -574,11 +592,11 @@ __device__ __forceinline__ void bpf_scan_body(const BpfModel<N, DQ, M>* __restri
   }
 }
 
-template <int N, int DQ, int M, int PPT, int NW, class SP = SpecRuntime>
+template <int N, int DQ, int M, int PPT, int NW, class SP = SpecRuntime, bool MISSING = false>
 __global__ void __launch_bounds__(64 * NW)
 bpf_scan_kernel(const BpfModel<N, DQ, M>* __restrict__ mdlp, const BpfArgs<N, DQ, M> args_by_value) {
   (void)args_by_value;   // (read from the kernarg segment inside)
-  bpf_scan_body<N, DQ, M, PPT, NW, SP>(mdlp);
+  bpf_scan_body<N, DQ, M, PPT, NW, SP, MISSING>(mdlp);
 }
 
 #ifndef BF_JIT   // host side: launches
@@ -602,10 +620,11 @@ static inline void bpf_capacity(int NP, int n, int* ppt, int* nw) {
   else if (NP <= 4096 && n <= 16) { *ppt = 4; *nw = 16; }
   else { *ppt = 0; *nw = 16; }
 }
-// dynamic LDS of a launch: CDF, reduction scratch, per-wave means, the gather tile (DCH state dimensions per pass)
-static inline size_t bpf_lds_bytes(int n, int ppt, int nw) {
+// dynamic LDS of a launch: CDF, reduction scratch, per-wave means, the gather tile (DCH state dimensions per pass), and behind
+// them the step density of the MISSING kernels (density_words = bpf_density_words(m))
+static inline size_t bpf_lds_bytes(int n, int ppt, int nw, int density_words = 0) {
   const int cap = 64 * nw * ppt, dch = (ppt >= 16) ? 1 : ((n >= 8) ? 8 : n);
-  return sizeof(float) * (size_t)(((cdf_words(cap) + 3) & ~3) + 64 + ((nw * n + 3) & ~3) + cap * dch);
+  return sizeof(float) * (size_t)(((cdf_words(cap) + 3) & ~3) + 64 + ((nw * n + 3) & ~3) + cap * dch + density_words);
 }
 // the argument struct, which does not depend on the dimensions (BpfArgs<1, 1, 1> for a kernel built at run time)
 template <int N, int DQ, int M>
@@ -626,9 +645,12 @@ struct BpfModelLaunch {
   const void* d_mdl;
   bool l96_pick;
 };
-static inline int prepare_bpf_model(const bf_bpf_model* bp, int user_flags, hipStream_t stream, BpfModelLaunch& L) {
+// missing: the model of a MISSING kernel, with the log-density's covariance behind the struct (bpf_model_lp_cov)
+static inline int prepare_bpf_model(const bf_bpf_model* bp, int user_flags, hipStream_t stream, BpfModelLaunch& L, bool missing = false) {
   const bf_model* p = &bp->ssm;
-  std::vector<uint32_t> words(bpf_model_words(p->n, p->dq, p->m), 0u);   // zeroed: the constant cache compares contents
+  const size_t nw_model = bpf_model_words(p->n, p->dq, p->m);
+  std::vector<uint32_t> words(nw_model + (missing ? (size_t)p->m * p->m : 0), 0u);   // zeroed: the constant cache compares contents
+  if (missing && !(user_flags & 4)) std::memcpy(words.data() + nw_model, bp->lp_cov, sizeof(float) * (size_t)p->m * p->m);
   const BpfModelView v = bpf_model_view_flat(words.data(), p->n, p->dq, p->m);
   const int rc = fill_bpf_model_view(bp, v, user_flags, bp->lp_theta, bp->n_lp_theta);
   if (rc != BF_OK) return rc;
@@ -637,15 +659,15 @@ static inline int prepare_bpf_model(const bf_bpf_model* bp, int user_flags, hipS
   return device_constants(words.data(), sizeof(uint32_t) * words.size(), stream, &L.d_mdl);
 }
 
-template <int N, int DQ, int M, int PPT, int NW, class SP = SpecRuntime>
+template <int N, int DQ, int M, int PPT, int NW, class SP = SpecRuntime, bool MISSING = false>
 static inline int launch_bpf_cfg(const BpfModel<N, DQ, M>* d_mdl, const bf_cstream* y, const bf_cstream* u, long long B,
                           long long T, int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr,
                           const BpfOut& out, hipStream_t stream) {
-  const size_t lds_bytes = bpf_lds_bytes(N, PPT, NW);
+  const size_t lds_bytes = bpf_lds_bytes(N, PPT, NW, MISSING ? bpf_density_words(M) : 0);
   if (lds_bytes > 160 * 1024) return set_error(BF_EUNSUPPORTED, "particle tile exceeds the 160 KiB LDS");
   BpfArgs<N, DQ, M> a;
   fill_bpf_args(a, y, u, B, T, NP, ess, resampler, key, cr, out);
-  auto kern = bpf_scan_kernel<N, DQ, M, PPT, NW, SP>;
+  auto kern = bpf_scan_kernel<N, DQ, M, PPT, NW, SP, MISSING>;
   if (lds_bytes > 64 * 1024)
     BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64 * NW), lds_bytes, stream, d_mdl, a);
@@ -658,31 +680,31 @@ extern Option g_bpf_hbm_mode;  // bf_set_option "bpf_hbm_mode": 0 = choose, 1 = 
 extern Option g_bpf_spec;      // bf_set_option "bpf_spec": 1 = compile-time model structure where an instance exists (default), 0 = off
 
 // bpf_big.hpp / bpf_wide.hpp: particle counts beyond the in-register capacities (declared here, defined after the kernels there)
-template <int N, int DQ, int M>
+template <int N, int DQ, int M, bool MISSING = false>
 static inline int launch_bpf_hbm_dims(const BpfModel<N, DQ, M>* d_mdl, const bf_cstream* y, const bf_cstream* u, long long B,
                                       long long T, int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr,
                                       const BpfOut& out, hipStream_t stream);
 
-template <int N, int DQ, int M>
+template <int N, int DQ, int M, bool MISSING = false>
 static inline int launch_bpf_dims(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
                            int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out,
                            hipStream_t stream) {
   static_assert(sizeof(BpfModel<N, DQ, M>) == 4 * bpf_model_words(N, DQ, M), "BpfModel: 4-byte members in declaration order, no padding");
   BpfModelLaunch L;
-  const int rc = prepare_bpf_model(bp, 0, stream, L);
+  const int rc = prepare_bpf_model(bp, 0, stream, L, MISSING);
   if (rc != BF_OK) return rc;
   const BpfModel<N, DQ, M>* d_mdl = static_cast<const BpfModel<N, DQ, M>*>(L.d_mdl);
   // few trajectories with thousands of particles: one workgroup per trajectory would leave the chip idle (a step of the
   // in-register kernel takes ~19 us per 1024 particles on its one CU); the workgroup-per-chunk kernels of bpf_wide.hpp
   // spread the particles over the CUs at ~25 us of launches per step
   const bool spread = NP > 2048 && B <= 32 && g_bpf_hbm_mode != 1;
-  if (spread) return launch_bpf_hbm_dims<N, DQ, M>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
+  if (spread) return launch_bpf_hbm_dims<N, DQ, M, MISSING>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
   int ppt, nw;
   bpf_capacity(NP, N, &ppt, &nw);
   // the compiled instance of that capacity, for the model's structure as a run-time (SpecRuntime) or compile-time (SpecFixed) property
   auto by_capacity = [&](auto spec) -> int {
     using SP = decltype(spec);
-#define BF_CFG(PPT_, NW_) return launch_bpf_cfg<N, DQ, M, PPT_, NW_, SP>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream)
+#define BF_CFG(PPT_, NW_) return launch_bpf_cfg<N, DQ, M, PPT_, NW_, SP, MISSING>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream)
     if (ppt == 1 && nw == 1) BF_CFG(1, 1);
     if (ppt == 1 && nw == 2) BF_CFG(1, 2);
     if (ppt == 1 && nw == 4) BF_CFG(1, 4);
@@ -700,7 +722,7 @@ static inline int launch_bpf_dims(const bf_bpf_model* bp, const bf_cstream* y, c
       if constexpr (N <= 4 && DQ <= 4) BF_CFG(16, 16);
     }
 #undef BF_CFG
-    return launch_bpf_hbm_dims<N, DQ, M>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);  // particles in HBM (bpf_big.hpp, bpf_wide.hpp)
+    return launch_bpf_hbm_dims<N, DQ, M, MISSING>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);  // particles in HBM (bpf_big.hpp, bpf_wide.hpp)
   };
   if constexpr (N == DQ && N >= 8 && 2 * M <= N + 1) {   // (bf_set_option "bpf_spec" = 0 turns the compile-time structure off)
     if (g_bpf_spec != 0 && L.l96_pick && NP <= 4096) return by_capacity(SpecFixed<DYN_LORENZ96, EMI_LINEAR, true, true, true, true>{});

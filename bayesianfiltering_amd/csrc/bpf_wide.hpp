@@ -59,7 +59,7 @@ wide_init_kernel(const BpfModel<N, DQ, M>* __restrict__ mdlp, BpfCarry carry, Wi
   }
 }
 
-template <int N, int DQ, int M>
+template <int N, int DQ, int M, bool MISSING = false>
 __global__ void __launch_bounds__(BIG_NT)
 wide_propagate_kernel(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, const float* __restrict__ uptr, long long u_sB, long long u_sT,
                       WideScratch sc, long long B, long long t, int NP) {
@@ -74,10 +74,17 @@ wide_propagate_kernel(const BpfModel<N, DQ, M>* __restrict__ mdlp, CView y, cons
   float yv[M];
   BF_UNROLL for (int a = 0; a < M; ++a) yv[a] = y.p[b * y.sB + t * y.sT + a * y.sE];
   const float u0 = uptr ? uptr[b * u_sB + t * u_sT] : 0.f;
+  float* sdens = nullptr;   // MISSING: the step density of a partly observed step, once per workgroup
+  uint64_t obs = 0;
+  if constexpr (MISSING) {
+    __shared__ float sdens_[bpf_density_words(M)];
+    sdens = sdens_;
+    obs = bpf_step_pattern<N, DQ, M, SpecRuntime>(mdlp, yv, sdens);
+  }
   float ll = -__builtin_inff();
   if (i < NP) {
     const U32x2 ki = threefry_split(k0, k1, (uint32_t)i + 1u, (uint32_t)NP + 1u);
-    ll = propagate_particle<N, DQ, M>(mdl, ki, x + (long long)i * N, u0, yv);
+    ll = propagate_particle<N, DQ, M, SpecRuntime, MISSING>(mdl, ki, x + (long long)i * N, u0, yv, sdens, obs);
     sc.s.ll[b * NP + i] = ll;
   }
   const float cm = block_tree_reduce<BIG_NW>(ll, red + 32, BpfMax());
@@ -242,7 +249,7 @@ __global__ void __launch_bounds__(BIG_NT) wide_carry_kernel(WideScratch sc, BpfC
   }
 }
 
-template <int N, int DQ, int M>
+template <int N, int DQ, int M, bool MISSING = false>
 static inline int launch_bpf_wide_dims(const BpfModel<N, DQ, M>* d_mdl, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
                                        int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out,
                                        hipStream_t stream) {
@@ -267,7 +274,7 @@ static inline int launch_bpf_wide_dims(const BpfModel<N, DQ, M>* d_mdl, const bf
   const dim3 grid((unsigned)nch, (unsigned)B), blk(BIG_NT);
   hipLaunchKernelGGL((wide_init_kernel<N, DQ, M>), grid, blk, 0, stream, d_mdl, cr, sc, B, NP, nch, nchp, key[0], key[1]);
   for (long long t = 0; t < T; ++t) {
-    hipLaunchKernelGGL((wide_propagate_kernel<N, DQ, M>), grid, blk, 0, stream, d_mdl, in.y, in.u, in.u_sB, in.u_sT, sc, B, t, NP);
+    hipLaunchKernelGGL((wide_propagate_kernel<N, DQ, M, MISSING>), grid, blk, 0, stream, d_mdl, in.y, in.u, in.u_sB, in.u_sT, sc, B, t, NP);
     hipLaunchKernelGGL(wide_weights_kernel, grid, blk, 0, stream, sc, NP, nchp);
     hipLaunchKernelGGL(wide_normalise_kernel, grid, blk, 0, stream, sc, NP, nchp);
     hipLaunchKernelGGL(wide_cdf_kernel, grid, blk, 0, stream, sc, NP, nchp, ess);
@@ -285,14 +292,14 @@ static inline int launch_bpf_wide_dims(const BpfModel<N, DQ, M>* d_mdl, const bf
 // particle counts beyond the in-register capacities: one workgroup per trajectory (bpf_big_kernel) when the batch
 // alone fills the chip, one workgroup per chunk (this file) otherwise.  bf_set_option("bpf_hbm_mode"): 0 = choose,
 // 1 = workgroup per trajectory, 2 = workgroup per chunk.  (Either launch refuses a count beyond the capacity: prepare_bpf_big.)
-template <int N, int DQ, int M>
+template <int N, int DQ, int M, bool MISSING>
 static inline int launch_bpf_hbm_dims(const BpfModel<N, DQ, M>* d_mdl, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
                                       int NP, float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out,
                                       hipStream_t stream) {
   const int hbm_mode = g_bpf_hbm_mode.load();
   const bool wide = B <= 65535 && (hbm_mode == 2 || (hbm_mode == 0 && B < 128));
-  if (wide) return launch_bpf_wide_dims<N, DQ, M>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
-  return launch_bpf_big_dims<N, DQ, M>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
+  if (wide) return launch_bpf_wide_dims<N, DQ, M, MISSING>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
+  return launch_bpf_big_dims<N, DQ, M, MISSING>(d_mdl, y, u, B, T, NP, ess, resampler, key, cr, out, stream);
 }
 
 }  // namespace bf

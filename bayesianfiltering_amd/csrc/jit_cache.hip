@@ -8,7 +8,9 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
+#include "elf_extent.hpp"
 #include "user_model.hpp"
 
 #ifndef BF_ARCH_NAME
@@ -192,7 +194,7 @@ int jit_load(const std::string& src, std::initializer_list<std::pair<const char*
     return le;
   };
   if (read_file(path, code)) {
-    e = load();
+    e = elf_image_is_whole(code.data(), code.size()) ? load() : hipErrorInvalidImage;   // (elf_extent.hpp: the loader takes no length)
     if (e != hipSuccess) {   // a file that does not load -- truncated, stale, foreign -- is deleted and rebuilt
       (void)hipGetLastError();
       if (e == hipErrorNoDevice || e == hipErrorInvalidDevice || dev < 0)

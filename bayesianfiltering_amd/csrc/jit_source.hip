@@ -167,6 +167,8 @@ const char* jit_entry_name(int kind, int variant) {
     case JIT_GS_FFBS_REGS: return "bf_user_gs_ffbs";
     case JIT_GS_RTS_REGS: return variant == 1 ? "bf_user_gs_rts_comp" : variant == 2 ? "bf_user_gs_rts_coll" : "bf_user_gs_rts_both";   // GS_COMP / GS_COLL / both
     case JIT_BPF: return "bf_user_bpf";
+    case JIT_BPF_MISSING: return "bf_user_bpf_missing";
+    case JIT_BPF_BIG_MISSING: return "bf_user_bpf_big_missing";
     case JIT_UGSF: return "bf_user_ugsf";
     case JIT_AGSF_UKF: case JIT_AGSF_EKF: return "bf_user_agsf";
     case JIT_GSF_REGS: return "bf_user_gsf_regs";
@@ -294,12 +296,12 @@ std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int s
          "variant, carry_records, tvq, tvr);\n}\n";
     return s;
   }
-  if (kind == JIT_BPF_BIG) {   // the particle filter with the particles in HBM (bpf_big.hpp): up to 2^20 particles per trajectory
+  if (kind == JIT_BPF_BIG || kind == JIT_BPF_BIG_MISSING) {   // the particle filter with the particles in HBM (bpf_big.hpp): up to 2^20 particles per trajectory
     s += kBpfBigSource;
-    s += "extern \"C\" __global__ void __launch_bounds__(1024) bf_user_bpf_big(const bf::BpfModel<BF_N, BF_DQ, BF_M>* __restrict__ mdlp, bf::CView y, "
+    s += std::string("extern \"C\" __global__ void __launch_bounds__(1024) ") + jit_entry_name(kind) + "(const bf::BpfModel<BF_N, BF_DQ, BF_M>* __restrict__ mdlp, bf::CView y, "
          "const float* __restrict__ uptr, long long u_sB, long long u_sT, bf::BpfCarry carry, bf::BpfOut out, bf::BigScratch sc, long long B, long long T, "
          "int NP, float ess_threshold, int resampler, uint32_t key0, uint32_t key1) {\n  bf::bpf_big_body<BF_N, BF_DQ, BF_M, " + spec +
-         ">(mdlp, y, uptr, u_sB, u_sT, carry, out, sc, B, T, NP, ess_threshold, resampler, key0, key1);\n}\n";
+         (kind == JIT_BPF_BIG_MISSING ? ", true" : "") + ">(mdlp, y, uptr, u_sB, u_sT, carry, out, sc, B, T, NP, ess_threshold, resampler, key0, key1);\n}\n";
     return s;
   }
   if (kind == JIT_SAMPLE) {   // NonlinearSSM.sample with the caller's functions (sample_ssm.hpp), a lane per trajectory
@@ -327,9 +329,10 @@ std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int s
          (ppt == 1 ? ", void, true" : "") + ">(mdlp, y, uptr, u_sB, u_sT, carry, out, B, T, K, KP, tvsq, tvsr);\n}\n";
     return s;
   }
-  s += "extern \"C\" __global__ void __launch_bounds__(" + std::to_string(64 * nw) + ") bf_user_bpf(const bf::BpfModel<BF_N, BF_DQ, BF_M>* __restrict__ mdlp, "
+  // (JIT_BPF or its MISSING = true twin)
+  s += "extern \"C\" __global__ void __launch_bounds__(" + std::to_string(64 * nw) + ") " + jit_entry_name(kind) + "(const bf::BpfModel<BF_N, BF_DQ, BF_M>* __restrict__ mdlp, "
        "const bf::BpfArgs<BF_N, BF_DQ, BF_M> args_by_value) {\n  (void)args_by_value;\n  bf::bpf_scan_body<BF_N, BF_DQ, BF_M, " +
-       std::to_string(ppt) + ", " + std::to_string(nw) + ", " + spec + ">(mdlp);\n}\n";
+       std::to_string(ppt) + ", " + std::to_string(nw) + ", " + spec + (kind == JIT_BPF_MISSING ? ", true" : "") + ">(mdlp);\n}\n";
   return s;
 }
 

@@ -1,6 +1,8 @@
 // Device-side state-space model for the sampling kernels (particle filter, data generator):
 // the registry functions' VALUES (no Jacobians), the Cholesky factors the Gaussian draws and the
 // emission log-density need, and the host code that fills them from the C-ABI structs.
+// A model prepared for the missing-observation kernels (prepare_bpf_model, missing = true) has the log-density's covariance
+// R_lp (M x M floats, row-major) directly BEHIND the BpfModel in the same buffer: bpf_model_lp_cov.
 #pragma once
 #ifndef BF_JIT
 #include <cstring>
@@ -12,6 +14,7 @@
 #include "kf_math.hpp"
 #include "models.hpp"
 #include "bf_canon_math.hpp"
+#include "bpf_missing.hpp"
 
 namespace bf {
 
@@ -37,6 +40,11 @@ struct BpfModel {
   float uth_dyn[64], uth_emi[64], uth_lp[64], r_eval[64];
 };
 enum { DYN_USER_SRC = 100, EMI_USER_SRC = 100 };   // BF_FN_USER
+// R_lp of a model prepared with missing = true: the M * M floats behind the struct
+template <int N, int DQ, int M>
+__device__ __forceinline__ const float* bpf_model_lp_cov(const BpfModel<N, DQ, M>* mdlp) {
+  return reinterpret_cast<const float*>(mdlp + 1);
+}
 
 // What the sampling code reads from a model's STRUCTURE fields (function ids, "this factor is diagonal" flags): at run time
 // from the struct (SpecRuntime: one binary serves every registry model), or as compile-time constants (SpecFixed: the
@@ -244,6 +252,24 @@ __device__ __forceinline__ void draw_dynamics_noise(const BpfModel<N, DQ, M>& md
   BF_UNROLL for (int d = 0; d < DQ; ++d) q[d] = mdl.q0[d] + q[d];
 }
 
+// mean of the emission density, h(x, r_eval, u): the caller's emission function, the selection shortcut, or the registry's --
+// the first lines of emission_loglik below, for emission_loglik_missing (emission_loglik keeps its own copy: sharing this one
+// moved branches in the compiled plain kernels, which are held byte-identical)
+template <int N, int DQ, int M, class SP = SpecRuntime>
+__device__ __forceinline__ void emission_density_mean(const BpfModel<N, DQ, M>& mdl, const float* xn, float u0, float* hx) {
+#pragma clang fp contract(off)
+#ifdef BF_USER_EMI
+  if constexpr (SP::user_emi) {
+    bfu::emission<float>(xn, mdl.r_eval, u0, mdl.uth_emi, hx);   // mean of the density: h(x, r_eval, u)
+  } else
+#endif
+  if (spec_h_pick<SP>(mdl)) {  // selection emission (e.g. the even states of Lorenz-96): the exact-zero terms of H x are skipped
+    BF_UNROLL for (int a = 0; a < M; ++a) hx[a] = xn[(2 * a) % N] + mdl.hb[a];
+  } else {
+    emi_value<N, DQ, M, SP>(mdl, xn, u0, hx);
+  }
+}
+
 // MVN(h(x, r_eval, u), R_lp).log_prob(y) (the `*lp` functions of the reference's scripts, e.g. nonlinearities.py:51-52)
 // through the Cholesky factor: forward substitution by fma, multiplication by the reciprocal diagonal, the quadratic
 // form by fma, -0.5 quad + const as ONE fma.  The oracle restates exactly this sequence (gaussfilt_oracle.py,
@@ -280,6 +306,30 @@ __device__ __forceinline__ float emission_loglik(const BpfModel<N, DQ, M>& mdl, 
     quad = __builtin_fmaf(zz[a], zz[a], quad);
   }
   return __builtin_fmaf(-0.5f, quad, mdl.lp_const) - lsc;
+}
+
+// The log-weight of the MISSING = true kernels: y[a] = NaN is a component that was not observed, `obs` the step's pattern
+// (bpf_observed_bits, the same in every lane of the workgroup: the three cases are uniform branches) and `sd` the step density
+// of a partly observed step (bpf_missing.hpp; in LDS).  Nothing observed: 0 for every particle, no density is evaluated.
+// Everything observed: emission_loglik itself, the plain route's bits.  A density from the caller's source is handed a partly
+// observed y as it is, NaN entries included: only a function that treats NaN itself takes partial gaps.
+template <int N, int DQ, int M, class SP = SpecRuntime>
+__device__ __forceinline__ float emission_loglik_missing(const BpfModel<N, DQ, M>& mdl, const float* sd, uint64_t obs, const float* xn, float u0,
+                                                         const float* yv) {
+#pragma clang fp contract(off)
+  if (obs == 0ull) return 0.f;
+  if constexpr (SP::user_lp) return emission_loglik<N, DQ, M, SP>(mdl, xn, u0, yv);
+  if (obs == bpf_all_observed<M>()) return emission_loglik<N, DQ, M, SP>(mdl, xn, u0, yv);
+  float hx[M];
+  emission_density_mean<N, DQ, M, SP>(mdl, xn, u0, hx);
+  if constexpr (N == M) {
+    if (spec_emi_id<SP>(mdl) == EMI_STOCH_VOL) {  // state-dependent covariance M R M^T: (M R M^T)_oo = M_o R_oo M_o, the scale of the observed rows
+      float sc[M];
+      BF_UNROLL for (int a = 0; a < M; ++a) sc[a] = sv_scale(mdl, xn[a], u0);
+      return emission_loglik_masked<M>(sd, obs, hx, yv, sc);
+    }
+  }
+  return emission_loglik_masked<M>(sd, obs, hx, yv, nullptr);
 }
 
 #ifndef BF_JIT   // host side: the C-ABI structs -> BpfModel

@@ -677,7 +677,8 @@ class ParticleCarry(NamedTuple):
 
 def bootstrap_particle_filter(params, emissions, num_particles: int, key=None, inputs=None,
                               ess_threshold: float = 0.5, *, resampler: str = "multinomial", output: str = "full",
-                              carry=None, return_carry: bool = False, return_ancestors: bool = False, device="cuda", options=None):
+                              carry=None, return_carry: bool = False, return_ancestors: bool = False, device="cuda", options=None,
+                              missing=None, observed=None):
     """Bootstrap particle filter, gaussfiltax/inference.py:1302-1380, on the HIP engine.
 
     Same positional signature as the reference (``key`` defaults to ``PRNGKey(0)``).  Returns the
@@ -687,10 +688,33 @@ def bootstrap_particle_filter(params, emissions, num_particles: int, key=None, i
     large run does not fit in HBM; ``output='both'`` returns everything.  ``resampler`` is
     'multinomial' (the reference's ``jr.choice``, utils.py:207-214) or 'systematic'.
     ``params.emission_distribution_log_prob`` must be a :class:`~.nonlinearities.GaussianLogProb`.
+
+    ``missing="nan"``: a NaN entry of ``emissions`` is a component that was not observed at that step (``bf_bpf_missing_f32``,
+    DESIGN.md 4c', on every kernel route).  Propagation and the keys a step consumes never change; with nothing missing the
+    results are the plain call's bit for bit.  A Gaussian density (``gaussian_log_prob`` / ``stoch_vol_log_prob``) weighs a partly
+    observed step by the density of its observed components, ``log N(y_o; h(x)_o, (R_lp)_oo)``.  A step with nothing observed
+    gives every particle log-weight 0 and runs the unchanged reweight: the weights are the previous ones renormalised, ``logz``
+    is within an ulp of 0 (not exactly 0), trailing gaps are a forecast, and ``sum_t logz`` is the log-evidence of the observed
+    entries.  A density of the caller's (``user_log_prob`` source, or a recorded Python function) is not called at a wholly missing
+    step; a PARTLY observed step is handed to it as it is, NaN entries included -- the package cannot marginalise a density it
+    does not know, so only a function that treats NaN itself (per component ``y[a] != y[a] ? 0 : ...``) takes partial gaps.
+    Without the keyword a NaN poisons its trajectory from that step on, as ever; +-Inf is never "missing".  ``observed``: a bool
+    mask of shape (T,), (B, T), (T, m) or (B, T, m), true where the entry was observed; it implies ``missing="nan"`` and the
+    filter runs on a device copy of the emissions with NaN where the mask is false (see :func:`kalman_filter`).
     """
     from .nonlinearities import GaussianLogProb, UserLogProb
+    gaps = _missing_route(missing, observed)
+    if not hasattr(params, "emission_distribution_log_prob"):
+        raise TypeError("params must be a ParamsBPF (with an emission_distribution_log_prob); got " + type(params).__name__)
     torch = _torch()
+    mask = None
+    if observed is not None:   # (m from the model dimensions; host work only: a mask that does not fit never reaches the device)
+        n0, _, dr0 = _param_dims(params)
+        h0 = require_device_function(params.emission_function, "emission", "params.emission_function", n0, dr0)
+        mask = _observed_mask(observed, np.shape(emissions), int(h0.out_dim))
     lib = _lib.require_gpu()
+    if mask is not None:
+        emissions = _masked_emissions(emissions, mask, device)
     NP = int(num_particles)
     if NP < 1:
         raise ValueError("num_particles must be >= 1")
@@ -778,8 +802,9 @@ def bootstrap_particle_filter(params, emissions, num_particles: int, key=None, i
 
     stream = torch.cuda.current_stream(dev).cuda_stream
     _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
-    _lib.check(lib.bf_bpf_f32(C.byref(bm), C.byref(yd), C.byref(ud), B, T, NP, key_c, float(ess_threshold),
-                              1 if resampler == "systematic" else 0, C.byref(cr), C.byref(od), C.c_void_p(stream)))
+    entry = lib.bf_bpf_missing_f32 if gaps else lib.bf_bpf_f32
+    _lib.check(entry(C.byref(bm), C.byref(yd), C.byref(ud), B, T, NP, key_c, float(ess_threshold),
+                     1 if resampler == "systematic" else 0, C.byref(cr), C.byref(od), C.c_void_p(stream)))
     if squeeze:
         res = {k: v[0] for k, v in res.items()}
     if return_carry:

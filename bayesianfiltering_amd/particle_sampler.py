@@ -193,10 +193,11 @@ def particle_posterior_sample(params, filtered, num_samples: int = 1, *, method:
 
 def bootstrap_particle_posterior_sample(params, emissions, num_particles, num_samples, key, inputs=None, **kw):
     """``bootstrap_particle_filter`` then :func:`particle_posterior_sample`, with ``kf, ks = random.split(key, 2)`` as the
-    filter's and the sampler's keys.  ``ess_threshold`` and ``resampler`` go to the filter, the other keywords to the sampler."""
+    filter's and the sampler's keys.  ``ess_threshold``, ``resampler`` and the missing-observation keywords ``missing`` /
+    ``observed`` go to the filter, the other keywords to the sampler (which reads no observations)."""
     from . import random as bfr
     kf, ks = bfr.split(np.asarray(key, dtype=np.uint32).reshape(2), 2)
-    fkw = {k: kw.pop(k) for k in ("ess_threshold", "resampler") if k in kw}
+    fkw = {k: kw.pop(k) for k in ("ess_threshold", "resampler", "missing", "observed") if k in kw}
     dev = kw.get("device", "cuda")
     filtered = bootstrap_particle_filter(params, emissions, num_particles, kf, inputs, return_ancestors=True, device=dev, **fkw)
     return particle_posterior_sample(params, filtered, num_samples, key=ks, inputs=inputs, **kw)

@@ -165,7 +165,7 @@ int bf_device_count(void);
  *                   and serves particle counts up to 4 096 with registry functions.
  * bf_set_option changes the PROCESS-WIDE default.  A library or a thread that must not disturb -- or be disturbed by -- other
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
- * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_missing_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_gsf_ekf_missing_f32, bf_ugsf_ukf_missing_f32, bf_agsf_*, bf_bpf_f32, bf_sample_ssm_f32,
+ * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_missing_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_gsf_ekf_missing_f32, bf_ugsf_ukf_missing_f32, bf_agsf_*, bf_bpf_f32, bf_bpf_missing_f32, bf_sample_ssm_f32,
  * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_rts_smoother_pscan_f32, bf_eks_smoother_f32,
  * bf_ffbs_sample_f32, bf_ffbs_sample_pscan_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_gs_smoother_f32, bf_gs_sample_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
@@ -431,6 +431,28 @@ typedef struct bf_bpf_out {
 int bf_bpf_f32(const bf_bpf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t N,
                const uint32_t key[2], float ess_threshold, int32_t resampler, const bf_bpf_carry* carry,
                const bf_bpf_out* out, void* stream);
+
+/* The bootstrap particle filter on observations with GAPS: bf_bpf_f32's arguments, dispatch (compiled instances, particles in
+ * HBM per trajectory or per chunk, kernels built at run time) and pre-launch refusals, on the MISSING = true kernels.  A NaN entry
+ * y[b, t, a] means "component a was not observed at step t"; o = the components of the step that are not NaN.
+ *   - Propagation never changes: every step consumes the keys it consumes in bf_bpf_f32.  With nothing missing the weights,
+ *     particles, ancestors, ESS, logz and carry are bf_bpf_f32's bit for bit.
+ *   - Gaussian densities (registry, source or recorded emission function), |o| > 0: the log-weight is
+ *     log N(y_o; h(x, r_eval, u)_o, (R_lp)_oo), factored per step; the stochastic-volatility scale enters for observed rows only.
+ *     What the model computes for a missing row is discarded.
+ *   - Nothing observed: every log-weight is 0 and the step runs the unchanged reweight -- the weights are the previous ones
+ *     renormalised, logz is log(sum w), within an ulp of 0 and not exactly 0; trailing gaps are a forecast, and sum_t logz is the
+ *     log-evidence of the observed entries.
+ *   - A density from the caller's source (bf_user_model_create_lp): a wholly missing step as above, the function is not called;
+ *     a PARTLY observed y is handed to it as it is, NaN entries included -- the library cannot marginalise a density it does not
+ *     know.  A function that treats NaN itself (per component `y[a] != y[a] ? 0 : ...`) takes gapped series, another one is
+ *     poisoned as under bf_bpf_f32.
+ *   - +-Inf is never "missing": a non-finite innovation of an observed component poisons that trajectory, and only it.
+ *   - Chunks through bf_bpf_carry cut anywhere, inside a gap included, equal the single call bit for bit.
+ * With this one, this header declares 49 entry points. */
+int bf_bpf_missing_f32(const bf_bpf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t N,
+                       const uint32_t key[2], float ess_threshold, int32_t resampler, const bf_bpf_carry* carry,
+                       const bf_bpf_out* out, void* stream);
 
 /* Synthetic data: NonlinearSSM.sample (gaussfiltax/models.py:240-289) for B trajectories, one key
  * per trajectory (d_keys [B][2], DEVICE).  model->ssm carries f, h, q0, Q, r0, R; model->m0 / P0 the
