@@ -172,6 +172,9 @@ SYMBOLS = {
     "bf_kalman_pscan_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
     "bf_kalman_filter_pscan_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
                                              C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p, C.c_int64, C.c_void_p]),
+    "bf_kalman_filter_pscan_missing_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
+                                                     C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p, C.c_int64,
+                                                     C.c_void_p]),
     "bf_smoother_abi_check": (C.c_int, [C.c_size_t, C.c_size_t]),
     "bf_rts_smoother_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_out_desc), C.c_int64, C.c_int64,
                                       C.POINTER(bf_smooth_carry), C.POINTER(bf_smooth_desc), C.c_void_p]),

@@ -113,7 +113,7 @@ Option& prs_block_option();  // rts_pscan.hip: 0 = from (B, T), else the block l
 Option& pfs_block_option();  // ffbs_pscan.hip: 0 = from (B, S, T), else the block length of the parallel-in-time posterior sampler
 long long kf_pscan_workspace_bytes(int n, int m, long long B, long long T, int block);
 int launch_kf_pscan(const bf_lgssm* model, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
-                    const bf_out_desc* out, void* workspace, long long workspace_bytes, hipStream_t stream);
+                    const bf_out_desc* out, void* workspace, long long workspace_bytes, hipStream_t stream, bool missing);
 
 // A shape / option the compiled instances do not cover falls through to the run-time-dimension kernel
 // (generic_scan.hip); if that cannot run it either, both reasons are reported.
@@ -279,7 +279,13 @@ int64_t bf_kalman_pscan_workspace_bytes(int32_t n, int32_t m, int64_t B, int64_t
 int bf_kalman_filter_pscan_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T, const bf_carry* carry,
                                const bf_out_desc* out, void* workspace, int64_t workspace_bytes, void* stream) {
   bf::CallOptionScope call_option_scope;
-  return bf::launch_kf_pscan(model, y, B, T, carry, out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+  return bf::launch_kf_pscan(model, y, B, T, carry, out, workspace, workspace_bytes, static_cast<hipStream_t>(stream), false);
+}
+
+int bf_kalman_filter_pscan_missing_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T, const bf_carry* carry,
+                                       const bf_out_desc* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  return bf::launch_kf_pscan(model, y, B, T, carry, out, workspace, workspace_bytes, static_cast<hipStream_t>(stream), true);
 }
 
 int bf_gsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t K,

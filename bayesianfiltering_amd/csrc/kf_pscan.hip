@@ -1,9 +1,11 @@
 // Host side of the parallel-in-time Kalman filter (kf_pscan.hpp): argument checks (all before the first HIP call), block
-// geometry, workspace size, and the dispatch over the compiled (n, m) table (instantiations: kf_pscan_group_{a,...,f}.hip).
+// geometry, workspace size, and the dispatch over the compiled (n, m) table (instantiations: kf_pscan_group_{a,...,f}.hip;
+// the missing-observation twins: kf_pscan_missing_group_{a,...,f}.hip).
 //
 // Register instances (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): every instance n = 1 ... 6, m = 1 ... 4 of the
 // three kernels builds without scratch; at n = 7 the scan kernel spills 860 bytes per lane (n = 8: fold 436, scan 1628), so
-// the limit is n = 6.  Table per instance: DESIGN.md, section 6h.
+// the limit is n = 6.  The MISSING = true twins of fold and emit build without scratch at every (n, m) too (the fold stages
+// the pattern table, at most 9 984 bytes, in LDS).  Tables per instance: DESIGN.md, section 6h.
 #include "forward_host.hpp"
 #include "pscan_host.hpp"
 
@@ -12,7 +14,9 @@ namespace bf {
 using KfPscanGroup = int(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
                          const bf_out_desc* out, float* workspace, int L, hipStream_t stream, bool* matched);
 KfPscanGroup launch_kf_pscan_group_a, launch_kf_pscan_group_b, launch_kf_pscan_group_c, launch_kf_pscan_group_d,
-    launch_kf_pscan_group_e, launch_kf_pscan_group_f;
+    launch_kf_pscan_group_e, launch_kf_pscan_group_f, launch_kf_pscan_missing_group_a, launch_kf_pscan_missing_group_b,
+    launch_kf_pscan_missing_group_c, launch_kf_pscan_missing_group_d, launch_kf_pscan_missing_group_e,
+    launch_kf_pscan_missing_group_f;
 
 static const char NAME[] = "parallel kalman filter";
 constexpr int PSCAN_M_MAX = 4;
@@ -47,8 +51,9 @@ long long kf_pscan_workspace_bytes(int n, int m, long long B, long long T, int b
   return NB < 0 ? NB : 4LL * B * NB * (4LL * n * n + 3LL * n);
 }
 
+// `missing`: bf_kalman_filter_pscan_missing_f32 -- the same checks in the same order and words, then the MISSING = true twins.
 int launch_kf_pscan(const bf_lgssm* model, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
-                    const bf_out_desc* out, void* workspace, long long workspace_bytes, hipStream_t stream) {
+                    const bf_out_desc* out, void* workspace, long long workspace_bytes, hipStream_t stream, bool missing) {
   if (!model || !y || !carry || !out || !workspace) return set_error(BF_EINVAL, "NULL argument");
   if (B <= 0 || T <= 0) return set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", B, T);
   int rc = check_lgssm(model);
@@ -66,10 +71,13 @@ int launch_kf_pscan(const bf_lgssm* model, const bf_cstream* y, long long B, lon
   if ((rc = pscan_check_workspace(NAME, "bf_kalman_pscan_workspace_bytes", workspace, workspace_bytes, need, B, T, 0, L)) != BF_OK)
     return rc;
 
-  KfPscanGroup* const groups[] = {launch_kf_pscan_group_a, launch_kf_pscan_group_b, launch_kf_pscan_group_c,
-                                  launch_kf_pscan_group_d, launch_kf_pscan_group_e, launch_kf_pscan_group_f};
+  KfPscanGroup* const plain[] = {launch_kf_pscan_group_a, launch_kf_pscan_group_b, launch_kf_pscan_group_c,
+                                 launch_kf_pscan_group_d, launch_kf_pscan_group_e, launch_kf_pscan_group_f};
+  KfPscanGroup* const gapped[] = {launch_kf_pscan_missing_group_a, launch_kf_pscan_missing_group_b,
+                                  launch_kf_pscan_missing_group_c, launch_kf_pscan_missing_group_d,
+                                  launch_kf_pscan_missing_group_e, launch_kf_pscan_missing_group_f};
   bool matched;
-  rc = pscan_run_groups(groups, &matched, model, y, B, T, carry, out, static_cast<float*>(workspace), L, stream);
+  rc = pscan_run_groups(missing ? gapped : plain, &matched, model, y, B, T, carry, out, static_cast<float*>(workspace), L, stream);
   if (matched) return rc;
   return set_error(BF_EUNSUPPORTED, "parallel kalman filter: (n=%d, m=%d) is not compiled in", model->n, model->m);
 }

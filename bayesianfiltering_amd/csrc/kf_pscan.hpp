@@ -48,11 +48,22 @@
 //
 // Registers: every per-lane array is indexed by compile-time constants only (fully unrolled loops).  A combination holds two
 // spans of 3 n^2 + 2 n floats plus the solve's right-hand sides: no scratch up to n = 6 (table in DESIGN.md, section 6h).
+//
+// Missing observations (MISSING = true, bf_kalman_filter_pscan_missing_f32): a NaN entry of y is a component that was not
+// observed at that step, with the contract of bf_kalman_filter_missing_f32.  The element of a step with observed rows o uses
+// S_o = H_o Qb H_o^T + Rb_oo, K_o = Qb H_o^T S_o^-1, W_o = A^T H_o^T S_o^-1 (o empty: (A, u, Qb, 0, 0)), so A_e, C_e, J_e, K, W
+// are constants per observation PATTERN: the host forms all 2^m (kf_pscan_patterns.hpp), the fold stages the table into LDS
+// and a lane takes its step's entry by the pattern's bit mask p = sum obs[a] << a, with v[a] = 0 for a missing a.  Entry 2^m - 1
+// is the complete step's element.  Block 0 and emit run condition_on_masked; the non-finite check runs over the observed
+// components only, and a wholly missing step leaves m and P as they are and has log-likelihood 0 -- on a poisoned trajectory
+// too, whose streams stay NaN.  ps_combine, the scan and the workspace are unchanged.
 #pragma once
 #include <cstring>
+#include <type_traits>
 #include "kf_scan_group.hpp"
 #include "pscan_common.hpp"
 #include "pscan_host.hpp"
+#include "kf_pscan_patterns.hpp"
 
 namespace bf {
 
@@ -84,9 +95,22 @@ struct PsSpan {
 // a block-start state: m | P
 constexpr int ps_state_floats(int n) { return n + n * n; }
 
-// o = i (+) j, i the earlier span.  o may alias i or j: everything is read before the first write.
+// One step's element with A, C and J left where they are (the missing route's table in LDS): a combination reads them at
+// their uses, which keeps 3 n^2 floats per lane out of the registers.
 template <int N>
-__device__ __forceinline__ void ps_combine(const PsSpan<N>& i, const PsSpan<N>& j, PsSpan<N>& o) {
+struct PsElementRef {
+  const float *a, *c, *jj;
+  float bv[N], ev[N];
+  __device__ const float* A() const { return a; }
+  __device__ const float* b() const { return bv; }
+  __device__ const float* C() const { return c; }
+  __device__ const float* eta() const { return ev; }
+  __device__ const float* J() const { return jj; }
+};
+
+// o = i (+) j, i the earlier span.  o may alias i or j: everything is read before the first write.
+template <int N, class SpanJ = PsSpan<N>>
+__device__ __forceinline__ void ps_combine(const PsSpan<N>& i, const SpanJ& j, PsSpan<N>& o) {
   constexpr int C1 = 2 * N + 1, C2 = N + 1;
   // (I + C_i J_j) X = [A_i | C_i | b_i + C_i eta_j]
   float M1[N * N], X[N * C1], t[N];
@@ -184,17 +208,27 @@ __device__ __forceinline__ void ps_load_y(const CView& y, long long b, long long
 // update: (m, P) prediction -> filtered; returns the log-likelihood.  An innovation that is not finite (a NaN / Inf
 // observation, or a mean that an earlier one made NaN) leaves no posterior: mean, covariance and log-likelihood are set to NaN
 // by selects, so that finite data keep the ordinary step's bits.
-template <int N, int M>
+// MISSING: a NaN entry of yv is a component that was not observed (condition_on_masked, kf_math.hpp); the check runs over the
+// observed components only, and a step with none leaves m and P as they are -- NaN on a poisoned trajectory -- and returns 0.
+template <int N, int M, bool MISSING = false>
 __device__ __forceinline__ float ps_update(const KFConst<N, M>& c, const float* yv, float* m, float* P) {
   float v[M];
   float z = 0.f;   // 0, or NaN when an entry of v is NaN / Inf
   BF_UNROLL for (int a = 0; a < M; ++a) {
     float s = c.H[a * N] * m[0];
     BF_UNROLL for (int i = 1; i < N; ++i) s = fmaf(c.H[a * N + i], m[i], s);
-    v[a] = yv[a] - (s + c.Dr0[a]);
-    z += v[a] - v[a];
+    if constexpr (MISSING) {
+      v[a] = s + c.Dr0[a];   // the predicted observation
+      const float d = yv[a] - v[a];
+      z += (yv[a] == yv[a]) ? d - d : 0.f;
+    } else {
+      v[a] = yv[a] - (s + c.Dr0[a]);
+      z += v[a] - v[a];
+    }
   }
-  const float ll = condition_on<N, M>(c.H, c.DRD, v, m, P);
+  float ll;
+  if constexpr (MISSING) ll = condition_on_masked<N, M>(c.H, c.DRD, yv, v, m, P);
+  else ll = condition_on<N, M>(c.H, c.DRD, v, m, P);
   const bool finite = (z == 0.f);
   BF_UNROLL for (int i = 0; i < N * N; ++i) P[i] = finite ? P[i] : __builtin_nanf("");
   BF_UNROLL for (int i = 0; i < N; ++i) m[i] = finite ? m[i] : __builtin_nanf("");   // (an Inf observation alone gives +-Inf here)
@@ -210,9 +244,12 @@ __device__ __forceinline__ void ps_predict(const Const& c, float* m, float* P) {
 }
 
 // ---- launch 1: fold -----------------------------------------------------------------------------------------------------
-template <int N, int M>
+// MISSING: `table` is the workgroup's LDS copy of PsPatternTable<N, M>; a middle-block step takes the element of its own
+// observation pattern from it, and block 0 runs the masked step.
+template <int N, int M, bool MISSING = false>
 __device__ __forceinline__ void ps_fold_body(const PsConst<N, M>& c, const CView& y, const CarryView& carry,
-                                             float* __restrict__ agg, long long B, long long NB, int L) {
+                                             float* __restrict__ agg, long long B, long long NB, int L,
+                                             [[maybe_unused]] const float* table = nullptr) {
   long long g, b, k;
   int j;
   if (!pscan_lane(B, 1, NB, g, b, j, k)) return;
@@ -225,30 +262,56 @@ __device__ __forceinline__ void ps_fold_body(const PsConst<N, M>& c, const CView
     BF_UNROLL for (int i = 0; i < N * N; ++i) P[i] = carry.P_in[b * N * N + i];
     for (int t = 0; t < L; ++t) {
       ps_load_y<N, M>(y, b, t, yv);
-      ps_update<N, M>(c.kf, yv, m, P);
+      ps_update<N, M, MISSING>(c.kf, yv, m, P);
       if (t + 1 < L) ps_predict<N>(c.kf, m, P);
     }
     BF_UNROLL for (int e = 0; e < N * N; ++e) { s.A()[e] = 0.f; s.C()[e] = P[e]; s.J()[e] = 0.f; }
     BF_UNROLL for (int e = 0; e < N; ++e) { s.b()[e] = m[e]; s.eta()[e] = 0.f; }
   } else {
-    PsSpan<N> e;
-    BF_UNROLL for (int i = 0; i < N * N; ++i) { e.A()[i] = c.Ae[i]; e.C()[i] = c.Ce[i]; e.J()[i] = c.Je[i]; }
+    std::conditional_t<MISSING, PsElementRef<N>, PsSpan<N>> e;
+    if constexpr (!MISSING) BF_UNROLL for (int i = 0; i < N * N; ++i) { e.A()[i] = c.Ae[i]; e.C()[i] = c.Ce[i]; e.J()[i] = c.Je[i]; }
     const long long t0 = k * (long long)L;
     for (int q = 0; q < L; ++q) {
       float yv[M], v[M];
       ps_load_y<N, M>(y, b, t0 + q, yv);
       BF_UNROLL for (int a = 0; a < M; ++a) v[a] = yv[a] - c.hud[a];
-      BF_UNROLL for (int i = 0; i < N; ++i) {
-        float sb = c.K[i * M] * v[0], se = c.W[i * M] * v[0];
-        BF_UNROLL for (int a = 1; a < M; ++a) {
-          sb = fmaf(c.K[i * M + a], v[a], sb);
-          se = fmaf(c.W[i * M + a], v[a], se);
+      const float *Kp = c.K, *Wp = c.W;
+      float *eb, *ee;
+      if constexpr (MISSING) {
+        unsigned p = 0;
+        BF_UNROLL for (int a = 0; a < M; ++a) {
+          const bool obs = (yv[a] == yv[a]);
+          v[a] = obs ? v[a] : 0.f;   // a select: the NaN never enters an fma
+          p |= (obs ? 1u : 0u) << a;
         }
-        e.b()[i] = c.kf.Gq0[i] + sb;
-        e.eta()[i] = se;
+        const float* el = table + p * PsPattern<N, M>::F;   // A_e | C_e | J_e | K | W of this lane's pattern
+        e.a = el;
+        e.c = el + N * N;
+        e.jj = el + 2 * N * N;
+        Kp = el + 3 * N * N;
+        Wp = Kp + N * M;
+        eb = e.bv;
+        ee = e.ev;
+      } else {
+        eb = e.b();
+        ee = e.eta();
+      }
+      BF_UNROLL for (int i = 0; i < N; ++i) {
+        float sb = Kp[i * M] * v[0], se = Wp[i * M] * v[0];
+        BF_UNROLL for (int a = 1; a < M; ++a) {
+          sb = fmaf(Kp[i * M + a], v[a], sb);
+          se = fmaf(Wp[i * M + a], v[a], se);
+        }
+        eb[i] = c.kf.Gq0[i] + sb;
+        ee[i] = se;
       }
       if (q == 0) {
-        BF_UNROLL for (int i = 0; i < PsSpan<N>::F; ++i) s.v[i] = e.v[i];
+        if constexpr (MISSING) {
+          BF_UNROLL for (int i = 0; i < N * N; ++i) { s.A()[i] = e.A()[i]; s.C()[i] = e.C()[i]; s.J()[i] = e.J()[i]; }
+          BF_UNROLL for (int i = 0; i < N; ++i) { s.b()[i] = e.b()[i]; s.eta()[i] = e.eta()[i]; }
+        } else {
+          BF_UNROLL for (int i = 0; i < PsSpan<N>::F; ++i) s.v[i] = e.v[i];
+        }
       } else {
         ps_combine<N>(s, e, s);
       }
@@ -284,7 +347,7 @@ struct PsScan {
 };
 
 // ---- launch 3: emit -----------------------------------------------------------------------------------------------------
-template <int N, int M>
+template <int N, int M, bool MISSING = false>
 __device__ __forceinline__ void ps_emit_body(const KFConst<N, M>& c, const CView& y, const CarryView& carry, const OutViews& out,
                                              const float* __restrict__ start, long long B, long long T, long long NB, int L) {
   long long g, b, k;
@@ -298,13 +361,23 @@ __device__ __forceinline__ void ps_emit_body(const KFConst<N, M>& c, const CView
   } else {
     pscan_col_load<ps_state_floats(N)>(start, B * NB, g, x);
     w = reweight_single(0.f, w);   // the weight after any earlier step: 1, or NaN for a carry weight that is not a positive number
+    if constexpr (MISSING) {
+      // A wholly missing step checks nothing and reports log-likelihood 0, on a poisoned trajectory too, so the block's
+      // first step need not learn of the poison as it does on the plain route.  The scan's covariances read no observation
+      // and are finite beside a NaN mean: a start mean that is not finite starts the block with NaN covariance and weight.
+      float z = 0.f;
+      BF_UNROLL for (int i = 0; i < N; ++i) z += m[i] - m[i];
+      const bool finite = (z == 0.f);
+      BF_UNROLL for (int i = 0; i < N * N; ++i) P[i] = finite ? P[i] : __builtin_nanf("");
+      w = finite ? w : __builtin_nanf("");
+    }
   }
   const long long t0 = k * (long long)L;
   const long long t1 = (t0 + L < T) ? t0 + L : T;
   for (long long t = t0; t < t1; ++t) {
     float yv[M];
     ps_load_y<N, M>(y, b, t, yv);
-    const float ll = ps_update<N, M>(c, yv, m, P);
+    const float ll = ps_update<N, M, MISSING>(c, yv, m, P);
     w = reweight_single(ll, w);
     if (out.w.p) out.w.p[b * out.w.sB + t * out.w.sT] = w;
     if (out.ll.p) out.ll.p[b * out.ll.sB + t * out.ll.sT] = ll;
@@ -321,10 +394,27 @@ __device__ __forceinline__ void ps_emit_body(const KFConst<N, M>& c, const CView
   }
 }
 
+// The fold's constants: PsConst, and on the missing route the device copy of the pattern table behind it.
 template <int N, int M>
-__global__ void __launch_bounds__(64) kf_pscan_fold_kernel(PsConst<N, M> c, CView y, CarryView carry, float* agg, long long B,
-                                                           long long NB, int L) {
-  ps_fold_body<N, M>(c, y, carry, agg, B, NB, L);
+struct PsConstMissing : PsConst<N, M> {
+  const float* table;   // PsPatternTable<N, M> (device_constants)
+};
+template <int N, int M, bool MISSING>
+using PsFoldConst = std::conditional_t<MISSING, PsConstMissing<N, M>, PsConst<N, M>>;
+
+template <int N, int M, bool MISSING = false>
+__global__ void __launch_bounds__(64) kf_pscan_fold_kernel(PsFoldConst<N, M, MISSING> c, CView y, CarryView carry, float* agg,
+                                                           long long B, long long NB, int L) {
+  if constexpr (MISSING) {
+    // the table once per workgroup, before any lane leaves: lanes of a wave index it by their own pattern
+    constexpr int F = (int)(sizeof(PsPatternTable<N, M>) / sizeof(float));
+    __shared__ float table[F];
+    for (int i = threadIdx.x; i < F; i += 64) table[i] = c.table[i];
+    __syncthreads();
+    ps_fold_body<N, M, true>(c, y, carry, agg, B, NB, L, table);
+  } else {
+    ps_fold_body<N, M>(c, y, carry, agg, B, NB, L);
+  }
 }
 template <int N>   // one workgroup per trajectory
 __global__ void __launch_bounds__(256) kf_pscan_scan_kernel(PsPredict<N> c, const float* agg, float* start, long long B,
@@ -332,10 +422,10 @@ __global__ void __launch_bounds__(256) kf_pscan_scan_kernel(PsPredict<N> c, cons
   __shared__ float lds[pscan_lds_floats<PsScan<N>>()];
   pscan_scan<PsScan<N>>({c, agg, start, blockIdx.x * NB, B * NB}, NB, lds);
 }
-template <int N, int M>
+template <int N, int M, bool MISSING = false>
 __global__ void __launch_bounds__(64) kf_pscan_emit_kernel(KFConst<N, M> c, CView y, CarryView carry, OutViews out,
                                                            const float* start, long long B, long long T, long long NB, int L) {
-  ps_emit_body<N, M>(c, y, carry, out, start, B, T, NB, L);
+  ps_emit_body<N, M, MISSING>(c, y, carry, out, start, B, T, NB, L);
 }
 
 // ---- host: the call's constants and the three launches ------------------------------------------------------------------
@@ -343,91 +433,34 @@ __global__ void __launch_bounds__(64) kf_pscan_emit_kernel(KFConst<N, M> c, CVie
 template <int N, int M>
 static inline bool ps_fill_const(const bf_lgssm* p, PsConst<N, M>& c) {
   fill_const<N, M>(p, c.kf, p->Q, p->R);
-  double A[N * N], H[M * N], Qb[N * N], u[N], S[M * M], Si[M * M], HQ[M * N], hud[M];
-  for (int i = 0; i < N * N; ++i) { A[i] = c.kf.A[i]; Qb[i] = c.kf.GQG[i]; }
-  for (int i = 0; i < M * N; ++i) H[i] = c.kf.H[i];
-  for (int i = 0; i < N; ++i) u[i] = c.kf.Gq0[i];
   for (int a = 0; a < M; ++a) {
     double s = c.kf.Dr0[a];
-    for (int i = 0; i < N; ++i) s += H[a * N + i] * u[i];
-    hud[a] = s;
-    for (int j = 0; j < N; ++j) {
-      double q = 0;
-      for (int i = 0; i < N; ++i) q += H[a * N + i] * Qb[i * N + j];
-      HQ[a * N + j] = q;
-    }
+    for (int i = 0; i < N; ++i) s += (double)c.kf.H[a * N + i] * (double)c.kf.Gq0[i];
+    c.hud[a] = (float)s;
   }
-  for (int a = 0; a < M; ++a)
-    for (int e = 0; e < M; ++e) {
-      double s = c.kf.DRD[a * M + e];
-      for (int j = 0; j < N; ++j) s += HQ[a * N + j] * H[e * N + j];
-      S[a * M + e] = s;
-      Si[a * M + e] = (a == e) ? 1.0 : 0.0;
-    }
-  for (int k = 0; k < M; ++k) {   // Gauss-Jordan with partial pivoting: Si <- S^-1
-    int piv = k;
-    for (int r = k + 1; r < M; ++r) if (std::fabs(S[r * M + k]) > std::fabs(S[piv * M + k])) piv = r;
-    const double d = S[piv * M + k];
-    if (!(std::fabs(d) > 1e-300) || !std::isfinite(d)) return false;
-    for (int e = 0; e < M; ++e) { std::swap(S[k * M + e], S[piv * M + e]); std::swap(Si[k * M + e], Si[piv * M + e]); }
-    for (int e = 0; e < M; ++e) { S[k * M + e] /= d; Si[k * M + e] /= d; }
-    for (int r = 0; r < M; ++r) if (r != k) {
-      const double f = S[r * M + k];
-      for (int e = 0; e < M; ++e) { S[r * M + e] -= f * S[k * M + e]; Si[r * M + e] -= f * Si[k * M + e]; }
-    }
-  }
-  double K[N * M], HA[M * N], W[N * M], IKH[N * N], Ae[N * N], Ce[N * N], Je[N * N];
-  for (int i = 0; i < N; ++i)
-    for (int a = 0; a < M; ++a) {
-      double s = 0;
-      for (int e = 0; e < M; ++e) s += HQ[e * N + i] * Si[e * M + a];   // Qb H^T S^-1 (Qb symmetric)
-      K[i * M + a] = s;
-    }
-  for (int a = 0; a < M; ++a)
-    for (int j = 0; j < N; ++j) {
-      double s = 0;
-      for (int i = 0; i < N; ++i) s += H[a * N + i] * A[i * N + j];
-      HA[a * N + j] = s;
-    }
-  for (int i = 0; i < N; ++i)
-    for (int a = 0; a < M; ++a) {
-      double s = 0;
-      for (int e = 0; e < M; ++e) s += HA[e * N + i] * Si[e * M + a];   // A^T H^T S^-1
-      W[i * M + a] = s;
-    }
-  for (int i = 0; i < N; ++i)
-    for (int j = 0; j < N; ++j) {
-      double s = (i == j) ? 1.0 : 0.0, q = 0;
-      for (int a = 0; a < M; ++a) { s -= K[i * M + a] * H[a * N + j]; q += W[i * M + a] * HA[a * N + j]; }
-      IKH[i * N + j] = s;
-      Je[i * N + j] = q;
-    }
-  for (int i = 0; i < N; ++i)
-    for (int j = 0; j < N; ++j) {
-      double s = 0, q = 0;
-      for (int k = 0; k < N; ++k) { s += IKH[i * N + k] * A[k * N + j]; q += IKH[i * N + k] * Qb[k * N + j]; }
-      Ae[i * N + j] = s;
-      Ce[i * N + j] = q;
-    }
-  for (int i = 0; i < N; ++i)
-    for (int j = 0; j < N; ++j) {
-      c.Ae[i * N + j] = (float)Ae[i * N + j];
-      c.Ce[i * N + j] = (float)(0.5 * (Ce[i * N + j] + Ce[j * N + i]));
-      c.Je[i * N + j] = (float)(0.5 * (Je[i * N + j] + Je[j * N + i]));
-    }
-  for (int i = 0; i < N * M; ++i) { c.K[i] = (float)K[i]; c.W[i] = (float)W[i]; }
-  for (int a = 0; a < M; ++a) c.hud[a] = (float)hud[a];
-  bool finite = true;
-  for (int i = 0; i < N * N; ++i) finite = finite && std::isfinite(c.Ae[i]) && std::isfinite(c.Ce[i]) && std::isfinite(c.Je[i]);
-  return finite;
+  PsPattern<N, M> e;   // every component observed: the element of a complete step
+  if (!ps_pattern_element<N, M>(c.kf.A, c.kf.H, c.kf.GQG, c.kf.DRD, (1u << M) - 1u, e)) return false;
+  std::memcpy(c.Ae, e.Ae, sizeof(c.Ae));
+  std::memcpy(c.Ce, e.Ce, sizeof(c.Ce));
+  std::memcpy(c.Je, e.Je, sizeof(c.Je));
+  std::memcpy(c.K, e.K, sizeof(c.K));
+  std::memcpy(c.W, e.W, sizeof(c.W));
+  return true;
 }
 
-template <int N, int M>
+// MISSING (bf_kalman_filter_pscan_missing_f32): the fold's middle blocks need one element per observation pattern; the host
+// forms all 2^M (kf_pscan_patterns.hpp), refuses a singular S_o like a singular S, and hands the table over as a cached
+// device constant block in front of the fold launch.  A single-block call (NB = 1) is the emit launch alone and uploads none.
+template <int N, int M, bool MISSING = false>
 static inline int launch_pscan_nm(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
                                   const bf_out_desc* out, float* workspace, int L, hipStream_t stream) {
-  PsConst<N, M> c;
-  if (!ps_fill_const<N, M>(p, c))
-    return set_error(BF_EUNSUPPORTED, "parallel kalman filter: S = H G Q G^T H^T + D R D^T is singular, the step element does not exist");
+  static const char singular[] =
+      "parallel kalman filter: S = H G Q G^T H^T + D R D^T is singular, the step element does not exist";
+  PsFoldConst<N, M, MISSING> c;
+  if (!ps_fill_const<N, M>(p, c)) return set_error(BF_EUNSUPPORTED, singular);
+  [[maybe_unused]] PsPatternTable<N, M> table;
+  if constexpr (MISSING)
+    if (!ps_pattern_table<N, M>(c.kf.A, c.kf.H, c.kf.GQG, c.kf.DRD, table)) return set_error(BF_EUNSUPPORTED, singular);
   auto [yv, cv, ov] = forward_views(y, carry, out);
   const PscanGeom g = pscan_geom(B, 1, T, L);
   float* agg = workspace;
@@ -437,11 +470,16 @@ static inline int launch_pscan_nm(const bf_lgssm* p, const bf_cstream* y, long l
     std::memcpy(pc.A, c.kf.A, sizeof(pc.A));
     std::memcpy(pc.GQG, c.kf.GQG, sizeof(pc.GQG));
     std::memcpy(pc.Gq0, c.kf.Gq0, sizeof(pc.Gq0));
-    hipLaunchKernelGGL((kf_pscan_fold_kernel<N, M>), dim3(g.grid), dim3(64), 0, stream, c, yv, cv, agg, B, g.NB, L);
+    if constexpr (MISSING) {
+      const void* d_table = nullptr;
+      if (const int rc = device_constants(&table, sizeof(table), stream, &d_table)) return rc;
+      c.table = static_cast<const float*>(d_table);
+    }
+    hipLaunchKernelGGL((kf_pscan_fold_kernel<N, M, MISSING>), dim3(g.grid), dim3(64), 0, stream, c, yv, cv, agg, B, g.NB, L);
     hipLaunchKernelGGL((kf_pscan_scan_kernel<N>), dim3((unsigned)B), dim3(g.scan_threads), 0, stream, pc, (const float*)agg, start,
                        B, g.NB);
   }
-  hipLaunchKernelGGL((kf_pscan_emit_kernel<N, M>), dim3(g.grid), dim3(64), 0, stream, c.kf, yv, cv, ov, (const float*)start, B, T,
+  hipLaunchKernelGGL((kf_pscan_emit_kernel<N, M, MISSING>), dim3(g.grid), dim3(64), 0, stream, c.kf, yv, cv, ov, (const float*)start, B, T,
                      g.NB, L);
   BF_HIP_CHECK(hipGetLastError());
   return BF_OK;

@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._backward import _front, _wrapper_kw, _LinearDynamics
-from .inference import FULL5, _kalman_call, _param_dims, _torch
+from .inference import FULL5, _Lgssm, _kalman_call, _masked_emissions, _missing_route, _observed_mask, _param_dims, _torch
 from .nonlinearities import DeviceFunction
 from .sampler import _sampler_front, _sampler_args
 from .smoother import _out_buffer, _smoothed_buffers, _smoothed_result
@@ -85,7 +85,7 @@ def _shared_workspace(params, emissions, kw, skw, other_bytes):
 def parallel_kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
                            fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
                            return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None,
-                           block=None, workspace=None):
+                           block=None, workspace=None, missing=None, observed=None):
     """``kalman_filter`` with time parallelism: same model, keywords, container, carry and log-likelihood.
 
     block: steps per block, 4 ... 4096; ``None`` = a default from (B, T): the largest of ceil(B T / 65 536) (one
@@ -94,13 +94,24 @@ def parallel_kalman_filter(params, emissions, *, initial_means=None, initial_cov
     workspace: a reusable ``torch.uint8`` device tensor of at least :func:`parallel_kalman_workspace_bytes` bytes; allocated
     when absent.  Its contents mean nothing before or after the call.
     Linear registry functions, constant Q and R, state dimension <= 6, emission dimension <= 4.
+
+    ``missing="nan"`` / ``observed=``: the two keywords of :func:`kalman_filter`, with its contract (a NaN entry is a component
+    that was not observed at that step; a step with none is predict-only with log-likelihood 0; trailing gaps are a forecast;
+    +-Inf still poisons, and without the keyword so does NaN), through ``bf_kalman_filter_pscan_missing_f32``: the fold takes
+    each step's element from a table with one entry per observation pattern, block 0 and the emit launch run the masked step.
+    A mask is written as NaN into a device copy of the emissions; the caller's tensor is never written.
     """
+    gaps = _missing_route(missing, observed)
+    mask = None if observed is None else _observed_mask(observed, np.shape(emissions), _Lgssm(params).m)
     lib = _lib.require_gpu()
+    if mask is not None:
+        emissions = _masked_emissions(emissions, mask, device)
+    entry = lib.bf_kalman_filter_pscan_missing_f32 if gaps else lib.bf_kalman_filter_pscan_f32
     k = _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
                      return_carry, device)
     _run(lib, "kalman", (k.mdl.n, k.mdl.m, k.B, k.T), block, workspace, k.y.device, options, "pkf_block",
-         lambda ws, size: lib.bf_kalman_filter_pscan_f32(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od),
-                                                         ws, size, C.c_void_p(k.stream)))
+         lambda ws, size: entry(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od), ws, size,
+                                C.c_void_p(k.stream)))
     return k.result()
 
 
@@ -146,10 +157,12 @@ def parallel_kalman_smoother(params, emissions, **kw):
     """:func:`parallel_kalman_filter` emitting the filtered fields only, then :func:`parallel_rts_smoother` on the recompute
     path.  Keywords of the filter (``initial_means``, ``initial_covariances``, ``layout``, ``device``) go to the filter, the
     others to the smoother; ``block`` goes to both passes.  One workspace of the larger -- the filter's -- size is allocated
-    once and handed to both (or ``workspace=`` is)."""
+    once and handed to both (or ``workspace=`` is).  ``missing`` / ``observed`` are the filter's: the backward pass reads no
+    observations, so it runs on the gapped posterior as it is."""
+    gaps = {k: kw.pop(k) for k in ("missing", "observed") if k in kw}
     fkw, skw = _wrapper_kw(params, kw, False)
     fkw.update(_shared_workspace(params, emissions, kw, skw, parallel_rts_workspace_bytes))
-    return parallel_rts_smoother(params, parallel_kalman_filter(params, emissions, **fkw), **skw)
+    return parallel_rts_smoother(params, parallel_kalman_filter(params, emissions, **fkw, **gaps), **skw)
 
 
 def parallel_ffbs_workspace_bytes(n: int, B: int, T: int, S: int, block=None) -> int:
@@ -201,8 +214,11 @@ def parallel_kalman_posterior_sample(params, emissions, num_samples, key, **kw):
     """:func:`parallel_kalman_filter` emitting the filtered fields only, then :func:`parallel_posterior_sample` on the
     recompute path.  Keywords of the filter (``initial_means``, ``initial_covariances``, ``layout``, ``device``) go to the
     filter, the others to the sampler (``noise=`` among them: then ``key`` is None); ``block`` goes to both passes.  One
-    workspace of the larger size is allocated once and handed to both (or ``workspace=`` is)."""
+    workspace of the larger size is allocated once and handed to both (or ``workspace=`` is).  ``missing`` / ``observed`` are the
+    filter's: the backward pass reads no observations."""
+    gaps = {k: kw.pop(k) for k in ("missing", "observed") if k in kw}
     fkw, skw = _wrapper_kw(params, kw, False)
     fkw.update(_shared_workspace(params, emissions, kw, skw,
                                  lambda n, B, T, block: parallel_ffbs_workspace_bytes(n, B, T, int(num_samples), block)))
-    return parallel_posterior_sample(params, parallel_kalman_filter(params, emissions, **fkw), num_samples, key=key, **skw)
+    return parallel_posterior_sample(params, parallel_kalman_filter(params, emissions, **fkw, **gaps), num_samples, key=key,
+                                     **skw)

@@ -165,7 +165,7 @@ int bf_device_count(void);
  *                   and serves particle counts up to 4 096 with registry functions.
  * bf_set_option changes the PROCESS-WIDE default.  A library or a thread that must not disturb -- or be disturbed by -- other
  * callers uses bf_set_call_option instead: it arms the same option on the CALLING THREAD for the NEXT filter entry point
- * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_missing_f32, bf_kalman_filter_pscan_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_gsf_ekf_missing_f32, bf_ugsf_ukf_missing_f32, bf_agsf_*, bf_bpf_f32, bf_bpf_missing_f32, bf_sample_ssm_f32,
+ * called on that thread (bf_kalman_filter_f32, bf_kalman_filter_missing_f32, bf_kalman_filter_pscan_f32, bf_kalman_filter_pscan_missing_f32, bf_gsf_ekf_f32, bf_ugsf_ukf_f32, bf_gsf_ekf_missing_f32, bf_ugsf_ukf_missing_f32, bf_agsf_*, bf_bpf_f32, bf_bpf_missing_f32, bf_sample_ssm_f32,
  * bf_resample_f32, bf_optimal_resample_f32, bf_collapse_f32, bf_rts_smoother_f32, bf_rts_smoother_pscan_f32, bf_eks_smoother_f32,
  * bf_ffbs_sample_f32, bf_ffbs_sample_pscan_f32, bf_effbs_sample_f32, bf_uks_smoother_f32, bf_gs_smoother_f32, bf_gs_sample_f32, bf_uffbs_sample_f32, bf_pf_backward_sample_f32, bf_pf_trace_sample_f32) and for that call only; every armed override is dropped when
  * that call returns, whatever its status. */
@@ -223,6 +223,25 @@ int64_t bf_kalman_pscan_workspace_bytes(int32_t n, int32_t m, int64_t B, int64_t
 int bf_kalman_filter_pscan_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T,
                                const bf_carry* carry, const bf_out_desc* out,
                                void* workspace, int64_t workspace_bytes, void* stream);
+
+/* bf_kalman_filter_pscan_f32 for series with gaps: the same arguments, workspace (bf_kalman_pscan_workspace_bytes) and three
+ * launches, with the contract of bf_kalman_filter_missing_f32 -- a NaN entry of y is a component that was not observed at
+ * that step; the update conditions on the observed rows only; a step with none leaves mean and covariance as they are and has
+ * log-likelihood 0 (on an already poisoned trajectory too: its weight stays NaN); the predict step always runs, so trailing
+ * gaps are a forecast; +-Inf in an observed entry still poisons from that step on.  Opt-in: bf_kalman_filter_pscan_f32 keeps
+ * treating NaN as poison.
+ * A step's filtering element depends on its observation pattern, so the host forms the constant parts (A_e, C_e, J_e and the
+ * maps K, W; float64, as for the complete step) once per call for each of the 2^m patterns -- 3 n^2 + 2 n m floats each, at
+ * most 9 984 bytes at (6, 4) --, keeps the table as a cached device constant block and the fold stages it into LDS; a lane
+ * selects its step's entry by the pattern's bit mask.  The entry of the complete pattern equals the constants of
+ * bf_kalman_filter_pscan_f32 bit for bit, and block 0 and the emit launch run the masked step of
+ * bf_kalman_filter_missing_f32; inside a block the outputs are that filter's from the block's start state, the start states
+ * are jitter-free, and the whole agrees with it to fp32 tolerance.  Scan, workspace layout and "pkf_block" are unchanged.
+ * Refusals: those of bf_kalman_filter_pscan_f32, in the same order and words, before the first HIP call; every S_o is a
+ * principal submatrix of S and is checked like S.  With this one, this header declares 50 entry points. */
+int bf_kalman_filter_pscan_missing_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T,
+                                       const bf_carry* carry, const bf_out_desc* out,
+                                       void* workspace, int64_t workspace_bytes, void* stream);
 
 /* A state-space model built from the function registry (the device-side replacement of the
  * Python callables f(x,q,u), h(x,r,u) of gaussfiltax/models.py:46-49; ids and theta layouts:
