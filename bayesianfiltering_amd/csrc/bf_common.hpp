@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdint>
 #include <atomic>
+#include <iterator>
 #include "../../include/bayesfilt.h"
 #include "bf_views.hpp"  // SView, CView, OutViews, CarryView, UView, UViewG
 
@@ -67,6 +68,30 @@ struct CallOptionScope {   // at the top of every filter entry point: overrides 
 // Device-resident copy of a host constant block (model struct, per-step covariance table), cached by content and
 // uploaded stream-ordered through pinned staging: no host synchronisation, nothing to free (const_cache.hip).
 int device_constants(const void* host, size_t bytes, hipStream_t stream, const void** d_out);
+
+// The instance tables (kf_group_*.hip, gsf_group_*.hip, ugsf_group_*.hip, bpf_group_*.hip, kf_pscan_group_*.hip) are slices
+// that the Makefile builds twice: as they stand, and with -DBF_MISSING=true for the missing-observation (MISSING = true)
+// instances of the same rows.  A slice passes BF_MISSING to its launch template and names its function BF_GROUP_FN(family, g):
+// launch_<family>_group_<g>, or launch_<family>_missing_group_<g> in the second build.
+#ifndef BF_MISSING
+#define BF_MISSING false
+#endif
+#if BF_MISSING
+#define BF_GROUP_FN(FAMILY_, G_) launch_##FAMILY_##_missing_group_##G_
+#else
+#define BF_GROUP_FN(FAMILY_, G_) launch_##FAMILY_##_group_##G_
+#endif
+
+// The walk over a family's slices: the first that has the call's instance runs it and sets *matched.
+template <class Group, class... Args>
+inline int run_groups(Group* const* groups, size_t count, bool* matched, const Args&... args) {
+  *matched = false;
+  for (size_t g = 0; g < count; ++g) {
+    const int rc = groups[g](args..., matched);
+    if (*matched) return rc;
+  }
+  return BF_OK;
+}
 
 inline SView make_sview(const bf_stream& s) { return SView{s.ptr, s.sB, s.sK, s.sT, s.sE}; }
 

@@ -1,16 +1,17 @@
 // Instantiations of the bootstrap particle filter kernel (bpf_scan.hpp) for a slice of the
 // (n, dq, m) table; split over several translation units to build in parallel.
+// Built twice (bf_common.hpp): as it stands, and with -DBF_MISSING=true for the missing-observation instances of the same rows.
 #include "bpf_wide.hpp"
 
 namespace bf {
 
-int launch_bpf_group_b(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP,
+int BF_GROUP_FN(bpf, b)(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP,
         float ess, int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out, hipStream_t stream, bool* matched) {
   const bf_model* p = &bp->ssm;
-#define BF_CASE(N_, DQ_, M_)                                                                        \
-  if (p->n == N_ && p->dq == DQ_ && p->m == M_) {                                                     \
-    *matched = true;                                                                                  \
-    return launch_bpf_dims<N_, DQ_, M_>(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream); \
+#define BF_CASE(N_, DQ_, M_)                                                                                   \
+  if (p->n == N_ && p->dq == DQ_ && p->m == M_) {                                                              \
+    *matched = true;                                                                                           \
+    return launch_bpf_dims<N_, DQ_, M_, BF_MISSING>(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream); \
   }
   BF_CASE(1, 1, 1);
   BF_CASE(3, 3, 3);

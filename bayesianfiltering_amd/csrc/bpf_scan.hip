@@ -1,5 +1,6 @@
 // Dispatch of the bootstrap particle filter over the compiled (n, dq, m) table (instantiations in
-// bpf_group_{a,b,c}.hip), the launch of the same kernels built at run time, and the stand-alone resampler.
+// bpf_group_{a,b,c}.hip, each built plain and with MISSING = true), the launch of the same kernels built at run time, and the
+// stand-alone resampler.
 #include "bpf_big.hpp"   // (brings bpf_scan.hpp)
 #include "user_model.hpp"
 
@@ -41,16 +42,13 @@ int launch_resample(const float* d_w, const uint32_t* d_keys, long long B, int N
   return BF_OK;
 }
 
-#define BF_DECL(F_)                                                                                                   \
-  int F_(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP, float ess, \
-         int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out, hipStream_t stream, bool* matched)
-BF_DECL(launch_bpf_group_a);
-BF_DECL(launch_bpf_group_b);
-BF_DECL(launch_bpf_group_c);
-BF_DECL(launch_bpf_missing_group_a);   // the MISSING = true instances of the same rows (bpf_missing_group_{a,b,c}.hip)
-BF_DECL(launch_bpf_missing_group_b);
-BF_DECL(launch_bpf_missing_group_c);
-#undef BF_DECL
+// the compiled (n, dq, m) table: bpf_group_{a,b,c}.hip, each built plain and with MISSING = true
+using BpfGroup = int(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int NP, float ess,
+                     int resampler, const uint32_t key[2], const BpfCarry& cr, const BpfOut& out, hipStream_t stream, bool* matched);
+BpfGroup launch_bpf_group_a, launch_bpf_group_b, launch_bpf_group_c, launch_bpf_missing_group_a, launch_bpf_missing_group_b,
+    launch_bpf_missing_group_c;
+static BpfGroup* const kPlainGroups[] = {launch_bpf_group_a, launch_bpf_group_b, launch_bpf_group_c};
+static BpfGroup* const kMissingGroups[] = {launch_bpf_missing_group_a, launch_bpf_missing_group_b, launch_bpf_missing_group_c};
 
 // The particle filter built at run time (user_model.hpp): around the functions of a handle from source (the caller's functions
 // see the CANONICAL arithmetic of the weight path, so a function written like its registry twin gives the registry twin's bits),
@@ -108,14 +106,10 @@ int launch_bpf(const bf_bpf_model* bp, const bf_cstream* y, const bf_cstream* u,
     return launch_bpf_jit(bp->ssm.user, bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, missing);
   if (bp->ssm.dyn_id == BF_FN_USER || bp->ssm.emi_id == BF_FN_USER)
     return set_error(BF_EINVAL, "dyn_id / emi_id = BF_FN_USER needs bf_model.user (bf_user_model_create)");
-  bool matched = false;
-  int rc = BF_OK;
   if (g_bpf_arith != 1) {   // (1: the same kernel with the hardware's transcendentals, compiled at run time)
-    rc = (missing ? launch_bpf_missing_group_a : launch_bpf_group_a)(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
-    if (matched) return rc;
-    rc = (missing ? launch_bpf_missing_group_b : launch_bpf_group_b)(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
-    if (matched) return rc;
-    rc = (missing ? launch_bpf_missing_group_c : launch_bpf_group_c)(bp, y, u, B, T, NP, ess, resampler, key, cr, out, stream, &matched);
+    bool matched;
+    const int rc = run_groups(missing ? kMissingGroups : kPlainGroups, std::size(kPlainGroups), &matched, bp, y, u, B, T, NP, ess,
+                              resampler, key, cr, out, stream);
     if (matched) return rc;
   }
   // hardware arithmetic, or no compiled instance for these dimensions: the same kernel, compiled now (needs hiprtc)

@@ -92,7 +92,7 @@ int launch_ffbs_pscan(const bf_lgssm* model, const bf_out_desc* filtered, long l
   FfbsPscanGroup* const groups[] = {launch_ffbs_pscan_group_a, launch_ffbs_pscan_group_b, launch_ffbs_pscan_group_c,
                                     launch_ffbs_pscan_group_d, launch_ffbs_pscan_group_e};
   bool matched;
-  rc = pscan_run_groups(groups, &matched, r, v, B, T, S, spl, static_cast<float*>(workspace), L, stream);
+  rc = run_groups(groups, std::size(groups), &matched, r, v, B, T, S, spl, static_cast<float*>(workspace), L, stream);
   if (matched) return rc;
   return set_error(BF_EUNSUPPORTED, "parallel sampler: n=%d is not compiled in", model->n);
 }

@@ -82,7 +82,7 @@ constexpr int wrap_mod(int i) {
 // MISSING = true: a NaN y[b, t, a] is a component that was not observed at that step.  Every component of the bank conditions
 // on the observed rows only, through the embedding of kf_math.hpp (psd_solve_masked / mvn_logpdf_chol_masked); what the model
 // computes for a missing row is discarded by selects, so a NaN or Inf it produces there never reaches the state.  Its own
-// instances (gsf_missing_group_*.hip); nothing else in the step changes.
+// instances (the -DBF_MISSING=true build of gsf_group_*.hip); nothing else in the step changes.
 template <int NS, int M, int NL, int MODE, int SPEC, bool EXT = false, bool MISSING = false>
 #ifndef BF_GSF_NONE_WAVES
 #define BF_GSF_NONE_WAVES 2

@@ -1,6 +1,6 @@
 // Host side of the parallel-in-time Kalman filter (kf_pscan.hpp): argument checks (all before the first HIP call), block
-// geometry, workspace size, and the dispatch over the compiled (n, m) table (instantiations: kf_pscan_group_{a,...,f}.hip;
-// the missing-observation twins: kf_pscan_missing_group_{a,...,f}.hip).
+// geometry, workspace size, and the dispatch over the compiled (n, m) table (instantiations: kf_pscan_group_{a,...,f}.hip,
+// each built plain and with MISSING = true for the missing-observation twins).
 //
 // Register instances (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): every instance n = 1 ... 6, m = 1 ... 4 of the
 // three kernels builds without scratch; at n = 7 the scan kernel spills 860 bytes per lane (n = 8: fold 436, scan 1628), so
@@ -17,6 +17,11 @@ KfPscanGroup launch_kf_pscan_group_a, launch_kf_pscan_group_b, launch_kf_pscan_g
     launch_kf_pscan_group_e, launch_kf_pscan_group_f, launch_kf_pscan_missing_group_a, launch_kf_pscan_missing_group_b,
     launch_kf_pscan_missing_group_c, launch_kf_pscan_missing_group_d, launch_kf_pscan_missing_group_e,
     launch_kf_pscan_missing_group_f;
+static KfPscanGroup* const kPlainGroups[] = {launch_kf_pscan_group_a, launch_kf_pscan_group_b, launch_kf_pscan_group_c,
+                                             launch_kf_pscan_group_d, launch_kf_pscan_group_e, launch_kf_pscan_group_f};
+static KfPscanGroup* const kMissingGroups[] = {launch_kf_pscan_missing_group_a, launch_kf_pscan_missing_group_b,
+                                               launch_kf_pscan_missing_group_c, launch_kf_pscan_missing_group_d,
+                                               launch_kf_pscan_missing_group_e, launch_kf_pscan_missing_group_f};
 
 static const char NAME[] = "parallel kalman filter";
 constexpr int PSCAN_M_MAX = 4;
@@ -71,13 +76,9 @@ int launch_kf_pscan(const bf_lgssm* model, const bf_cstream* y, long long B, lon
   if ((rc = pscan_check_workspace(NAME, "bf_kalman_pscan_workspace_bytes", workspace, workspace_bytes, need, B, T, 0, L)) != BF_OK)
     return rc;
 
-  KfPscanGroup* const plain[] = {launch_kf_pscan_group_a, launch_kf_pscan_group_b, launch_kf_pscan_group_c,
-                                 launch_kf_pscan_group_d, launch_kf_pscan_group_e, launch_kf_pscan_group_f};
-  KfPscanGroup* const gapped[] = {launch_kf_pscan_missing_group_a, launch_kf_pscan_missing_group_b,
-                                  launch_kf_pscan_missing_group_c, launch_kf_pscan_missing_group_d,
-                                  launch_kf_pscan_missing_group_e, launch_kf_pscan_missing_group_f};
   bool matched;
-  rc = pscan_run_groups(missing ? gapped : plain, &matched, model, y, B, T, carry, out, static_cast<float*>(workspace), L, stream);
+  rc = run_groups(missing ? kMissingGroups : kPlainGroups, std::size(kPlainGroups), &matched, model, y, B, T, carry, out,
+                  static_cast<float*>(workspace), L, stream);
   if (matched) return rc;
   return set_error(BF_EUNSUPPORTED, "parallel kalman filter: (n=%d, m=%d) is not compiled in", model->n, model->m);
 }

@@ -1,6 +1,6 @@
 // Host side the three parallel-in-time passes share (kf_pscan.hip, rts_pscan.hip, ffbs_pscan.hip and the launch templates of
-// their headers): the limits, the block length, the block count, the workspace refusals, the launch geometry and the walk over
-// the group translation units.  `name` is the family's display name, the head of every message ("parallel kalman filter",
+// their headers): the limits, the block length, the block count, the workspace refusals and the launch geometry (the walk
+// over the group translation units is run_groups, bf_common.hpp).  `name` is the family's display name, the head of every message ("parallel kalman filter",
 // "parallel rts smoother", "parallel sampler"); S = 0 stands for a family without samples, and the texts then leave S out.
 #pragma once
 #include <cstddef>
@@ -82,18 +82,6 @@ inline PscanGeom pscan_geom(long long B, long long NSB, long long T, int L) {
   g.grid = (unsigned)((g.lanes + 63) / 64);
   g.scan_threads = g.NB - 1 <= 64 ? 64 : 256;
   return g;
-}
-
-// The group translation units each hold a slice of the instance table: the first that has the call's instance runs it and
-// sets *matched.
-template <class Group, size_t K, class... Args>
-inline int pscan_run_groups(Group* const (&groups)[K], bool* matched, const Args&... args) {
-  *matched = false;
-  for (Group* group : groups) {
-    const int rc = group(args..., matched);
-    if (*matched) return rc;
-  }
-  return BF_OK;
 }
 
 }  // namespace bf

@@ -65,7 +65,7 @@ int launch_rts_pscan(const bf_lgssm* model, const bf_out_desc* filtered, long lo
   RtsPscanGroup* const groups[] = {launch_rts_pscan_group_a, launch_rts_pscan_group_b, launch_rts_pscan_group_c,
                                    launch_rts_pscan_group_d};
   bool matched;
-  rc = pscan_run_groups(groups, &matched, r, v, B, T, static_cast<float*>(workspace), L, stream);
+  rc = run_groups(groups, std::size(groups), &matched, r, v, B, T, static_cast<float*>(workspace), L, stream);
   if (matched) return rc;
   return set_error(BF_EUNSUPPORTED, "parallel rts smoother: n=%d is not compiled in", model->n);
 }

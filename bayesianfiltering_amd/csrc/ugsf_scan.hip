@@ -1,5 +1,5 @@
-// Instances and dispatch of the unscented Gaussian-sum filter kernel (ugsf_scan.hpp) over the compiled
-// (n, dq, m, dr) table, and the launches of the same kernel built at run time (user_model.hpp).  Any dimension above 8 -- or
+// Dispatch of the unscented Gaussian-sum filter kernel (ugsf_scan.hpp) over the compiled (n, dq, m, dr) table (instantiations:
+// ugsf_group_{u,v}.hip), and the launches of the same kernel built at run time (user_model.hpp).  Any dimension above 8 -- or
 // bf_set_option "ugsf_force_generic" = 1 -- goes to the run-time-dimension kernel instead (ugsf_generic.hip).
 #include "ugsf_scan.hpp"
 #include "user_model.hpp"
@@ -7,6 +7,13 @@
 namespace bf {
 
 extern Option g_ugsf_force_generic;   // ugsf_generic.hip
+
+// the compiled (n, dq, m, dr) table: ugsf_group_{u,v}.hip, each built plain and with MISSING = true
+using UgsfGroup = int(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B, long long T,
+                      int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, bool* matched);
+UgsfGroup launch_ugsf_group_u, launch_ugsf_group_v, launch_ugsf_missing_group_u, launch_ugsf_missing_group_v;
+static UgsfGroup* const kPlainGroups[] = {launch_ugsf_group_u, launch_ugsf_group_v};
+static UgsfGroup* const kMissingGroups[] = {launch_ugsf_missing_group_u, launch_ugsf_missing_group_v};
 
 // ugsf_scan_body built around the handle's functions: `kind` JIT_UGSF (sigma points through f and h) or JIT_GSF_REGS
 // (extended-Kalman operations, Jacobians by dual numbers; user_flags bit 2: the covariances themselves, not their roots)
@@ -65,19 +72,9 @@ int launch_ugsf_ukf(const bf_model* p, const bf_ukf_params* up, const bf_cstream
     return set_error(BF_EINVAL, "dyn_id / emi_id = BF_FN_USER needs bf_model.user (bf_user_model_create)");
   if (p->n > 8 || p->dq > 8 || p->m > 8 || p->dr > 8 || g_ugsf_force_generic.load() != 0)   // beyond the registers: state in LDS, ahead-of-time instance
     return launch_ugsf_generic(p, up, y, u, B, T, K, carry, out, stream);
-#define BF_CASE(N_, DQ_, M_, DR_)                                                      \
-  if (p->n == N_ && p->dq == DQ_ && p->m == M_ && p->dr == DR_)                        \
-    return launch_ugsf<N_, DQ_, M_, DR_>(p, up, y, u, B, T, K, carry, out, stream);
-  BF_CASE(1, 1, 1, 1);   // growth / sine + quadratic (Experiment_TSP_2023.ipynb cell 2)
-  BF_CASE(2, 2, 1, 1);
-  BF_CASE(2, 2, 2, 2);   // stochastic volatility (adaptive_experiment.py:51-54)
-  BF_CASE(3, 3, 1, 1);   // Lorenz-63 + quadratic (exp_lorentz63.py)
-  BF_CASE(3, 3, 3, 3);
-  BF_CASE(4, 2, 1, 1);   // manoeuvring target + bearing only (docs/tests/test_inference.py)
-  BF_CASE(4, 2, 2, 2);   // manoeuvring target + bearing / range, constant-velocity models (BOT_Experiment_script.py)
-  BF_CASE(4, 4, 2, 2);
-  BF_CASE(8, 8, 4, 4);   // Lorenz-96 with the even-state emission (nonlinearities.py:37-50)
-#undef BF_CASE
+  bool matched;
+  const int rc = run_groups(kPlainGroups, std::size(kPlainGroups), &matched, p, up, y, u, B, T, K, carry, out, stream);
+  if (matched) return rc;
   // no compiled instance for these dimensions: the same kernel, compiled now (needs hiprtc; dimensions up to 8)
   bf_model jit = *p;
   jit.user = registry_jit_handle(p, false);
@@ -87,11 +84,6 @@ int launch_ugsf_ukf(const bf_model* p, const bf_ukf_params* up, const bf_cstream
 
 // ---- missing observations (NaN entries): the MISSING = true twins of the register kernels above.  Nothing else takes gaps, so
 // whatever the plain route would send to a run-time-dimension kernel is refused here (bf_api.hip checks before any HIP call).
-int launch_ugsf_missing_group_u(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
-        long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, bool* matched);
-int launch_ugsf_missing_group_v(const bf_model* p, const bf_ukf_params* up, const bf_cstream* y, const bf_cstream* u, long long B,
-        long long T, int K, const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, bool* matched);
-
 int launch_gsf_user_regs_missing_impl(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
                                       const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
   const int rc = check_user_model(p->user, p);
@@ -106,10 +98,8 @@ int launch_ugsf_ukf_missing(const bf_model* p, const bf_ukf_params* up, const bf
     if (rc != BF_OK) return rc;
     return launch_ugsf_jit(JIT_UGSF, p, up, y, u, B, T, K, carry, out, stream, true);
   }
-  bool matched = false;
-  int rc = launch_ugsf_missing_group_u(p, up, y, u, B, T, K, carry, out, stream, &matched);
-  if (matched) return rc;
-  rc = launch_ugsf_missing_group_v(p, up, y, u, B, T, K, carry, out, stream, &matched);
+  bool matched;
+  const int rc = run_groups(kMissingGroups, std::size(kMissingGroups), &matched, p, up, y, u, B, T, K, carry, out, stream);
   if (matched) return rc;
   // no compiled instance for these dimensions: the same kernel, compiled now (needs hiprtc; dimensions up to 8)
   bf_model jit = *p;

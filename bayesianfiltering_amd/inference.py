@@ -347,11 +347,18 @@ def _masked_emissions(emissions, mask, device):
     return torch.where(torch.as_tensor(mask, device=y.device), y, torch.full((), float("nan"), dtype=torch.float32, device=y.device))
 
 
-def _missing_route(missing, observed):
-    """Whether the call takes the missing-observation entry point: ``missing="nan"``, or any ``observed=`` mask."""
+def _missing_route(missing, observed, emissions, device, emission_dim):
+    """The front of every filter that takes ``missing=`` / ``observed=``.  Returns (gaps, lib, emissions): whether the call takes
+    the missing-observation entry point (``missing="nan"``, or any ``observed=`` mask), the GPU library, and the emissions --
+    with a mask, a device copy with NaN where it is false.  ``emission_dim()`` gives m, and is called only with a mask.  Host
+    work first: a keyword or a mask that does not fit is refused before the device is asked for."""
     if missing not in (None, "nan"):
         raise ValueError(f"missing must be None or 'nan'; got {missing!r}")
-    return missing == "nan" or observed is not None
+    mask = None if observed is None else _observed_mask(observed, np.shape(emissions), int(emission_dim()))
+    lib = _lib.require_gpu()
+    if mask is not None:
+        emissions = _masked_emissions(emissions, mask, device)
+    return missing == "nan" or observed is not None, lib, emissions
 
 
 def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
@@ -374,11 +381,7 @@ def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=
     "missing".  ``observed``: a bool mask of shape (T,), (B, T), (T, m) or (B, T, m), true where the entry was observed; it
     implies ``missing="nan"`` and the filter runs on a device copy of the emissions with NaN where the mask is false.
     """
-    gaps = _missing_route(missing, observed)
-    mask = None if observed is None else _observed_mask(observed, np.shape(emissions), _Lgssm(params).m)
-    lib = _lib.require_gpu()
-    if mask is not None:
-        emissions = _masked_emissions(emissions, mask, device)
+    gaps, lib, emissions = _missing_route(missing, observed, emissions, device, lambda: _Lgssm(params).m)
     k = _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
                      return_carry, device)
     _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
@@ -497,20 +500,17 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
     (B, T), (T, m) or (B, T, m), true where the entry was observed; it implies ``missing="nan"`` (see :func:`kalman_filter`).
     """
     torch = _torch()
-    gaps = _missing_route(missing, observed)
     K = int(num_components)
     if K < 1:
         raise ValueError("num_components must be >= 1")
-    mask = None
-    if observed is not None:   # (m from the model dimensions; host work only: a mask that does not fit never reaches the device)
+
+    def emission_dim():   # (m from the model dimensions)
         h = params.emission_function
         if not isinstance(h, DeviceFunction):   # a plain Python function: recorded on the host, as _Model does
             n0, _, dr0 = _param_dims(params)
             h = require_device_function(h, "emission", "params.emission_function", n0, dr0)
-        mask = _observed_mask(observed, np.shape(emissions), int(h.out_dim))
-    lib = _lib.require_gpu()
-    if mask is not None:
-        emissions = _masked_emissions(emissions, mask, device)
+        return h.out_dim
+    gaps, lib, emissions = _missing_route(missing, observed, emissions, device, emission_dim)
     k = _filter_call(_Model(params), emissions, K, "K",
                      (lambda: sample_initial_component_means(params, K)) if initial_means is None else initial_means,
                      params.initial_covariance if initial_covariances is None else initial_covariances, carry, inputs, fields,
@@ -703,18 +703,14 @@ def bootstrap_particle_filter(params, emissions, num_particles: int, key=None, i
     filter runs on a device copy of the emissions with NaN where the mask is false (see :func:`kalman_filter`).
     """
     from .nonlinearities import GaussianLogProb, UserLogProb
-    gaps = _missing_route(missing, observed)
     if not hasattr(params, "emission_distribution_log_prob"):
         raise TypeError("params must be a ParamsBPF (with an emission_distribution_log_prob); got " + type(params).__name__)
     torch = _torch()
-    mask = None
-    if observed is not None:   # (m from the model dimensions; host work only: a mask that does not fit never reaches the device)
+
+    def emission_dim():   # (m from the model dimensions)
         n0, _, dr0 = _param_dims(params)
-        h0 = require_device_function(params.emission_function, "emission", "params.emission_function", n0, dr0)
-        mask = _observed_mask(observed, np.shape(emissions), int(h0.out_dim))
-    lib = _lib.require_gpu()
-    if mask is not None:
-        emissions = _masked_emissions(emissions, mask, device)
+        return require_device_function(params.emission_function, "emission", "params.emission_function", n0, dr0).out_dim
+    gaps, lib, emissions = _missing_route(missing, observed, emissions, device, emission_dim)
     NP = int(num_particles)
     if NP < 1:
         raise ValueError("num_particles must be >= 1")

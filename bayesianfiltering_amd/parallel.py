@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._backward import _front, _wrapper_kw, _LinearDynamics
-from .inference import FULL5, _Lgssm, _kalman_call, _masked_emissions, _missing_route, _observed_mask, _param_dims, _torch
+from .inference import FULL5, _Lgssm, _kalman_call, _missing_route, _param_dims, _torch
 from .nonlinearities import DeviceFunction
 from .sampler import _sampler_front, _sampler_args
 from .smoother import _out_buffer, _smoothed_buffers, _smoothed_result
@@ -101,11 +101,7 @@ def parallel_kalman_filter(params, emissions, *, initial_means=None, initial_cov
     each step's element from a table with one entry per observation pattern, block 0 and the emit launch run the masked step.
     A mask is written as NaN into a device copy of the emissions; the caller's tensor is never written.
     """
-    gaps = _missing_route(missing, observed)
-    mask = None if observed is None else _observed_mask(observed, np.shape(emissions), _Lgssm(params).m)
-    lib = _lib.require_gpu()
-    if mask is not None:
-        emissions = _masked_emissions(emissions, mask, device)
+    gaps, lib, emissions = _missing_route(missing, observed, emissions, device, lambda: _Lgssm(params).m)
     entry = lib.bf_kalman_filter_pscan_missing_f32 if gaps else lib.bf_kalman_filter_pscan_f32
     k = _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
                      return_carry, device)

@@ -1,9 +1,47 @@
 """Shared builders for tests: the same model on the oracle side and on the product side."""
+import glob
+import os
+import re
+
 import numpy as np
 
 from oracle import gaussfilt_oracle as go, models as om, threefry as otf
 
 F32 = np.float32
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bayesianfiltering_amd", "csrc")
+
+
+def read_csrc(name):
+    with open(os.path.join(CSRC, name)) as fh:
+        return fh.read()
+
+
+def instance_rows(name, missing=False):
+    """The ``BF_CASE(...)`` rows of csrc/<name>, a slice of an instance table, as tuples of int in file order.  A slice is built
+    twice (csrc/Makefile); ``missing``: the rows of its -DBF_MISSING=true build, that is without those under ``#if !BF_MISSING``."""
+    src = read_csrc(name)
+    if missing:
+        src = re.sub(r"^#if !BF_MISSING\b.*?^#endif\n", "", src, flags=re.M | re.S)
+    return [tuple(int(x) for x in r.split(",")) for r in re.findall(r"^\s*BF_CASE\(([\d, ]+)\);", src, re.M)]
+
+
+def assert_slices_are_built_twice(family, groups, launch_call, dispatcher):
+    """What makes the missing-observation instances the plain table's: every slice csrc/<family>_group_<g>.hip hands BF_MISSING
+    to its launch template (``launch_call``) and takes its name from BF_GROUP_FN, the Makefile builds every slice plain and
+    with -DBF_MISSING=true, the family's ``dispatcher`` names both functions, and no hand-copied twin exists."""
+    mk, disp, hdr = read_csrc("Makefile"), read_csrc(dispatcher), read_csrc("bf_common.hpp")
+    assert "#define BF_MISSING false" in hdr
+    assert "#define BF_GROUP_FN(FAMILY_, G_) launch_##FAMILY_##_missing_group_##G_" in hdr
+    assert "#define BF_GROUP_FN(FAMILY_, G_) launch_##FAMILY_##_group_##G_" in hdr
+    assert "OBJS = $(SRCS:.hip=.o) $(GROUP_SRCS:.hip=.o) $(GROUP_SRCS:.hip=.missing.o)" in mk
+    assert "%.missing.o: %.hip $(HDRS)\n\t$(HIPCC) $(CXXFLAGS) -DBF_MISSING=true -c $< -o $@" in mk
+    slices = re.search(r"^GROUP_SRCS = (.*)$", mk, re.M).group(1).split()
+    for g in groups:
+        src = read_csrc(f"{family}_group_{g}.hip")
+        assert launch_call in src and f"int BF_GROUP_FN({family}, {g})(" in src, g
+        assert slices.count(f"{family}_group_{g}.hip") == 1, g
+        assert f"launch_{family}_group_{g}" in disp and f"launch_{family}_missing_group_{g}" in disp, g
+    assert not glob.glob(os.path.join(CSRC, "*_missing_group_*.hip"))
 
 
 def cv_model_arrays(dt=0.5, q=1e-2, r=1e-1):

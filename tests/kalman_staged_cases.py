@@ -1,5 +1,5 @@
-"""Every compiled instance of the register Kalman kernel (csrc/kf_scan_group.hpp, the tables of csrc/kf_group_{a,b,c,d}.hip)
-on its LDS-staged emitter: the cases shared by test_kalman_staged_cpu.py (which pins the geometry below to the header's
+"""Every compiled instance of the register Kalman kernel (csrc/kf_scan_group.hpp, the tables of csrc/kf_group_{a,b,c,d}.hip in
+their plain build) on its LDS-staged emitter: the cases shared by test_kalman_staged_cpu.py (which pins the geometry below to the header's
 formulas and checks that the references have headroom, without a GPU) and test_kalman_staged_gpu.py (which runs them).
 
 One case per instance: the 26 (n, m) pairs at their default lanes per trajectory plus (4, 2) at kf_lanes 1 and 4 -- 28.
@@ -62,7 +62,7 @@ def case_id(inst):
 
 
 def default_lanes(n):
-    """launch_kf_group: lanes = n <= 2 ? 1 : (n <= 4 ? 2 : 4)."""
+    """csrc/kf_scan_group.hip, default_lanes: n <= 2 ? 1 : (n <= 4 ? 2 : 4)."""
     return 1 if n <= 2 else (2 if n <= 4 else 4)
 
 

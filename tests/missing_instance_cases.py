@@ -1,6 +1,6 @@
-"""Every compiled instance of the missing-observation routes (``missing="nan"``): the 26 (n, m) pairs of
-csrc/kf_missing_group_{a,b,c,d}.hip, the (n, m, lanes) rows of csrc/gsf_missing_group_{a..e}.hip that
-bf_gsf_ekf_missing_f32 can reach, and the ahead-of-time unscented shapes of csrc/gsf_missing_group_{u,v}.hip that no other
+"""Every compiled instance of the missing-observation routes (``missing="nan"``): the 26 (n, m) pairs of the
+-DBF_MISSING=true build of csrc/kf_group_{a,b,c,d}.hip, the (n, m, lanes) rows of csrc/gsf_group_{a..e}.hip that
+bf_gsf_ekf_missing_f32 can reach, and the ahead-of-time unscented shapes of csrc/ugsf_group_{u,v}.hip that no other
 test launches.  Cases and references shared by tests/test_missing_instances_cpu.py (which validates them without a GPU) and
 tests/test_missing_instances_gpu.py (which runs them).
 
@@ -260,7 +260,7 @@ STANDARD = dict({k: gc.TOL for k in STREAMS[1:] + ("loglik",)}, weights=gc.WTOL)
 
 
 # ==== 3. unscented ===========================================================================================================
-# (n, dq, m, dr) of csrc/gsf_missing_group_{u,v}.hip: those no other test launches, and the three that
+# (n, dq, m, dr) of csrc/ugsf_group_{u,v}.hip: those no other test launches, and the three that
 # tests/test_gsf_missing_gpu.py runs on nonlinear models
 UKF_SHAPES = [(2, 2, 1, 1), (2, 2, 2, 2), (3, 3, 1, 1), (3, 3, 3, 3), (4, 2, 1, 1), (4, 4, 2, 2)]
 UKF_COVERED_ELSEWHERE = [(1, 1, 1, 1), (4, 2, 2, 2), (8, 8, 4, 4)]

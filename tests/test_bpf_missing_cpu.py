@@ -248,22 +248,13 @@ def test_symbol_and_header():
 
 
 # ---- the instance lists -----------------------------------------------------------------------------------------------------
-def _rows(path, macro):
-    return re.findall(rf"^\s*{macro}\(([\d, ]+)\);", open(os.path.join(CSRC, path)).read(), re.M)
-
-
 def test_instance_lists_equal_the_plain_tables():
     total = 0
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    for g in "abc":                                             # file by file: the same (n, dq, m) rows in the same order
-        plain, miss = _rows(f"bpf_group_{g}.hip", "BF_CASE"), _rows(f"bpf_missing_group_{g}.hip", "BF_MISSING_CASE")
+    for g in "abc":                                             # slice by slice: the one list of (n, dq, m) rows serves both builds
+        plain, miss = cm.instance_rows(f"bpf_group_{g}.hip"), cm.instance_rows(f"bpf_group_{g}.hip", missing=True)
         assert plain and plain == miss, (g, plain, miss)
         total += len(miss)
-        src = open(os.path.join(CSRC, f"bpf_missing_group_{g}.hip")).read()
-        assert "launch_bpf_dims<N_, DQ_, M_, true>" in src and f"launch_bpf_missing_group_{g}(" in src
-        assert f"bpf_missing_group_{g}.hip" in mk
     assert total == 12
-    disp = open(os.path.join(CSRC, "bpf_scan.hip")).read()
-    for g in "abc":
-        assert f"missing ? launch_bpf_missing_group_{g} : launch_bpf_group_{g}" in disp
-    assert "bpf_missing.hpp" in open(os.path.join(CSRC, "jit_embed.py")).read()
+    cm.assert_slices_are_built_twice("bpf", "abc", "launch_bpf_dims<N_, DQ_, M_, BF_MISSING>", "bpf_scan.hip")
+    assert "run_groups(missing ? kMissingGroups : kPlainGroups," in cm.read_csrc("bpf_scan.hip")
+    assert "bpf_missing.hpp" in cm.read_csrc("jit_embed.py")

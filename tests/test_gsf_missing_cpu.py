@@ -1,7 +1,7 @@
 """The missing-observation route of the Gaussian-sum filters without a GPU: the reference of tests/gsf_missing_cases.py against
 the oracle and against its float64 copy, what ``missing=`` / ``observed=`` refuse in Python before the device is asked for, what
 bf_gsf_ekf_missing_f32 / bf_ugsf_ukf_missing_f32 refuse before their first HIP call (through ctypes, on host buffers nothing
-reads), the header, and the instance lists of the new translation units."""
+reads), the header, and the instance lists."""
 import ctypes as C
 import os
 import re
@@ -11,6 +11,7 @@ import pytest
 
 from bayesianfiltering_amd import _lib
 from oracle import gaussfilt_oracle as go
+from tests import common as cm
 from tests import gsf_missing_cases as gc
 
 F32 = np.float32
@@ -251,18 +252,14 @@ def test_symbols_and_header():
 
 
 # ---- the instance lists -----------------------------------------------------------------------------------------------------
-def _rows(path, macro):
-    return re.findall(rf"^\s*{macro}\(([\d, ]+)\);", open(os.path.join(CSRC, path)).read(), re.M)
-
-
 def test_instance_lists_equal_the_plain_tables():
-    for g in "abcde":                                           # file by file: the same (n, m, lanes) rows in the same order
-        plain, miss = _rows(f"gsf_group_{g}.hip", "BF_CASE"), _rows(f"gsf_missing_group_{g}.hip", "BF_MISSING_CASE")
+    for g in "abcde":                                           # slice by slice: the one list of (n, m, lanes) rows serves both builds
+        plain, miss = cm.instance_rows(f"gsf_group_{g}.hip"), cm.instance_rows(f"gsf_group_{g}.hip", missing=True)
         assert plain and plain == miss, (g, plain, miss)
-        assert ("SPEC_L96_PICK, true" if g == "e" else "SPEC_GENERIC, true") in open(os.path.join(CSRC, f"gsf_missing_group_{g}.hip")).read()
-    plain = _rows("ugsf_scan.hip", "BF_CASE")
-    miss = _rows("gsf_missing_group_u.hip", "BF_MISSING_CASE") + _rows("gsf_missing_group_v.hip", "BF_MISSING_CASE")
+    cm.assert_slices_are_built_twice("gsf", "abcd", "launch_gsf<N_, M_, NL_, SPEC_GENERIC, BF_MISSING>", "gsf_scan.hip")
+    cm.assert_slices_are_built_twice("gsf", "e", "launch_gsf<N_, M_, NL_, SPEC_L96_PICK, BF_MISSING>", "gsf_scan.hip")
+    plain = cm.instance_rows("ugsf_group_u.hip") + cm.instance_rows("ugsf_group_v.hip")
+    miss = cm.instance_rows("ugsf_group_u.hip", missing=True) + cm.instance_rows("ugsf_group_v.hip", missing=True)
     assert len(plain) == 9 and plain == miss, (plain, miss)
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    for g in "abcdeuv":
-        assert f"gsf_missing_group_{g}.hip" in mk, g
+    assert "BF_CASE" not in cm.read_csrc("ugsf_scan.hip")       # the table left the dispatcher: it calls the groups
+    cm.assert_slices_are_built_twice("ugsf", "uv", "launch_ugsf<N_, DQ_, M_, DR_, BF_MISSING>", "ugsf_scan.hip")

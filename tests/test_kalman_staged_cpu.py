@@ -26,7 +26,9 @@ def test_cases_are_the_compiled_instances():
     assert len(cases) == len(set(cases)) == 28
     assert set(cases) == compiled
     with open(os.path.join(CSRC, "kf_scan_group.hip")) as fh:
-        assert "lanes = p->n <= 2 ? 1 : (p->n <= 4 ? 2 : 4);" in fh.read()
+        src = fh.read()
+    assert "static int default_lanes(int n) { return n <= 2 ? 1 : (n <= 4 ? 2 : 4); }" in src
+    assert "if (lanes == 0 && p->n >= 1 && p->n <= 8) lanes = default_lanes(p->n);" in src
     # per (n, m) the default is the only instance, except (4, 2), which has all three
     by_pair = {}
     for n, m, nl in compiled:

@@ -1,10 +1,8 @@
-"""The cases of tests/test_missing_instances_gpu.py, no GPU: the case lists are the compiled tables of the missing-observation
-translation units (a row added later fails here until it has a case), the vectorised float64 Kalman recursion is the
+"""The cases of tests/test_missing_instances_gpu.py, no GPU: the case lists are the compiled tables as the missing-observation
+build of the slices takes them (a row added later fails here until it has a case), the vectorised float64 Kalman recursion is the
 per-trajectory one of kalman_missing_cases.py, every gap pattern occurs, the list of rows without staged tiles is what the
 headers' formulas give, and on every case the float32 reference is within a fraction of the asserted tolerance of float64 (the
 project's rule: the tolerance never moves, the inputs do)."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -15,42 +13,37 @@ from tests import kalman_missing_cases as kc
 from tests import kalman_staged_cases as ks
 from tests import missing_instance_cases as mi
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bayesianfiltering_amd", "csrc")
 KIDS = [mi.pair_id(p) for p in mi.KALMAN]
 GIDS = [mi.gsf_id(r) for r in mi.GSF_REACHABLE]
 CPU_NREF = 8          # trajectories of a Gaussian-sum case whose headroom is checked here (the fixed patterns among them)
 
 
-def _read(name):
-    with open(os.path.join(CSRC, name)) as fh:
-        return fh.read()
-
-
-def _rows(path, macro="BF_MISSING_CASE"):
-    return [tuple(int(x) for x in r.split(",")) for r in re.findall(rf"^\s*{macro}\(([\d, ]+)\);", _read(path), re.M)]
-
-
 # ---- the instance tables ------------------------------------------------------------------------------------------------
 def test_kalman_cases_are_the_compiled_instances():
-    compiled = [r for g in "abcd" for r in _rows(f"kf_missing_group_{g}.hip")]
-    assert len(compiled) == len(set(compiled)) == 26
+    plain = [r for g in "abcd" for r in cm.instance_rows(f"kf_group_{g}.hip")]
+    compiled = [r for g in "abcd" for r in cm.instance_rows(f"kf_group_{g}.hip", missing=True)]
+    assert len(plain) == len(set(plain)) == 28 and len(compiled) == len(set(compiled)) == 26
+    assert set(plain) - set(compiled) == {(4, 2, 1), (4, 2, 4)}      # the rows marked plain-only: the other lanes of (4, 2)
+    assert [r for r in plain if r in compiled] == compiled
+    cm.assert_slices_are_built_twice("kf", "abcd", "launch_nml<N_, M_, NL_, BF_MISSING>", "kf_scan_group.hip")
     assert set(compiled) == {(n, m, ks.default_lanes(n)) for n, m in mi.KALMAN}
     assert len(mi.KALMAN) == len(set(mi.KALMAN)) == 26
     assert all(mi.geometry(n, m)["lanes"] == ks.default_lanes(n) for n, m in mi.KALMAN)
 
 
 def test_gaussian_sum_cases_are_the_compiled_instances():
-    compiled = [(mi.GENERIC,) + r for g in "abcd" for r in _rows(f"gsf_missing_group_{g}.hip")]
-    compiled += [(mi.L96,) + r for r in _rows("gsf_missing_group_e.hip")]
+    compiled = [(mi.GENERIC,) + r for g in "abcd" for r in cm.instance_rows(f"gsf_group_{g}.hip", missing=True)]
+    compiled += [(mi.L96,) + r for r in cm.instance_rows("gsf_group_e.hip", missing=True)]
     assert len(compiled) == len(set(compiled)) == 33
-    assert "SPEC_L96_PICK, true" in _read("gsf_missing_group_e.hip")
+    cm.assert_slices_are_built_twice("gsf", "abcd", "SPEC_GENERIC, BF_MISSING>", "gsf_scan.hip")
+    cm.assert_slices_are_built_twice("gsf", "e", "SPEC_L96_PICK, BF_MISSING>", "gsf_scan.hip")
     assert len(mi.GSF_REACHABLE) == len(set(mi.GSF_REACHABLE)) == 29 and len(mi.GSF_UNREACHABLE) == 4
     assert set(compiled) == set(mi.GSF_REACHABLE) | set(mi.GSF_UNREACHABLE)
     # unreachable = the rows whose lanes are not the default of their n, which is all the entry point passes on
-    src = _read("gsf_scan.hip")
+    src = cm.read_csrc("gsf_scan.hip")
     assert "static const int kGsfDefaultLanes[9] = {0, 1, 1, 1, 2, 1, 2, 1, 2};" in src
     assert "if (lanes == 0) lanes = gsf_default_lanes(p->n);" in src
-    assert "if (lanes != 0 && lanes != bf::gsf_default_lanes(model->n))" in _read("bf_api.hip")
+    assert "if (lanes != 0 && lanes != bf::gsf_default_lanes(model->n))" in cm.read_csrc("bf_api.hip")
     assert mi.GSF_DEFAULT_LANES == (0, 1, 1, 1, 2, 1, 2, 1, 2)
     assert set(mi.GSF_UNREACHABLE) == {r for r in compiled if r[3] != mi.GSF_DEFAULT_LANES[r[1]]}
     # every generic pair of the Kalman table has its row, and the structured rows are Lorenz-96 shapes (m = n / 2)
@@ -59,7 +52,8 @@ def test_gaussian_sum_cases_are_the_compiled_instances():
 
 
 def test_unscented_cases_are_the_compiled_instances():
-    compiled = _rows("gsf_missing_group_u.hip") + _rows("gsf_missing_group_v.hip")
+    compiled = cm.instance_rows("ugsf_group_u.hip", missing=True) + cm.instance_rows("ugsf_group_v.hip", missing=True)
+    cm.assert_slices_are_built_twice("ugsf", "uv", "launch_ugsf<N_, DQ_, M_, DR_, BF_MISSING>", "ugsf_scan.hip")
     assert len(compiled) == len(set(compiled)) == 9
     assert set(compiled) == set(mi.UKF_SHAPES) | set(mi.UKF_COVERED_ELSEWHERE)
     assert len(mi.UKF_SHAPES) == 6 and not set(mi.UKF_SHAPES) & set(mi.UKF_COVERED_ELSEWHERE)
@@ -80,7 +74,7 @@ def _gsf_staged_ok(n, nl, wsm=16):
 
 
 def test_rows_without_staged_tiles():
-    hpp, common = _read("gsf_scan.hpp"), _read("scan_common.hpp")
+    hpp, common = cm.read_csrc("gsf_scan.hpp"), cm.read_csrc("scan_common.hpp")
     for line in ("static constexpr int CPW = 64 / NL;  // chains per wave", "static constexpr int EP = NS * NS;",
                  "static constexpr int WMIN = 4 * NL;",
                  "static constexpr int WP = (EP >= 32 ? EP : 32) > WMIN ? (EP >= 32 ? EP : 32) : WMIN;",

@@ -239,23 +239,16 @@ def test_symbol_and_header():
 
 
 # ---- the instance lists -----------------------------------------------------------------------------------------------------
-def _rows(path, macro):
-    return re.findall(rf"^\s*{macro}\(([\d, ]+)\);", open(os.path.join(CSRC, path)).read(), re.M)
-
-
 def test_instance_lists_equal_the_plain_tables():
     total = []
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    disp = open(os.path.join(CSRC, "kf_pscan.hip")).read()
-    for g in "abcdef":
-        rows, miss = _rows(f"kf_pscan_group_{g}.hip", "BF_CASE"), _rows(f"kf_pscan_missing_group_{g}.hip", "BF_MISSING_CASE")
+    for g in "abcdef":                                          # slice by slice: the one list of (n, m) rows serves both builds
+        rows, miss = cm.instance_rows(f"kf_pscan_group_{g}.hip"), cm.instance_rows(f"kf_pscan_group_{g}.hip", missing=True)
         assert rows and rows == miss, (g, rows, miss)
         total += miss
-        src = open(os.path.join(CSRC, f"kf_pscan_missing_group_{g}.hip")).read()
-        assert "launch_pscan_nm<N_, M_, true>" in src and f"launch_kf_pscan_missing_group_{g}(" in src
-        assert f"kf_pscan_missing_group_{g}.hip" in mk
-        assert f"launch_kf_pscan_missing_group_{g}" in disp
-    assert sorted(total) == sorted(f"{n}, {m}" for n in range(1, 7) for m in range(1, 5))
+    assert sorted(total) == [(n, m) for n in range(1, 7) for m in range(1, 5)]
+    cm.assert_slices_are_built_twice("kf_pscan", "abcdef", "launch_pscan_nm<N_, M_, BF_MISSING>", "kf_pscan.hip")
+    mk = cm.read_csrc("Makefile")                               # max-ilp: the missing object of slice f, and no other
+    assert re.findall(r"^(\S+): CXXFLAGS \+= .*max-ilp", mk, re.M) == ["kf_pscan_group_f.missing.o"]
     hpp = open(os.path.join(CSRC, "kf_pscan.hpp")).read()
     for name in ("ps_update", "ps_fold_body", "ps_emit_body", "kf_pscan_fold_kernel", "kf_pscan_emit_kernel", "launch_pscan_nm"):
         assert re.search(r"template <int N, int M, bool MISSING = false>\s*\n[^;{]*\b" + name + r"\(", hpp), name
