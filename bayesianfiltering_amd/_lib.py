@@ -122,7 +122,7 @@ class bf_bpf_out(C.Structure):
                 ("resampled", C.c_void_p)]
 
 
-# every symbol include/bayesfilt.h declares: name -> (restype, argtypes)
+# every symbol include/bayesfilt.h and include/bayesfilt_ext.h declare: name -> (restype, argtypes)
 SYMBOLS = {
     "bf_version": (C.c_int, []),
     "bf_abi_check": (C.c_int, [C.c_int32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
@@ -214,6 +214,11 @@ SYMBOLS = {
     "bf_pf_trace_sample_f32": (C.c_int, [C.POINTER(bf_pf_history), C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(bf_pf_sample_carry), C.POINTER(bf_pf_sample_desc), C.c_void_p]),
     "bf_random_uniform_f32": (C.c_int, [C.POINTER(C.c_uint32), C.c_int64, _FP]),
+    # include/bayesfilt_ext.h: missing observations at any dimension (the run-time-dimension kernel)
+    "bf_kalman_filter_missing_anydim_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
+                                                      C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
+    "bf_gsf_ekf_missing_anydim_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_cstream), C.c_int64,
+                                                C.c_int64, C.c_int32, C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
 }
 
 _lib = None

@@ -3,6 +3,7 @@
 // their launchers: rts_smoother.hip, ffbs_sampler.hip, pf_sampler.hip.)
 #include <cstring>
 #include "bf_common.hpp"
+#include "../../include/bayesfilt_ext.h"
 #include "forward_host.hpp"
 #include "pscan_host.hpp"
 #include "user_model.hpp"
@@ -35,9 +36,9 @@ int launch_kf_mfma(const bf_lgssm* p, const bf_cstream* y, long long B, long lon
 int launch_kf_bf32(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry, const bf_out_desc* out,
                    hipStream_t stream, int K, bool multi, int dyn_kind, const float* dth);
 int launch_kf_generic(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
-                      const bf_out_desc* out, hipStream_t stream);
+                      const bf_out_desc* out, hipStream_t stream, bool missing);   // missing: NaN observations are gaps (generic_scan_missing.hip)
 int launch_gsf_generic(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
-                       const bf_carry* carry, const bf_out_desc* out, hipStream_t stream);
+                       const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, bool missing);
 int launch_collapse(const bf_stream* w, const bf_stream* m, const bf_stream* P, long long B, long long T, int K, int n,
                     float* mean_out, float* cov_out, hipStream_t stream);
 int launch_gsf_ekf(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
@@ -235,7 +236,7 @@ int bf_kalman_filter_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, 
   if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
   if (int rc; (rc = bf::check_lgssm(model)) || (rc = bf::check_streams(y, carry))) return rc;
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  auto generic = [&]() { return bf::launch_kf_generic(model, y, B, T, carry, out, hs); };
+  auto generic = [&]() { return bf::launch_kf_generic(model, y, B, T, carry, out, hs, false); };
   if (bf::g_force_generic.load()) return generic();
   // dense products large enough for the matrix cores: (64, 32) itself and, zero-padded into its tiles, every model from
   // n = 24 up (4.9e7 steps/s whatever the size; the run-time-dimension kernel does 3.8e7 at n = 24, 1.6e7 at 32, 1.2e6 at 64)
@@ -295,7 +296,7 @@ int bf_gsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream*
   if (B <= 0 || T <= 0 || K <= 0) return bf::set_error(BF_EINVAL, "B, T and K must be positive");
   if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_streams(y, carry))) return rc;
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  auto generic = [&]() { return bf::launch_gsf_generic(model, y, u, B, T, K, carry, out, hs); };
+  auto generic = [&]() { return bf::launch_gsf_generic(model, y, u, B, T, K, carry, out, hs, false); };
   if (model->user && bf::g_force_generic.load() == 0 && bf::gsf_user_regs_eligible(model, K, out))   // from source, n <= 8: state in registers
     return bf::launch_gsf_user_regs_impl(model, y, u, B, T, K, carry, out, hs);
   if (model->user || model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER) return generic();  // compiled from source
@@ -399,6 +400,35 @@ int bf_ugsf_ukf_missing_f32(const bf_model* model, const bf_ukf_params* uparams,
   if (model->user && model->user->has_lp)
     return bf::set_error(BF_EINVAL, "a log-density from source belongs to the particle filter, not to the unscented filter");
   return bf::launch_ugsf_ukf_missing(model, uparams, y, u, B, T, K, carry, out, static_cast<hipStream_t>(stream));
+}
+
+// Missing observations at any dimension (include/bayesfilt_ext.h): always the run-time-dimension kernel, MISSING = true
+// (generic_scan_missing.hip).  "force_generic" is what these two are, so it changes nothing.  The LDS capacity is the last
+// refusal, made by launch_gsf_generic before its first HIP call.
+int bf_kalman_filter_missing_anydim_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T, const bf_carry* carry,
+                                        const bf_out_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  if (!model || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
+  if (int rc; (rc = bf::check_lgssm(model)) || (rc = bf::check_streams(y, carry))) return rc;
+  if (out->coll_mean.ptr || out->coll_cov.ptr)
+    return bf::set_error(BF_EUNSUPPORTED, "kalman filter with missing observations: collapsed streams are not produced (with one component they equal means / covs)");
+  return bf::launch_kf_generic(model, y, B, T, carry, out, static_cast<hipStream_t>(stream), true);
+}
+
+int bf_gsf_ekf_missing_anydim_f32(const bf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t K,
+                                  const bf_carry* carry, const bf_out_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  static const char* const who = "gaussian-sum filter with missing observations (run-time dimensions)";
+  if (!model || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (B <= 0 || T <= 0 || K <= 0) return bf::set_error(BF_EINVAL, "B, T and K must be positive");
+  if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_streams(y, carry))) return rc;
+  if (out->coll_mean.ptr || out->coll_cov.ptr)
+    return bf::set_error(BF_EUNSUPPORTED, "%s: collapsed streams inside the scan need a compiled instance; use bf_collapse_f32 on the emitted streams", who);
+  if (model->flags != 0) return bf::set_error(BF_EUNSUPPORTED, "%s: the legacy classes (flags != 0) are not served", who);
+  if (model->user && !model->user->has_dyn && !model->user->has_emi)
+    return bf::set_error(BF_EINVAL, "%s: bf_model.user carries only a log-density, which belongs to the particle filter", who);
+  return bf::launch_gsf_generic(model, y, u, B, T, K, carry, out, static_cast<hipStream_t>(stream), true);
 }
 
 int bf_agsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T,

@@ -477,7 +477,11 @@ __device__ void user_emi_linearize(const GenModel& p, const float* x, float u0, 
 }
 #endif
 
-template <int NT>
+// MISSING: a NaN entry of y is a component that was not observed at that step (the contract of DESIGN.md 4a' / 4b').  A
+// workgroup serves one trajectory, so the pattern is uniform over it: the observed rows o of H_x, h(x), y and H_r R H_r^T are
+// compacted to the front (copies; what the model computed for a missing row is never read again) and the update below runs on
+// that reduced model with mo = |o| in place of m.  mo == 0 skips the update by a uniform branch: m+ = m-, P+ = P-, ll = 0.
+template <int NT, bool MISSING = false>
 __device__ __forceinline__ void gsf_generic_body(const GenModel& p, CView y, UViewG u, CarryView carry, OutViews out,
                                                  float* __restrict__ gm, float* __restrict__ gP, long long B, long long T, int K,
                                                  int KP) {
@@ -552,32 +556,59 @@ __device__ __forceinline__ void gsf_generic_body(const GenModel& p, CView y, UVi
         gsync<NT>();
       }
       // ================= _condition_on (inference.py:72-105)
-#ifdef BF_USER_EMI
-      if (p.emi_id == EMI_USER) user_emi_linearize<NT>(p, smean, u0, t, sH, ldn, shx, sRR, ldm, ureg, tid);
-      else
-#endif
-      gen_emi_linearize<NT>(p, smean, u0, t, sH, ldn, shx, sRR, ldm, tid);
-      for (int a = tid; a < m; a += NT) sv[a] = y.p[b * y.sB + t * y.sT + a * y.sE] - shx[a];
-      transpose_lds<NT>(sHT, ldm, sH, ldn, m, n, tid);
-      mm_lds<NT, 0>(sHP, ldn, sH, ldn, sP, ldn, nullptr, 0, m, n, n, tid);           // H_x P
-      gsync<NT>();
-      mm_lds<NT, 1>(sS, ldm, sHP, ldn, sHT, ldm, sRR, ldm, m, n, m, tid);            // S = H_r R H_r^T + (H_x P) H_x^T
-      for (int e = tid; e < m * n; e += NT) sX[(e / n) * ldn + (e % n)] = sHP[(e / n) * ldn + (e % n)];
-      gsync<NT>();
-      for (int e = tid; e < m * m; e += NT) sa[(e / m) * ldm + (e % m)] = sS[(e / m) * ldm + (e % m)] + p.jitter;
-      gsync<NT>();
-      lu_solve_lds<NT>(sa, ldm, sX, ldn, srd, sperm, m, n, tid);                       // psd_solve (utils.py:256-259)
-      transpose_lds<NT>(sXT, ldm, sX, ldn, m, n, tid);                                 // K = X^T
-      gsync<NT>();
-      mm_lds<NT, 0>(sKS, ldm, sXT, ldm, sS, ldm, nullptr, 0, n, m, m, tid);            // K S (un-jittered S)
-      for (int i = tid; i < n; i += NT) {                                               // m+ = m + K v
-        float s = sXT[i * ldm] * sv[0];
-        for (int a = 1; a < m; ++a) s = fmaf(sXT[i * ldm + a], sv[a], s);
-        smean[i] += s;
+      int mo = m;                 // rows the update conditions on
+      float *cH = sH, *cHP = sHP, *cS = sS, *cRR = sRR;
+      if constexpr (MISSING) {
+        // every lane counts the same observed rows; their ascending list goes to sperm, idle until the factorization (the
+        // barriers of the linearisation below publish it)
+        mo = 0;
+        for (int a = 0; a < m; ++a) {
+          const float ya = y.p[b * y.sB + t * y.sT + a * y.sE];
+          if (ya == ya) {
+            if (tid == 0) sperm[mo] = a;
+            ++mo;
+          }
+        }
+        mo = __builtin_amdgcn_readfirstlane(mo);   // the same on every lane: a scalar, so the loops and the branch below stay uniform
       }
-      gsync<NT>();
-      mm_lds<NT, 2>(sP, ldn, sKS, ldm, sX, ldn, sP, ldn, n, m, n, tid);               // P+ = P - (K S) K^T
-      const float ll = chol_logpdf_lds<NT>(sS, sL, ldm, sv, sr, m, tid);               // log N(y; h(m), S) (inference.py:104, :24)
+      float ll = 0.f;
+      if (!MISSING || mo > 0) {
+#ifdef BF_USER_EMI
+        if (p.emi_id == EMI_USER) user_emi_linearize<NT>(p, smean, u0, t, sH, ldn, shx, sRR, ldm, ureg, tid);
+        else
+#endif
+        gen_emi_linearize<NT>(p, smean, u0, t, sH, ldn, shx, sRR, ldm, tid);
+        if constexpr (MISSING) {
+          // rows o of H_x -> the H P tile, (H_r R H_r^T)[o, o] -> the S tile (both dead here); the two pairs then swap roles
+          for (int e = tid; e < mo * n; e += NT) sHP[(e / n) * ldn + (e % n)] = sH[sperm[e / n] * ldn + (e % n)];
+          for (int e = tid; e < mo * mo; e += NT) sS[(e / mo) * ldm + (e % mo)] = sRR[sperm[e / mo] * ldm + sperm[e % mo]];
+          for (int a = tid; a < mo; a += NT) sv[a] = y.p[b * y.sB + t * y.sT + sperm[a] * y.sE] - shx[sperm[a]];
+          cH = sHP; cHP = sH; cS = sRR; cRR = sS;
+          gsync<NT>();
+        } else {
+          for (int a = tid; a < m; a += NT) sv[a] = y.p[b * y.sB + t * y.sT + a * y.sE] - shx[a];
+        }
+        transpose_lds<NT>(sHT, ldm, cH, ldn, mo, n, tid);
+        mm_lds<NT, 0>(cHP, ldn, cH, ldn, sP, ldn, nullptr, 0, mo, n, n, tid);          // H_x P
+        gsync<NT>();
+        mm_lds<NT, 1>(cS, ldm, cHP, ldn, sHT, ldm, cRR, ldm, mo, n, mo, tid);          // S = H_r R H_r^T + (H_x P) H_x^T
+        for (int e = tid; e < mo * n; e += NT) sX[(e / n) * ldn + (e % n)] = cHP[(e / n) * ldn + (e % n)];
+        gsync<NT>();
+        for (int e = tid; e < mo * mo; e += NT) sa[(e / mo) * ldm + (e % mo)] = cS[(e / mo) * ldm + (e % mo)] + p.jitter;
+        gsync<NT>();
+        lu_solve_lds<NT>(sa, ldm, sX, ldn, srd, sperm, mo, n, tid);                      // psd_solve (utils.py:256-259)
+        transpose_lds<NT>(sXT, ldm, sX, ldn, mo, n, tid);                                // K = X^T
+        gsync<NT>();
+        mm_lds<NT, 0>(sKS, ldm, sXT, ldm, cS, ldm, nullptr, 0, n, mo, mo, tid);          // K S (un-jittered S)
+        for (int i = tid; i < n; i += NT) {                                               // m+ = m + K v
+          float s = sXT[i * ldm] * sv[0];
+          for (int a = 1; a < mo; ++a) s = fmaf(sXT[i * ldm + a], sv[a], s);
+          smean[i] += s;
+        }
+        gsync<NT>();
+        mm_lds<NT, 2>(sP, ldn, sKS, ldm, sX, ldn, sP, ldn, n, mo, n, tid);              // P+ = P - (K S) K^T
+        ll = chol_logpdf_lds<NT>(cS, sL, ldm, sv, sr, mo, tid);                          // log N(y; h(m), S) (inference.py:104, :24)
+      }
       if (tid == 0) {
         sll[k] = ll;
         if (out.ll.p) out.ll.p[b * out.ll.sB + k * out.ll.sK + t * out.ll.sT] = ll;
@@ -634,11 +665,11 @@ __device__ __forceinline__ void gsf_generic_body(const GenModel& p, CView y, UVi
 }
 
 #ifndef BF_JIT
-template <int NT>
+template <int NT, bool MISSING = false>
 __global__ void __launch_bounds__(NT)
 gsf_generic_kernel(GenModel p, CView y, UViewG u, CarryView carry, OutViews out, float* __restrict__ gm, float* __restrict__ gP,
                    long long B, long long T, int K, int KP) {
-  gsf_generic_body<NT>(p, y, u, carry, out, gm, gP, B, T, K, KP);
+  gsf_generic_body<NT, MISSING>(p, y, u, carry, out, gm, gP, B, T, K, KP);
 }
 #endif
 

@@ -161,8 +161,13 @@ static int gen_nt64_max() {
   return v;
 }
 
+// generic_scan_missing.hip: the MISSING = true instances (NaN observations are gaps), in a translation unit of their own
+int launch_gsf_generic_missing_kernel(int nt, unsigned grid, size_t lds_bytes, hipStream_t stream, const GenModel& g, const ForwardViews& v,
+                                      UViewG uv, float* gm, float* gP, long long B, long long T, int K, int KP);
+
+// missing: bf_kalman_filter_missing_anydim_f32 / bf_gsf_ekf_missing_anydim_f32 -- the same checks, the same LDS, then the MISSING = true twins
 int launch_gsf_generic(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
-                       const bf_carry* carry, const bf_out_desc* out, hipStream_t stream) {
+                       const bf_carry* carry, const bf_out_desc* out, hipStream_t stream, bool missing) {
   if (out->coll_mean.ptr || out->coll_cov.ptr)
     return set_error(BF_EUNSUPPORTED, "collapsed streams inside the scan need a compiled instance (n <= 8, m <= 4, K x lanes <= 256); "
                                       "use bf_collapse_f32 on the emitted streams");
@@ -210,18 +215,26 @@ int launch_gsf_generic(const bf_model* p, const bf_cstream* y, const bf_cstream*
     // (m_out / P_out may alias m_in / P_in: the kernel reads the inputs at t = 0 only, component by component,
     // before it writes that component's slot)
   }
-  auto [yv, cv, ov] = forward_views(y, carry, out);
+  const ForwardViews fv = forward_views(y, carry, out);
+  auto [yv, cv, ov] = fv;
   UViewG uv = input_view<UViewG>(u);
   hipError_t le;
+  const int nt = (p->n <= gen_nt64_max() && p->m <= gen_nt64_max()) ? 64 : 256;
   if (p->user) {  // the run-time build of the same kernel with the caller's functions compiled in (user_model.hip)
     int kp = KP;
     void* args[] = {&g, &yv, &uv, &cv, &ov, &gm, &gP, &B, &T, &K, &kp};
-    const int nt = (p->n <= gen_nt64_max() && p->m <= gen_nt64_max()) ? 64 : 256;
-    rc = launch_user_kernel(p->user, nt, (unsigned)B, lds_bytes, stream, args);
+    hipFunction_t fn = nullptr;   // plain: the handle's k64 / k256; with gaps: the twin of this workgroup size, built on first use
+    if (missing) rc = user_kernel(p->user, JIT_GSF_GENERIC_MISSING, 0, nt / 64, JIT_SPEC_USER, &fn);
+    if (rc == BF_OK) rc = launch_user_kernel(p->user, nt, (unsigned)B, lds_bytes, stream, args, fn);
     if (scratch) (void)hipFreeAsync(scratch, stream);
     return rc;
   }
-  if (p->n <= gen_nt64_max() && p->m <= gen_nt64_max()) {
+  if (missing) {
+    rc = launch_gsf_generic_missing_kernel(nt, (unsigned)B, lds_bytes, stream, g, fv, uv, gm, gP, B, T, K, KP);
+    if (scratch) (void)hipFreeAsync(scratch, stream);
+    return rc;
+  }
+  if (nt == 64) {
     auto kern = gsf_generic_kernel<64>;
     if (lds_bytes > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), lds_bytes, stream, g, yv, uv, cv, ov, gm, gP, B, T, K, KP);
@@ -239,7 +252,7 @@ int launch_gsf_generic(const bf_model* p, const bf_cstream* y, const bf_cstream*
 
 // The linear model of bf_kalman_filter_f32 as a registry model (DYN_LINEAR / EMI_LINEAR), K = 1.
 int launch_kf_generic(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
-                      const bf_out_desc* out, hipStream_t stream) {
+                      const bf_out_desc* out, hipStream_t stream, bool missing) {
   const int n = p->n, m = p->m, dq = p->dq, dr = p->dr;
   std::vector<float> dth((size_t)n * n + (size_t)n * dq), eth((size_t)m * n + (size_t)m * dr);
   for (int i = 0; i < n * n; ++i) dth[i] = p->A[i];
@@ -253,7 +266,7 @@ int launch_kf_generic(const bf_lgssm* p, const bf_cstream* y, long long B, long 
   mdl.dyn_id = DYN_LINEAR; mdl.emi_id = EMI_LINEAR; mdl.n = n; mdl.dq = dq; mdl.m = m; mdl.dr = dr;
   mdl.dyn_theta = dth.data(); mdl.n_dyn_theta = (int)dth.size(); mdl.emi_theta = eth.data(); mdl.n_emi_theta = (int)eth.size();
   mdl.q0 = p->q0; mdl.r0 = p->r0; mdl.Q = p->Q; mdl.R = p->R; mdl.flags = 0; mdl.Q_steps = p->Q_steps; mdl.R_steps = p->R_steps;
-  return launch_gsf_generic(&mdl, y, nullptr, B, T, 1, carry, out, stream);
+  return launch_gsf_generic(&mdl, y, nullptr, B, T, 1, carry, out, stream, missing);
 }
 
 

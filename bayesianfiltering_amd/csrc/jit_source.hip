@@ -93,8 +93,9 @@ __device__ inline Dual fma(Dual a, float b, Dual c) { return a * b + c; }
 
 // The run-time-dimension Gaussian-sum scan (generic_device.hpp) with dual-number Jacobians: libm's float functions.
 // nt_ugsf = 0: its two entry points; 64 / 256: the run-time-dimension unscented scan (ugsf_generic_device.hpp) instead, on the
-// same headers and the same float functions -- values of f and h only, no Jacobians.
-std::string generic_scan_source(const bf_user_model& um, int nt_ugsf) {
+// same headers and the same float functions -- values of f and h only, no Jacobians.  nt_missing = 64 / 256: the MISSING = true
+// twin of the Gaussian-sum scan at that workgroup size (NaN observations are gaps), one entry point.
+std::string generic_scan_source(const bf_user_model& um, int nt_ugsf, int nt_missing = 0) {
   std::string s;
   s += "#define BF_JIT 1\n";
   if (um.has_dyn) s += "#define BF_USER_DYN 1\n";
@@ -117,6 +118,13 @@ std::string generic_scan_source(const bf_user_model& um, int nt_ugsf) {
     s += "extern \"C\" __global__ void __launch_bounds__(" + nt + ") bf_user_ugsf_generic(bf::UgModel p, bf::CView y, bf::UViewG u, bf::CarryView carry,\n"
          "    bf::OutViews out, float* gm, float* gP, long long B, long long T, int K, int KP) {\n"
          "  bf::ugsf_generic_body<" + nt + ">(p, y, u, carry, out, gm, gP, B, T, K, KP);\n}\n";
+    return s;
+  }
+  if (nt_missing != 0) {
+    const std::string nt = std::to_string(nt_missing);
+    s += "extern \"C\" __global__ void __launch_bounds__(" + nt + ") bf_user_scan_missing(bf::GenModel p, bf::CView y, bf::UViewG u, bf::CarryView carry,\n"
+         "    bf::OutViews out, float* gm, float* gP, long long B, long long T, int K, int KP) {\n"
+         "  bf::gsf_generic_body<" + nt + ", true>(p, y, u, carry, out, gm, gP, B, T, K, KP);\n}\n";
     return s;
   }
   s += R"BFSRC(
@@ -175,6 +183,7 @@ const char* jit_entry_name(int kind, int variant) {
     case JIT_SAMPLE: return "bf_user_sample";
     case JIT_BPF_BIG: return "bf_user_bpf_big";
     case JIT_UGSF_GENERIC: return "bf_user_ugsf_generic";
+    case JIT_GSF_GENERIC_MISSING: return "bf_user_scan_missing";
     default: return "bf_user_scan_64";
   }
 }
@@ -182,6 +191,7 @@ const char* jit_entry_name(int kind, int variant) {
 std::string jit_source(const bf_user_model& um, int kind, int ppt, int nw, int spec_id) {
   if (kind == JIT_GSF_GENERIC) return generic_scan_source(um, 0);
   if (kind == JIT_UGSF_GENERIC) return generic_scan_source(um, 64 * nw);   // nw = 1: one wave per trajectory, 4: four
+  if (kind == JIT_GSF_GENERIC_MISSING) return generic_scan_source(um, 0, 64 * nw);
   if (kind == JIT_RTS_GENERIC || kind == JIT_FFBS_GENERIC || kind == JIT_GS_RTS_GENERIC || kind == JIT_GS_FFBS_GENERIC) {
     // The run-time-dimension kernels of the smoother / the posterior sampler around the caller's dynamics: libm's float functions
     // under the dual numbers, as in JIT_GSF_GENERIC, whose streams they read; the kernel bodies are rts_generic.hpp's, with every

@@ -12,7 +12,8 @@
 enum bf_jit_kind { JIT_GSF_GENERIC, JIT_BPF, JIT_UGSF, JIT_AGSF_UKF, JIT_AGSF_EKF, JIT_GSF_REGS, JIT_SAMPLE, JIT_BPF_BIG, JIT_UGSF_GENERIC,
                    JIT_RTS_REGS, JIT_FFBS_REGS, JIT_RTS_GENERIC, JIT_FFBS_GENERIC,     // the smoother's / the posterior sampler's kernels around dynamics from source
                    JIT_GS_RTS_REGS, JIT_GS_RTS_GENERIC, JIT_GS_FFBS_REGS, JIT_GS_FFBS_GENERIC,     // the Gaussian-sum smoother's / sampler's (K chains per trajectory)
-                   JIT_BPF_MISSING, JIT_BPF_BIG_MISSING };   // the particle filter's MISSING = true twins (NaN observations are gaps)
+                   JIT_BPF_MISSING, JIT_BPF_BIG_MISSING,     // the particle filter's MISSING = true twins (NaN observations are gaps)
+                   JIT_GSF_GENERIC_MISSING };   // ... and the run-time-dimension Gaussian-sum scan's, one entry point per workgroup size (nw = 1 or 4 waves)
 // the model structure a sampling kernel is compiled for: the handle's own functions, or (registry models) bpf_scan.hpp's specs
 enum bf_jit_spec { JIT_SPEC_USER = 0, JIT_SPEC_RUNTIME = 1, JIT_SPEC_L96_PICK = 2 };
 

@@ -361,6 +361,22 @@ def _missing_route(missing, observed, emissions, device, emission_dim):
     return missing == "nan" or observed is not None, lib, emissions
 
 
+def _gapped_entry(family, n, m, dq, dr, from_source=False, options=None):
+    """Name of the C entry point that serves a call WITH gaps.  ``family``: "kalman" (linear model, one component) or "gsf"
+    (the extended Gaussian-sum filter).  The register kernels of ``bf_*_missing_f32`` take what they always took; what they
+    cannot take -- Kalman: n > 8, m > 4 or m > n; Gaussian sum: registry functions with n > 8 or m > 4, functions from source
+    or recorded ones with any dimension above 8 -- and every call with ``options={"force_generic": 1}`` goes to the
+    run-time-dimension kernel (``bf_*_missing_anydim_f32``, include/bayesfilt_ext.h).  Pure: no library, no device."""
+    force = bool(options) and int(options.get("force_generic", 0)) != 0
+    if family == "kalman":
+        beyond = n > 8 or m > 4 or m > n
+        return "bf_kalman_filter_missing_anydim_f32" if (beyond or force) else "bf_kalman_filter_missing_f32"
+    if family != "gsf":
+        raise ValueError(f"unknown filter family {family!r}")
+    beyond = max(n, dq, m, dr) > 8 if from_source else (n > 8 or m > 4)
+    return "bf_gsf_ekf_missing_anydim_f32" if (beyond or force) else "bf_gsf_ekf_missing_f32"
+
+
 def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
                   fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
                   return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None,
@@ -376,8 +392,11 @@ def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=
     previously returned posterior whose buffers are reused.
 
     ``missing="nan"``: a NaN entry of ``emissions`` is a component that was not observed at that step
-    (``bf_kalman_filter_missing_f32``: the update conditions on the observed rows only, a step with none is predict-only with
-    log-likelihood 0; n <= 8 and m <= 4).  Without it a NaN poisons its trajectory from that step on, as ever.  +-Inf is never
+    (the update conditions on the observed rows only, a step with none is predict-only with log-likelihood 0), at any
+    dimensions: ``bf_kalman_filter_missing_f32`` (register kernels) for n <= 8 and m <= min(n, 4), else -- or with
+    ``options={"force_generic": 1}`` -- ``bf_kalman_filter_missing_anydim_f32`` (the run-time-dimension kernel, as far as its
+    160 KiB of LDS go; a gapped model with n >= 16 leaves the matrix-core route for it, DESIGN.md 4a'').  Without it a NaN
+    poisons its trajectory from that step on, as ever.  +-Inf is never
     "missing".  ``observed``: a bool mask of shape (T,), (B, T), (T, m) or (B, T, m), true where the entry was observed; it
     implies ``missing="nan"`` and the filter runs on a device copy of the emissions with NaN where the mask is false.
     """
@@ -385,7 +404,7 @@ def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=
     k = _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
                      return_carry, device)
     _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
-    entry = lib.bf_kalman_filter_missing_f32 if gaps else lib.bf_kalman_filter_f32
+    entry = getattr(lib, _gapped_entry("kalman", k.mdl.n, k.mdl.m, k.mdl.dq, k.mdl.dr, False, options)) if gaps else lib.bf_kalman_filter_f32
     _lib.check(entry(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od), C.c_void_p(k.stream)))
     return k.result()
 
@@ -495,9 +514,12 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
     ``missing="nan"``: a NaN entry of ``emissions`` is a component that was not observed at that step
     (``bf_gsf_ekf_missing_f32``, DESIGN.md 4b'): every component of the bank conditions on the observed rows only, a step with
     none leaves means and covariances untouched with log-likelihood 0 (the weights are renormalised only), trailing gaps are a
-    forecast.  Register kernels only: registry models with n <= 8 and m <= 4, models from source with every dimension <= 8.
-    Without it a NaN poisons its trajectory, as ever; +-Inf is never "missing".  ``observed``: a bool mask of shape (T,),
-    (B, T), (T, m) or (B, T, m), true where the entry was observed; it implies ``missing="nan"`` (see :func:`kalman_filter`).
+    forecast.  Any dimensions: the register kernels take registry models with n <= 8 and m <= 4 and models from source with
+    every dimension <= 8; everything larger -- and any call with ``options={"force_generic": 1}`` -- runs on the
+    run-time-dimension kernel (``bf_gsf_ekf_missing_anydim_f32``, DESIGN.md 4a''; no collapsed streams there).  The unscented
+    bank keeps its limit (every dimension <= 8).  Without it a NaN poisons its trajectory, as ever; +-Inf is never "missing".
+    ``observed``: a bool mask of shape (T,), (B, T), (T, m) or (B, T, m), true where the entry was observed; it implies
+    ``missing="nan"`` (see :func:`kalman_filter`).
     """
     torch = _torch()
     K = int(num_components)
@@ -525,7 +547,9 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
         coll = (tuple(k.unwrap(v) for v in coll),)
     # (_uparams: the unscented bank -- same carry / streams, sigma-point moment matching instead of Jacobians)
     if _uparams is None:
-        fn, head = (lib.bf_gsf_ekf_missing_f32 if gaps else lib.bf_gsf_ekf_f32), ()
+        c = k.mdl.c
+        fn = getattr(lib, _gapped_entry("gsf", c.n, c.m, c.dq, c.dr, bool(c.user), options)) if gaps else lib.bf_gsf_ekf_f32
+        head = ()
     else:
         fn, head = (lib.bf_ugsf_ukf_missing_f32 if gaps else lib.bf_ugsf_ukf_f32), (C.byref(_uparams),)
     _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
