@@ -219,6 +219,11 @@ SYMBOLS = {
                                                       C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
     "bf_gsf_ekf_missing_anydim_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_cstream), C.c_int64,
                                                 C.c_int64, C.c_int32, C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
+    # include/bayesfilt_ext2.h: missing observations on the one-wave matrix-core kernel (elsewhere: the two above)
+    "bf_kalman_filter_missing_tiles_f32": (C.c_int, [C.POINTER(bf_lgssm), C.POINTER(bf_cstream), C.c_int64, C.c_int64,
+                                                     C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
+    "bf_gsf_ekf_missing_tiles_f32": (C.c_int, [C.POINTER(bf_model), C.POINTER(bf_cstream), C.POINTER(bf_cstream), C.c_int64,
+                                               C.c_int64, C.c_int32, C.POINTER(bf_carry), C.POINTER(bf_out_desc), C.c_void_p]),
 }
 
 _lib = None

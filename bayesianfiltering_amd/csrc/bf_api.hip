@@ -3,7 +3,7 @@
 // their launchers: rts_smoother.hip, ffbs_sampler.hip, pf_sampler.hip.)
 #include <cstring>
 #include "bf_common.hpp"
-#include "../../include/bayesfilt_ext.h"
+#include "../../include/bayesfilt_ext2.h"
 #include "forward_host.hpp"
 #include "pscan_host.hpp"
 #include "user_model.hpp"
@@ -34,7 +34,7 @@ int launch_kf_missing_group(const bf_lgssm* p, const bf_cstream* y, long long B,
 int launch_kf_mfma(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
                    const bf_out_desc* out, hipStream_t stream, int K, bool multi, int dyn_kind, const float* dth);
 int launch_kf_bf32(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry, const bf_out_desc* out,
-                   hipStream_t stream, int K, bool multi, int dyn_kind, const float* dth);
+                   hipStream_t stream, int K, bool multi, int dyn_kind, const float* dth, bool missing);   // missing: the MISSING = true twins (kf_scan_bf32_missing.hip)
 int launch_kf_generic(const bf_lgssm* p, const bf_cstream* y, long long B, long long T, const bf_carry* carry,
                       const bf_out_desc* out, hipStream_t stream, bool missing);   // missing: NaN observations are gaps (generic_scan_missing.hip)
 int launch_gsf_generic(const bf_model* p, const bf_cstream* y, const bf_cstream* u, long long B, long long T, int K,
@@ -108,6 +108,38 @@ Option& rts_load_mode_option();  // rts_smoother.hip: -1 = from the layout, 0 = 
 static Option g_kf_small_mode{1, OPT_KF_SMALL_MODE};   // bf_set_option "kf_small_mode": 1 = one-wave matrix-core kernel for 9 <= n <= 32 (default), 0 = off
 static Option g_force_generic{0, OPT_FORCE_GENERIC};  // 1 = run the run-time-dimension kernel even where a compiled instance exists
 Option& force_generic_option() { return g_force_generic; }  // read by the backward family's entry points (backward_host.hpp)
+
+// The shapes of the one-wave matrix-core kernel (kf_scan_bf32.hip) -- 9 <= n <= 32, m <= 32 and (n >= 16 or m > 8) -- unless
+// "kf_small_mode" is 0
+static bool kf_small_tiles(int n, int m) { return n >= 9 && n <= 32 && m <= 32 && (n >= 16 || m > 8) && g_kf_small_mode.load() != 0; }
+
+// A Gaussian-sum model the matrix-core Kalman kernels can run as K chains of a linear model: a linear emission, no legacy class,
+// K <= 64 and either linear dynamics or registry dynamics with an analytic, sparse Jacobian and identity noise input
+// (dyn_kind 1 = Lorenz-96, 2 = sine: extended Kalman chains on the one-wave kernel).  `lg` points into the model's arrays.
+struct GsfTiles {
+  bool linear;
+  bf_lgssm lg;
+  int dyn_kind;
+  float dth[8];
+};
+static GsfTiles gsf_tiles(const bf_model* model, int K) {
+  GsfTiles t;
+  std::memset(&t, 0, sizeof(t));
+  const bool lin_emi = model->emi_id == 0 && model->n_emi_theta == model->m * model->n + model->m * model->dr;
+  const bool lin_dyn = model->dyn_id == 0 && model->n_dyn_theta == model->n * model->n + model->n * model->dq;
+  t.dyn_kind = (model->dyn_id == 1 && model->n_dyn_theta == 5 && model->dq == model->n) ? 1
+             : (model->dyn_id == 4 && model->n_dyn_theta == 1 && model->dq == model->n) ? 2 : 0;
+  t.linear = lin_emi && model->flags == 0 && K <= 64 && (lin_dyn || t.dyn_kind != 0);
+  if (!t.linear) return t;
+  bf_lgssm& lg = t.lg;
+  lg.n = model->n; lg.dq = model->dq; lg.m = model->m; lg.dr = model->dr;
+  if (lin_dyn) { lg.A = model->dyn_theta; lg.G = model->dyn_theta + model->n * model->n; t.dyn_kind = 0; }
+  lg.H = model->emi_theta; lg.D = model->emi_theta + model->m * model->n;
+  lg.q0 = model->q0; lg.r0 = model->r0; lg.Q = model->Q; lg.R = model->R;
+  lg.Q_steps = model->Q_steps > 0 ? model->Q_steps : 1; lg.R_steps = model->R_steps > 0 ? model->R_steps : 1;
+  if (!lin_dyn) for (int i = 0; i < model->n_dyn_theta && i < 8; ++i) t.dth[i] = model->dyn_theta[i];
+  return t;
+}
 Option& ffbs_spl_option();  // ffbs_sampler.hip: 0 = from S and n, else samples per lane of the register kernel
 Option& pkf_block_option();  // kf_pscan.hip: 0 = from (B, T), else the block length of the parallel-in-time Kalman filter
 Option& prs_block_option();  // rts_pscan.hip: 0 = from (B, T), else the block length of the parallel-in-time RTS smoother
@@ -242,8 +274,8 @@ int bf_kalman_filter_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, 
   // n = 24 up (4.9e7 steps/s whatever the size; the run-time-dimension kernel does 3.8e7 at n = 24, 1.6e7 at 32, 1.2e6 at 64)
   // 9 <= n <= 32: one wave per trajectory on single 32 x 32 tiles, 1.8e8 steps/s whatever the size; the run-time-dimension
   // kernel is faster only for the smallest of them (n = 12, m = 4: 1.7e8; n = 16, m = 8: 1.0e8; (32, 32): 3.5e6)
-  if (model->n >= 9 && model->n <= 32 && model->m <= 32 && (model->n >= 16 || model->m > 8) && bf::g_kf_small_mode.load() != 0)
-    return bf::with_generic_fallback(bf::launch_kf_bf32(model, y, B, T, carry, out, hs, 1, false, 0, nullptr), generic);
+  if (bf::kf_small_tiles(model->n, model->m))
+    return bf::with_generic_fallback(bf::launch_kf_bf32(model, y, B, T, carry, out, hs, 1, false, 0, nullptr, false), generic);
   if (model->n >= 24 && model->n <= 64 && model->m <= 32)
     return bf::with_generic_fallback(bf::launch_kf_mfma(model, y, B, T, carry, out, hs, 1, false, 0, nullptr), generic);
   return bf::with_generic_fallback(
@@ -304,30 +336,14 @@ int bf_gsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream*
   // a LINEAR model beyond the register kernels (n >= 9): the Gaussian-sum filter's K components take turns on the matrix-core
   // kernels (bf16 three-term products: one wave per trajectory on single 32 x 32 tiles up to n = 32, four waves on 64 x 64 up
   // to n = 64), per-step Q_t / R_t tables included
-  const bool small_tiles = model->n >= 9 && model->n <= 32 && model->m <= 32 && (model->n >= 16 || model->m > 8) && bf::g_kf_small_mode.load() != 0;
+  const bf::GsfTiles tl = bf::gsf_tiles(model, K);
+  const bool small_tiles = bf::kf_small_tiles(model->n, model->m);
   const bool big_tiles = !small_tiles && model->n >= 24 && model->n <= 64 && model->m <= 32;
-  const bool lin_emi = model->emi_id == 0 && model->n_emi_theta == model->m * model->n + model->m * model->dr;
-  const bool lin_dyn = model->dyn_id == 0 && model->n_dyn_theta == model->n * model->n + model->n * model->dq;
-  // registry dynamics with an analytic, sparse Jacobian and identity noise input: extended Kalman chains on the one-wave kernel
-  const int dyn_kind = (model->dyn_id == 1 && model->n_dyn_theta == 5 && model->dq == model->n) ? 1
-                     : (model->dyn_id == 4 && model->n_dyn_theta == 1 && model->dq == model->n) ? 2 : 0;
-  if (lin_emi && model->flags == 0 && K <= 64 && !out->coll_mean.ptr && !out->coll_cov.ptr &&
-      (small_tiles || big_tiles) && (lin_dyn || dyn_kind != 0)) {
-    bf_lgssm lg;
-    std::memset(&lg, 0, sizeof(lg));
-    lg.n = model->n; lg.dq = model->dq; lg.m = model->m; lg.dr = model->dr;
-    if (lin_dyn) { lg.A = model->dyn_theta; lg.G = model->dyn_theta + model->n * model->n; }
-    lg.H = model->emi_theta; lg.D = model->emi_theta + model->m * model->n;
-    lg.q0 = model->q0; lg.r0 = model->r0; lg.Q = model->Q; lg.R = model->R;
-    lg.Q_steps = model->Q_steps > 0 ? model->Q_steps : 1; lg.R_steps = model->R_steps > 0 ? model->R_steps : 1;
-    if (!lin_dyn) {
-      float dth[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int i = 0; i < model->n_dyn_theta && i < 8; ++i) dth[i] = model->dyn_theta[i];
-      if (small_tiles) return bf::with_generic_fallback(bf::launch_kf_bf32(&lg, y, B, T, carry, out, hs, K, true, dyn_kind, dth), generic);
-      return bf::with_generic_fallback(bf::launch_kf_mfma(&lg, y, B, T, carry, out, hs, K, true, dyn_kind, dth), generic);
-    }
-    if (small_tiles) return bf::with_generic_fallback(bf::launch_kf_bf32(&lg, y, B, T, carry, out, hs, K, K > 1, 0, nullptr), generic);
-    return bf::with_generic_fallback(bf::launch_kf_mfma(&lg, y, B, T, carry, out, hs, K, K > 1, 0, nullptr), generic);   // 33 <= n <= 64: four waves per trajectory
+  if (tl.linear && !out->coll_mean.ptr && !out->coll_cov.ptr && (small_tiles || big_tiles)) {
+    const bool multi = tl.dyn_kind != 0 || K > 1;
+    const float* dth = tl.dyn_kind != 0 ? tl.dth : nullptr;
+    if (small_tiles) return bf::with_generic_fallback(bf::launch_kf_bf32(&tl.lg, y, B, T, carry, out, hs, K, multi, tl.dyn_kind, dth, false), generic);
+    return bf::with_generic_fallback(bf::launch_kf_mfma(&tl.lg, y, B, T, carry, out, hs, K, multi, tl.dyn_kind, dth), generic);   // 33 <= n <= 64: four waves per trajectory
   }
   return bf::with_generic_fallback(
       bf::launch_gsf_ekf(model, y, u, B, T, K, carry, out, hs, bf::g_kf_emit_mode.load(), bf::g_kf_lanes.load()), generic);
@@ -429,6 +445,48 @@ int bf_gsf_ekf_missing_anydim_f32(const bf_model* model, const bf_cstream* y, co
   if (model->user && !model->user->has_dyn && !model->user->has_emi)
     return bf::set_error(BF_EINVAL, "%s: bf_model.user carries only a log-density, which belongs to the particle filter", who);
   return bf::launch_gsf_generic(model, y, u, B, T, K, carry, out, static_cast<hipStream_t>(stream), true);
+}
+
+// Missing observations on the one-wave matrix-core kernel (include/bayesfilt_ext2.h): where the plain twin would take that
+// kernel, its MISSING = true instance; everywhere else -- and when that launch answers BF_EUNSUPPORTED -- the two entry points
+// above, refusal for refusal and bit for bit.
+int bf_kalman_filter_missing_tiles_f32(const bf_lgssm* model, const bf_cstream* y, int64_t B, int64_t T, const bf_carry* carry,
+                                       const bf_out_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  if (!model || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (B <= 0 || T <= 0) return bf::set_error(BF_EINVAL, "B and T must be positive (B=%lld, T=%lld)", (long long)B, (long long)T);
+  if (int rc; (rc = bf::check_lgssm(model)) || (rc = bf::check_streams(y, carry))) return rc;
+  if (out->coll_mean.ptr || out->coll_cov.ptr)
+    return bf::set_error(BF_EUNSUPPORTED, "kalman filter with missing observations: collapsed streams are not produced (with one component they equal means / covs)");
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  auto generic = [&]() { return bf::launch_kf_generic(model, y, B, T, carry, out, hs, true); };
+  if (bf::g_force_generic.load() == 0 && bf::kf_small_tiles(model->n, model->m))
+    return bf::with_generic_fallback(bf::launch_kf_bf32(model, y, B, T, carry, out, hs, 1, false, 0, nullptr, true), generic);
+  return generic();
+}
+
+int bf_gsf_ekf_missing_tiles_f32(const bf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T, int32_t K,
+                                 const bf_carry* carry, const bf_out_desc* out, void* stream) {
+  bf::CallOptionScope call_option_scope;
+  static const char* const who = "gaussian-sum filter with missing observations (run-time dimensions)";
+  if (!model || !y || !carry || !out) return bf::set_error(BF_EINVAL, "NULL argument");
+  if (B <= 0 || T <= 0 || K <= 0) return bf::set_error(BF_EINVAL, "B, T and K must be positive");
+  if (int rc; (rc = bf::check_model(model)) || (rc = bf::check_streams(y, carry))) return rc;
+  if (out->coll_mean.ptr || out->coll_cov.ptr)
+    return bf::set_error(BF_EUNSUPPORTED, "%s: collapsed streams inside the scan need a compiled instance; use bf_collapse_f32 on the emitted streams", who);
+  if (model->flags != 0) return bf::set_error(BF_EUNSUPPORTED, "%s: the legacy classes (flags != 0) are not served", who);
+  if (model->user && !model->user->has_dyn && !model->user->has_emi)
+    return bf::set_error(BF_EINVAL, "%s: bf_model.user carries only a log-density, which belongs to the particle filter", who);
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  auto generic = [&]() { return bf::launch_gsf_generic(model, y, u, B, T, K, carry, out, hs, true); };
+  const bool from_source = model->user || model->dyn_id == BF_FN_USER || model->emi_id == BF_FN_USER;
+  if (!from_source && bf::g_force_generic.load() == 0 && bf::kf_small_tiles(model->n, model->m)) {
+    const bf::GsfTiles tl = bf::gsf_tiles(model, K);
+    if (tl.linear)
+      return bf::with_generic_fallback(bf::launch_kf_bf32(&tl.lg, y, B, T, carry, out, hs, K, tl.dyn_kind != 0 || K > 1, tl.dyn_kind,
+                                                          tl.dyn_kind != 0 ? tl.dth : nullptr, true), generic);
+  }
+  return generic();
 }
 
 int bf_agsf_ekf_f32(const bf_model* model, const bf_cstream* y, const bf_cstream* u, int64_t B, int64_t T,

@@ -377,6 +377,15 @@ def _gapped_entry(family, n, m, dq, dr, from_source=False, options=None):
     return "bf_gsf_ekf_missing_anydim_f32" if (beyond or force) else "bf_gsf_ekf_missing_f32"
 
 
+def _gapped_route(name, options=None):
+    """The entry point a gapped call really takes, given the name :func:`_gapped_entry` chose: an ``*_anydim_*`` name becomes
+    its ``*_tiles_*`` twin (include/bayesfilt_ext2.h) -- the MISSING instance of the one-wave matrix-core kernel where the plain
+    call would run that kernel, the ``*_anydim_*`` entry point itself (same refusals, same kernel, same bits) everywhere else --
+    unless ``options`` sets ``force_generic``, which keeps the run-time-dimension kernel by name.  Pure: no library, no device."""
+    force = bool(options) and int(options.get("force_generic", 0)) != 0
+    return name if force else name.replace("_missing_anydim_", "_missing_tiles_")
+
+
 def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=None, carry=None,
                   fields: Sequence[str] = FULL5, layout: str = "reference", out=None,
                   return_loglik: bool = False, return_carry: bool = False, device="cuda", options=None,
@@ -393,9 +402,11 @@ def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=
 
     ``missing="nan"``: a NaN entry of ``emissions`` is a component that was not observed at that step
     (the update conditions on the observed rows only, a step with none is predict-only with log-likelihood 0), at any
-    dimensions: ``bf_kalman_filter_missing_f32`` (register kernels) for n <= 8 and m <= min(n, 4), else -- or with
-    ``options={"force_generic": 1}`` -- ``bf_kalman_filter_missing_anydim_f32`` (the run-time-dimension kernel, as far as its
-    160 KiB of LDS go; a gapped model with n >= 16 leaves the matrix-core route for it, DESIGN.md 4a'').  Without it a NaN
+    dimensions: ``bf_kalman_filter_missing_f32`` (register kernels) for n <= 8 and m <= min(n, 4); the MISSING instance of the
+    one-wave matrix-core kernel (``bf_kalman_filter_missing_tiles_f32``, DESIGN.md 4a''') where the plain call runs that
+    kernel -- 9 <= n <= 32, m <= 32 and (n >= 16 or m > 8); everywhere else -- or with ``options={"force_generic": 1}`` --
+    the run-time-dimension kernel (``bf_kalman_filter_missing_anydim_f32``, DESIGN.md 4a'', as far as its 160 KiB of LDS go;
+    a gapped model with 33 <= n <= 64 leaves the four-wave matrix-core route for it).  Without it a NaN
     poisons its trajectory from that step on, as ever.  +-Inf is never
     "missing".  ``observed``: a bool mask of shape (T,), (B, T), (T, m) or (B, T, m), true where the entry was observed; it
     implies ``missing="nan"`` and the filter runs on a device copy of the emissions with NaN where the mask is false.
@@ -404,7 +415,7 @@ def kalman_filter(params, emissions, *, initial_means=None, initial_covariances=
     k = _kalman_call(params, emissions, initial_means, initial_covariances, carry, fields, layout, out, return_loglik,
                      return_carry, device)
     _lib.arm_call_options(lib, options)      # tuning options for THIS call only (bf_set_call_option)
-    entry = getattr(lib, _gapped_entry("kalman", k.mdl.n, k.mdl.m, k.mdl.dq, k.mdl.dr, False, options)) if gaps else lib.bf_kalman_filter_f32
+    entry = getattr(lib, _gapped_route(_gapped_entry("kalman", k.mdl.n, k.mdl.m, k.mdl.dq, k.mdl.dr, False, options), options)) if gaps else lib.bf_kalman_filter_f32
     _lib.check(entry(C.byref(k.mdl.c), C.byref(k.yd), k.B, k.T, C.byref(k.cr), C.byref(k.od), C.c_void_p(k.stream)))
     return k.result()
 
@@ -515,8 +526,11 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
     (``bf_gsf_ekf_missing_f32``, DESIGN.md 4b'): every component of the bank conditions on the observed rows only, a step with
     none leaves means and covariances untouched with log-likelihood 0 (the weights are renormalised only), trailing gaps are a
     forecast.  Any dimensions: the register kernels take registry models with n <= 8 and m <= 4 and models from source with
-    every dimension <= 8; everything larger -- and any call with ``options={"force_generic": 1}`` -- runs on the
-    run-time-dimension kernel (``bf_gsf_ekf_missing_anydim_f32``, DESIGN.md 4a''; no collapsed streams there).  The unscented
+    every dimension <= 8; models the plain call runs on the one-wave matrix-core kernel (9 <= n <= 32, linear emission,
+    linear / Lorenz-96 / sine dynamics, K <= 64, per-step tables included) run on its MISSING instance
+    (``bf_gsf_ekf_missing_tiles_f32``, DESIGN.md 4a'''); everything else -- and any call with
+    ``options={"force_generic": 1}`` -- runs on the run-time-dimension kernel (``bf_gsf_ekf_missing_anydim_f32``, DESIGN.md
+    4a''; no collapsed streams on either).  The unscented
     bank keeps its limit (every dimension <= 8).  Without it a NaN poisons its trajectory, as ever; +-Inf is never "missing".
     ``observed``: a bool mask of shape (T,), (B, T), (T, m) or (B, T, m), true where the entry was observed; it implies
     ``missing="nan"`` (see :func:`kalman_filter`).
@@ -548,7 +562,7 @@ def gaussian_sum_filter(params, emissions, num_components: int = 1, num_iter: in
     # (_uparams: the unscented bank -- same carry / streams, sigma-point moment matching instead of Jacobians)
     if _uparams is None:
         c = k.mdl.c
-        fn = getattr(lib, _gapped_entry("gsf", c.n, c.m, c.dq, c.dr, bool(c.user), options)) if gaps else lib.bf_gsf_ekf_f32
+        fn = getattr(lib, _gapped_route(_gapped_entry("gsf", c.n, c.m, c.dq, c.dr, bool(c.user), options), options)) if gaps else lib.bf_gsf_ekf_f32
         head = ()
     else:
         fn, head = (lib.bf_ugsf_ukf_missing_f32 if gaps else lib.bf_ugsf_ukf_f32), (C.byref(_uparams),)
