@@ -196,7 +196,7 @@ def test_optimal_variant(nc):
                                           ((100, 2, 2), True), ((130, 2, 3), False)])
 def test_trees_wider_than_a_wave(nc, unscented):
     """num_components = [100, 2, 2] is what BOT_Experiment_script.py:118 runs: 400 leaves = one 512-thread workgroup
-    per trajectory (reductions and the cumulative sum continue across waves); 105 and 180 leaves use 256 threads, 780 leaves 1024."""
+    per trajectory (reductions and the cumulative sum continue across waves); 70 and 105 leaves use 128 threads, 180 leaves 256, 780 leaves 1024."""
     bfa, nl = _nl()
     T, B = 8, 2
     mu0 = np.array([2.0, 0.3, 3.0, -0.2], F32)
